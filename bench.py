@@ -18,6 +18,11 @@ MLP + 3 8x128 object MLPs, bf16 MFMA GEMMs (fp32 accumulate, fp32 everywhere els
 GPU (weak scaling: the global batch is 4096*N rays, sharded contiguously).  `--config` selects
 cfg2 (CARLA, K=1, far=200), cfg4 (Waymo + box-pose optimisation, 1024 rays/GPU) or cfg5 (K=8,
 1024 rays/GPU).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what the headline does not need: the
+CPU baseline, the live vendor-GEMM calibration, the single-stream pass of the roofline kernels and (default headline, one
+GPU) the short passes over the other workloads and the eval mode.  `--dump-outputs DIR` writes what the timed path computed
+in its last timed step as DIR/<name>.npy, so that two builds can be compared output for output on identical seeded inputs.
 """
 import argparse
 import gc
@@ -73,10 +78,15 @@ def parse_args():
     ap.add_argument('--prewarm-events', type=int, default=768,
                     help='timing events recorded (and kept alive) before the warm-up: grows the HIP runtime\'s event pool there')
     ap.add_argument('--max-ahead', type=int, default=0, help='bound the number of steps the host may enqueue ahead of the GPU (0 = unbounded)')
-    ap.add_argument('--no-calibration', action='store_true', help='skip the vendor-GEMM board calibration line')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also the CPU baseline, the board calibration, the single-stream roofline pass and (default headline, '
+                         'one GPU) the other workloads + eval -- a plain run times the headline alone')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy')
+    ap.add_argument('--no-calibration', action='store_true', help='--full: skip the vendor-GEMM board calibration line')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--no-workloads', action='store_true',
-                    help='skip the short passes over the other BASELINE.json configurations (`workloads` in the JSON line)')
+                    help='--full: skip the short passes over the other BASELINE.json configurations (`workloads` in the JSON line)')
     ap.add_argument('--profile-ops', action='store_true', help='print the per-op time table to stderr')
     ap.add_argument('--main-priority', type=int, default=0,
                     help='experiment: run the step loop on a stream of this priority (-1 = high), so that side-stream work '
@@ -321,6 +331,8 @@ def run_eval(args, dev, cfg_name, steps, warmup, image_call=False, one_call=Fals
     e1.record()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:           # the last image render_image returned
+        dump_outputs(args.dump_outputs, dict(rgb=rgb, distance=dist_, acc=acc))
     totals = ops.timer_totals()
     ops.recycle_timers()
     ops.TIMERS = None
@@ -378,6 +390,46 @@ def flush_c_stdio():
         pass
 
 
+DUMP_LIMIT = 64 << 20       # bytes of all --dump-outputs files together
+DUMP_SAMPLE = 1 << 21       # an array with more elements is written as a fixed, seeded sample of this many of its entries
+
+
+def dump_outputs(out_dir, named):
+    """--dump-outputs: `named` (name -> tensor, number, list of them or dataclass of them) as out_dir/<name>.npy -- float32,
+    float64 where the value is a 64-bit float or an integer; list entries and dataclass fields get `_<index>` / `_<field>`."""
+    import dataclasses
+    import numpy as np
+    import torch
+    arrays = {}
+
+    def put(name, v):
+        if v is None:
+            return
+        if dataclasses.is_dataclass(v):
+            for f in dataclasses.fields(v):
+                put('%s_%s' % (name, f.name), getattr(v, f.name))
+            return
+        if isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                put('%s_%d' % (name, i), x)
+            return
+        t = torch.as_tensor(v).detach()
+        t = t.to(torch.float32 if (t.is_floating_point() and t.element_size() <= 4) else torch.float64)
+        a = t.cpu().numpy()
+        if a.size > DUMP_SAMPLE:     # (the same indices in every run: the sample depends on the array's size alone)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        arrays[name] = a
+
+    for k, v in named.items():
+        put(k, v)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit('--dump-outputs: %d bytes over the %d-byte limit' % (total, DUMP_LIMIT))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+
+
 # algorithmic HBM bytes per sample of the three background-MLP launches (DESIGN.md 4: what each kernel has to write / read
 # once -- bf16 stash of 8 ReLU layers + view layer + masks + encoding tile; dz of the same layers; both operands of 10 GEMMs)
 BYTES_FWD, BYTES_BWD, BYTES_DW = 4640 + 128, 4384, 9088
@@ -402,10 +454,10 @@ def pmc_entry(lib_version, workload, rays, kernel):
     return None
 
 
-def run_train(args, cfg_name, dev, rank, world, steps, warmup, rays=0, objects=-1, precision='bf16', light=False):
+def run_train(args, cfg_name, dev, rank, world, steps, warmup, rays=0, objects=-1, precision='bf16', light=False, dump=None):
     """Warm-up + timed region of one training workload on this rank; rank 0 returns the result dict (the JSON line's keys),
     the other ranks None.  light: one of the extra `workloads` passes -- no CPU baseline, board calibration or single-stream
-    pass."""
+    pass, which only --full runs anyway.  dump: rank 0 writes the train state and stats of the last timed step there."""
     import torch
     import torch.distributed as dist
     from durf_amd import _lib, ops, train_boxpose
@@ -437,6 +489,7 @@ def run_train(args, cfg_name, dev, rank, world, steps, warmup, rays=0, objects=-
     # timing events, none after this pre-warm even with --warmup 2).  `step_ms` in the JSON line (p50 / p90 / max /
     # slow_steps) shows any such outlier.
     profile_ops = args.profile_ops and not light
+    full = args.full and not light
     # The step runs through the ONE C call (durf_train_step: the drop-in boundary itself; bit-identical to the Python-issued
     # launches of train_step and 1-3 % faster -- no interpreter between the launches) wherever that entry point covers the
     # workload; its timing hooks (durf_train_args.timing) record the same HIP events around the same launches.  --python-step
@@ -498,11 +551,13 @@ def run_train(args, cfg_name, dev, rank, world, steps, warmup, rays=0, objects=-
     totals = ops.timer_totals()
     ops.TIMERS = None
     ops.TIMERS_ACTIVE = True
+    if dump and rank == 0:          # (before the single-stream pass below, which updates the same buffers in place)
+        dump_outputs(dump, dict(params=state.variables.flat, adam_m=state.m, adam_v=state.v, step=state.step, stats=stats))
     # With the object launches on a side stream the timed background kernels share the chip with them for part of their
     # run, and their live durations say so.  A short extra pass on ONE stream (outside the timed region; every rank takes
     # part, the step holds the collective) gives the same kernels' undisturbed durations: `roofline.single_stream`.
     totals_ss = None
-    if (not light and K_OBJ and model.object_precision() == 'bf16' and ops.overlap_mode(B * NS) != '0' and not profile_ops):
+    if (full and K_OBJ and model.object_precision() == 'bf16' and ops.overlap_mode(B * NS) != '0' and not profile_ops):
         keep_mode = ops._MODE
         ops.set_overlap_mode('0')
         ops.TIMERS = {}
@@ -604,13 +659,13 @@ def run_train(args, cfg_name, dev, rank, world, steps, warmup, rays=0, objects=-
         if totals_ss:
             roof['single_stream'] = {k: dict(us=sv / nv * 1e6, frac=mfma[k] / (sv / nv) / peak)
                                      for k, (nv, sv) in totals_ss.items() if k in mfma}
-        if not light and not args.no_calibration and not f32:
+        if full and not args.no_calibration and not f32:
             roof['board'] = board_calibration(dev, info[max(mlp, key=lambda k: info[k]['achieved'])]['achieved'])
     if profile_ops:
         for k, (n, s) in sorted(totals.items(), key=lambda kv: -kv[1][1]):
             print('%-22s calls %4d  total %8.2f ms  per step %7.3f ms' % (k, n, s * 1e3, s * 1e3 / sampled),
                   file=sys.stderr)
-    cb = None if (light or args.no_cpu_baseline or world > 1) else cpu_baseline(batch_np, K_OBJ, NS, config)   # rank 0, N = 1 only
+    cb = None if (not full or args.no_cpu_baseline or world > 1) else cpu_baseline(batch_np, K_OBJ, NS, config)   # rank 0, N = 1 only
     out = dict(metric='train_rays_per_sec', value=B * world * steps / dt, unit='rays/s',
                n_gpus=world, steps=steps, warmup=warmup, ms_per_step=dt / steps * 1e3,
                higher_is_better=True, scaling='weak', vs_baseline=None, dtype=precision, data='synthetic',
@@ -641,8 +696,8 @@ def run_train(args, cfg_name, dev, rank, world, steps, warmup, rays=0, objects=-
 
 
 # The other BASELINE.json configurations, the reference's own batch size and its own arithmetic: short passes behind the
-# headline's timed region, summarised under `workloads` in the same JSON line (N = 1, default headline only; --no-workloads
-# skips them).  name -> (config, rays per GPU (0 = the config's), precision, steps, warm-up)
+# headline's timed region, summarised under `workloads` in the same JSON line (--full, N = 1, default headline only;
+# --no-workloads skips them).  name -> (config, rays per GPU (0 = the config's), precision, steps, warm-up)
 EXTRA_WORKLOADS = [          # (the small steps get as many steps as the headline: a 40-step pass of a 0.4 ms step read 8 % low)
     ('cfg1', 'cfg1', 0, 'bf16', 200, 20),
     ('cfg2', 'cfg2', 0, 'bf16', 40, 5),
@@ -701,10 +756,10 @@ def main():
     _ops.EVENT_POOL.extend(prewarm)          # ... and they are the timing events the one-call step is handed (ops._step_timing)
 
     out = run_train(args, args.config, dev, rank, world, args.steps, args.warmup, rays=args.rays, objects=args.objects,
-                    precision=args.precision)
+                    precision=args.precision, dump=args.dump_outputs)
     default_headline = (args.config == 'cfg3' and args.rays == 0 and args.objects < 0 and args.precision == 'bf16' and
                         not args.force_dist and not args.profile_ops)
-    if world == 1 and default_headline and not args.no_workloads:
+    if world == 1 and default_headline and args.full and not args.no_workloads:
         extra = {}
         for name, cfg, rays, prec, steps, warm in EXTRA_WORKLOADS:
             try:

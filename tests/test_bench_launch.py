@@ -85,3 +85,29 @@ def test_extra_workloads_cover_every_baseline_config():
     assert s['dominant'] == 'mlp_dw_256' and s['bound'] == 'hbm' and s['frac'] == 0.3 and s['mfma_frac'] == 0.3
     assert s['hbm_dataflow_frac'] == 0.7
     assert s['rays_per_s'] == 1.0 and s['ms_per_step'] == 2.0
+
+
+def test_dump_outputs_writes_every_field_as_float_arrays(tmp_path):
+    """--dump-outputs: dataclass fields and list entries by name, float32 / float64, a large array as the same seeded sample
+    in every run, and nothing written past the size limit"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from durf_amd import utils
+    big = torch.arange(bench.DUMP_SAMPLE + 5, dtype=torch.float32)
+    stats = utils.Stats(loss=torch.tensor(0.25), weights=[torch.ones(4, 3), torch.zeros(4, 3, dtype=torch.bfloat16)],
+                        multi_hit_rays=torch.tensor(2, dtype=torch.int64))
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), dict(params=big, step=7, stats=stats))
+    a = {f: np.load(str(tmp_path / 'a' / f)) for f in os.listdir(str(tmp_path / 'a'))}
+    assert a['stats_loss.npy'].dtype == np.float32 and float(a['stats_loss.npy']) == 0.25
+    assert a['stats_weights_0.npy'].shape == (4, 3) and a['stats_weights_1.npy'].dtype == np.float32
+    assert a['stats_multi_hit_rays.npy'].dtype == np.float64 and float(a['stats_multi_hit_rays.npy']) == 2.0
+    assert a['step.npy'].dtype == np.float64 and float(a['step.npy']) == 7.0
+    p = a['params.npy']
+    assert p.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(p) > 0)      # a sorted sample of distinct entries
+    assert np.array_equal(p, np.load(str(tmp_path / 'b' / 'params.npy')))
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / 'c'), {'x%d' % i: big for i in range(9)})
+    assert not os.path.exists(str(tmp_path / 'c'))

@@ -7,8 +7,9 @@ of JAX but array arithmetic, `lax.stop_gradient`, `jax.linearize` and `jax.rando
 from /root/reference with a numpy-backed stand-in registered as the `jax` module (float64; linearize by central
 differences; uniform draws replayed from the arrays the oracle is handed), and every one is compared with its
 restatement in the oracle on the same random inputs.  A stand-in library pins nothing about JAX's arithmetic -- it
-catches a mistyped formula, a swapped argument, a wrong axis.  Nothing here travels to the GPU box: the test is skipped
-where /root/reference is absent, and no reference text is copied into the repo."""
+catches a mistyped formula, a swapped argument, a wrong axis.  No reference text is copied into the repo: what the
+reference's functions returned on these seeded inputs is stored in tests/golden/ref_crosscheck.npz (tests/ref_record.py),
+and the oracle is checked against that wherever the tests run; DURF_RECORD_REFERENCE=1 re-records it from the reference."""
 import importlib
 import os
 import sys
@@ -19,11 +20,13 @@ import pytest
 import torch
 
 REF = '/root/reference'
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'internal')), reason='reference tree not present')
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import durf_ref as R  # noqa: E402
+from tests import ref_record  # noqa: E402
+
+REC = ref_record.Recorder('ref_crosscheck')
 
 
 class _Uniform:
@@ -79,13 +82,17 @@ def _install_numpy_jax():
 
 @pytest.fixture(scope='module')
 def ref():
+    if not ref_record.recording():
+        yield REC.calls(None)
+        return
     saved = {k: sys.modules.get(k) for k in ('jax', 'jax.numpy', 'jax.lax', 'jax.random', 'jax.scipy', 'internal')}
     _install_numpy_jax()
     sys.path.insert(0, REF)
     for k in [k for k in sys.modules if k == 'internal' or k.startswith('internal.')]:
         del sys.modules[k]
     mods = types.SimpleNamespace(**{n: importlib.import_module('internal.' + n) for n in ('math', 'mip', 'mip360', 'box_helpers')})
-    yield mods
+    yield REC.calls(mods)
+    REC.save()
     sys.path.remove(REF)
     for k in [k for k in sys.modules if k == 'internal' or k.startswith('internal.')]:
         del sys.modules[k]

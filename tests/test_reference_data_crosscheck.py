@@ -4,7 +4,9 @@
     readers, are dummies) -- origins, directions, viewdirs, radii, near, far of every camera, bit for bit;
   * SSIM: `math.compute_ssim` (internal/math.py:66-140) under the numpy stand-ins (jax.scipy.signal.convolve2d -> scipy,
     a real vmap over the channel axis) -- value and map.
-These are the restatements the device ray generator (csrc/data.hip) and durf_ssim are tested against on the GPU."""
+These are the restatements the device ray generator (csrc/data.hip) and durf_ssim are tested against on the GPU.
+What the reference returned on these seeded inputs is stored in tests/golden/ref_data_crosscheck.npz (tests/ref_record.py)
+and checked against wherever the tests run; DURF_RECORD_REFERENCE=1 re-records it from the reference."""
 import os
 import sys
 import types
@@ -15,16 +17,21 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import durf_data_ref as D  # noqa: E402
-from tests import ref_standin  # noqa: E402
+from tests import ref_record, ref_standin  # noqa: E402
 
-pytestmark = pytest.mark.skipif(not ref_standin.available(), reason='reference tree not present')
+REC = ref_record.Recorder('ref_data_crosscheck')
+RAY_FIELDS = ('origins', 'directions', 'viewdirs', 'radii', 'lossmult', 'near', 'far')
 
 
 @pytest.fixture(scope='module')
 def ref():
+    if not ref_record.recording():
+        yield REC.calls(None)
+        return
     mods = ref_standin.load(dataset=True)
-    yield mods
+    yield REC.calls(mods)
     ref_standin.unload()
+    REC.save()
 
 
 def _rig(seed, n_cam=3):
@@ -43,12 +50,16 @@ def _rig(seed, n_cam=3):
 
 def test_generate_rays_multi(ref):
     h, w, focal, pp, c2w = _rig(0)
-    self = types.SimpleNamespace(h=h, w=w, focal=focal, principal_point=pp, camtoworlds=c2w, near=0.0, far=40.0,
-                                 timesteps=np.arange(len(h)))
-    ref.obbpose_dataset.Waymo._generate_rays_multi(self)
+
+    def reference():
+        self = types.SimpleNamespace(h=h, w=w, focal=focal, principal_point=pp, camtoworlds=c2w, near=0.0, far=40.0,
+                                     timesteps=np.arange(len(h)))
+        ref.obbpose_dataset.Waymo._generate_rays_multi(self)
+        return [getattr(self.rays, name) for name in RAY_FIELDS]
+    rays = dict(zip(RAY_FIELDS, REC.outputs('rays', reference)))
     want = D.generate_rays_multi(h, w, focal, pp, c2w, near=0.0, far=40.0)
-    for name in ('origins', 'directions', 'viewdirs', 'radii', 'lossmult', 'near', 'far'):
-        got = getattr(self.rays, name)
+    for name in RAY_FIELDS:
+        got = rays[name]
         assert len(got) == len(want[name]) == len(h)
         for cam, (g, x) in enumerate(zip(got, want[name])):
             g, x = np.asarray(g, dtype=np.float64), np.asarray(x, dtype=np.float64)

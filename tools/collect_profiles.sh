@@ -10,7 +10,7 @@ cfg=${2:-cfg3}
 out=/root/repo/gpurun_out/$tag
 mkdir -p $out
 cd /root/repo
-python3 bench.py --config $cfg > $out/bench.json 2> $out/bench.err      # the default line, exactly as the driver runs it
+python3 bench.py --config $cfg --full > $out/bench.json 2> $out/bench.err      # the full line: CPU baseline, vendor GEMM, other workloads
 python3 bench.py --config $cfg --steps 50 --profile-ops --no-cpu-baseline --no-workloads > $out/bench_all_ops_timed.json 2> $out/bench_op_times.txt   # full per-op table (every op timed)
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/p_stats

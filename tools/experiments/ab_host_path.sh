@@ -8,7 +8,7 @@ echo "# bench.py <workload> --no-workloads --no-cpu-baseline [--python-step], in
 for w in "--config cfg3" "--config cfg3 --rays 512" "--config cfg1" "--config cfg2" "--config cfg4" "--config cfg5"; do
   for rep in 1 2 3; do
     for m in "" "--python-step"; do
-      python3 bench.py $w --no-workloads --no-cpu-baseline $m 2>/dev/null | python3 -c "
+      python3 bench.py $w --full --no-workloads --no-cpu-baseline $m 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('%-28s %-14s %8.1f k  (%.4f ms)  vendor GEMM %4.0f TFLOP/s' % ('$w', d['config']['host_path'][:12], d['value'] / 1e3, d['ms_per_step'], d['roofline']['board']['vendor_gemm_tflops']))" >> $out

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One table of current numbers from a default `python bench.py` JSON line (README):
+"""One table of current numbers from a `python bench.py --full` JSON line (README):
     python tools/make_results_table.py profiles/r06_bench.json [BENCH_r05.json ...]
 First file = the line the table is made of; further files (driver records `BENCH_rNN.json` or earlier bench lines) add a
 column each with that file's rays/s per workload."""

@@ -4,11 +4,12 @@
 #   512 rays, cfg2 / cfg4 / cfg5, the eval (render_image) mode, and the forced world-size-1 RCCL path
 out=/root/repo/gpurun_out/other_workloads.txt
 rm -f $out
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 run() {   # label, bench args...
   local label=$1; shift
   echo "=== $label: python3 bench.py $*" >> $out
-  python3 /root/repo/bench.py "$@" 2>/dev/null | tail -1 >> $out
+  python3 "$root/bench.py" --full "$@" 2>/dev/null | tail -1 >> $out
   rm -rf /tmp/p_ow
   rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_ow -- python3 /root/repo/bench.py "$@" --steps 10 --warmup 12 --no-cpu-baseline --no-calibration --no-workloads > /dev/null 2>&1
   echo "--- rocprofv3 --kernel-trace --stats, 22 steps (eval: 12 images)" >> $out
