@@ -59,3 +59,13 @@ def slow_fuzz_seeds(seeds):
     included whenever DURF_FUZZ_EXTRA is set"""
     import os
     return list(seeds) if int(os.environ.get('DURF_FUZZ_EXTRA', '0')) > 0 else []
+
+
+def subset_batch(b, idx):
+    """the rays `idx` (in that order) of a make_batch batch; the per-batch fields (boxes, timestep) are kept"""
+    idx = np.asarray(idx, dtype=np.int64)
+    out = {k: (v[idx] if k in ('pixels', 'depth', 'sky') else v) for k, v in b.items() if k != 'rays'}
+    out['rays'] = {k: np.ascontiguousarray(v[idx]) for k, v in b['rays'].items()}
+    for k in ('pixels', 'depth', 'sky'):
+        out[k] = np.ascontiguousarray(out[k])
+    return out

@@ -11,6 +11,7 @@ import torch
 from durf_amd import obbpose_model, ops, synthetic, train_boxpose, utils
 from oracle import durf_ref as R
 from tests import helpers as H
+from tests import layer_grads as LG
 
 pytestmark = pytest.mark.gpu
 
@@ -100,6 +101,9 @@ def test_gradients_match_the_sample_by_sample_path_and_the_oracle(cuda, B, K, N)
                                         ob['init'][0:1], noise=noise_c, mlp_hook=R.mlp_apply_bf16)
     og = torch.cat([x.reshape(-1) for x in ograds])
     assert _rel(grads[True].cpu()[sl], og[sl]) < 5e-2
+    pcs = LG.pieces_for(lay, b['ts'])
+    print(LG.compare(grads[True], og, pcs, LG.GATES['bf16'], LG.structural_zeros(pcs, unhit=LG.unhit_objects(ob, b['ts'])),
+                     title='dedup B=%d K=%d' % (B, K)))
 
 
 @pytest.mark.parametrize('case', ['all_rays_hit', 'no_ray_hits'])

@@ -72,6 +72,7 @@ def _bf16_objects_with_pose_gradient(cuda):
     from durf_amd import obbpose_model, synthetic, train_boxpose, utils
     from oracle import durf_ref as R
     from tests import helpers as H
+    from tests import layer_grads as LG
     B, N, K, alpha = 1024, 32, 1, 10.0
     utils.clear_gin()
     utils.parse_gin('MipNerfModel.num_samples = %d\nMipNerfModel.density_noise = 0.0\nMipNerfModel.obj_precision = "bf16"\n'
@@ -96,6 +97,10 @@ def _bf16_objects_with_pose_gradient(cuda):
     og = torch.cat([x.reshape(-1) for x in ograds])
     so = slice(lay.mlp_off['BoxMLP_0'], lay.mlp_off['BoxMLP_0'] + lay.mlp_size[128])
     assert rel(grad.cpu()[so], og[so]) < 5e-2
+    # per piece, every MLP (the box-pose rows are held below)
+    pcs = LG.pieces_for(lay, ts)
+    print(LG.compare(grad, og, pcs, LG.GATES['bf16'], LG.structural_zeros(pcs, frozen_pose=False, unhit=LG.unhit_objects(ob, ts)),
+                     title='bf16 objects with the pose gradient'))
     got, want = grad[lay.box[0]:lay.box[1]].view(lay.T, K, 6).cpu()[ts], ograds[0][ts]
     assert float(want.abs().max()) > 0
     assert rel(got[:, :3], want[:, :3]) < 0.1 and rel(got[:, 3:], want[:, 3:]) < 0.3, (got, want)

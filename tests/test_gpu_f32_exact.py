@@ -11,6 +11,7 @@ import torch
 from durf_amd import obbpose_model, ops, synthetic, train_boxpose, utils
 from oracle import durf_ref as R
 from tests import helpers as H
+from tests import layer_grads as LG
 
 pytestmark = pytest.mark.gpu
 
@@ -153,6 +154,9 @@ def test_train_step_fp32_exact(cuda, K, N, B):
         if float(og[sl].norm()) > 0:
             r = _rel(grad.cpu()[sl], og[sl])
             assert r < 1e-3, '%s grad rel err %g' % (name, r)
+    pcs = LG.pieces_for(lay, b['ts'])
+    print(LG.compare(grad, og, pcs, LG.GATES['f32'], LG.structural_zeros(pcs, unhit=LG.unhit_objects(ob, b['ts'])),
+                     title='fp32 exact K=%d N=%d B=%d' % (K, N, B)))
     torch.testing.assert_close(stats.grad_norm.cpu(), ostats['grad_norm'], rtol=1e-3, atol=0)
     # post-Adam parameters: the first step moves every weight by lr * sign(g) (bias-corrected Adam), so the update
     # only differs where a gradient is so close to zero that fp32 summation order decides its sign: <= 5e-2 here

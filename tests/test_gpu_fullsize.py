@@ -11,6 +11,7 @@ import torch
 
 from durf_amd import obbpose_model, ops, synthetic, train_boxpose, utils
 from tests import helpers as H
+from tests import layer_grads as LG
 
 pytestmark = pytest.mark.gpu
 B, N = 4096, 128
@@ -268,6 +269,17 @@ def test_per_rank_shapes_of_cfg5_and_cfg4_at_128_samples(cuda, K, pose_opt, alph
         if float(f['grad'][sl].norm()) > 0:
             r = _rel(a['grad'][sl], f['grad'][sl])
             assert r < 5e-2, '%s: bf16 vs exact-fp32 gradient rel err %g' % (name, r)
+    # per piece, bf16 against the exact-fp32 instrument (no oracle here, so no structural zeros: exact zeros of the
+    # instrument have to be exact zeros of the production path all the same).  MLP_0 at the bf16-vs-fp32 gates (measured
+    # 6.9e-2 / 7.1e-2).  The object MLPs of cfg5 (K = 8 on 1,024 rays, measured 0.26 on BoxMLP_1's Dense_0 bias, 0.24 Dense_1,
+    # 0.20-0.22 kernels, falling with depth to < 1e-2 at the head) sit above that ceiling, and that is bf16 rounding itself:
+    # on this batch (make_batch(1024, 8, seed=98, far=40), N = 128, bf16-representable glorot weights, this test's sampling
+    # noise) the CPU oracle with bf16-rounded GEMM operands (R.mlp_apply_bf16) is as far from the plain fp32 oracle --
+    # BoxMLP_1 Dense_0 bias 0.263, Dense_1 bias 0.248, Dense_0 / Dense_1 kernels 0.219 / 0.201, MLP_0 at most 0.069 (~70 s on
+    # the CPU, too slow for the suite).  Held at 0.75: a zeroed (1.0) or sign-flipped (2.0) piece still fails.
+    gates = dict(LG.GATES['bf16_vs_f32'], **({} if pose_opt else {'BoxMLP.kernel': 0.75, 'BoxMLP.bias': 0.75}))
+    pcs = LG.pieces_for(lay, a['ts'])
+    print(LG.compare(a['grad'], f['grad'], pcs, gates, title='per-rank shape K=%d pose_opt=%s' % (K, pose_opt)))
     if pose_opt:
         # The pose gradient is a sum over ~100 hit rays x 128 samples that cancels to ~1 % of its summed magnitudes, so
         # bf16 rounding anywhere on the hit rays used to leave 3-38 % on it (round 2; tools/pose_grad_ablate.py shows the
@@ -377,6 +389,13 @@ def test_gradients_at_the_reference_batch_and_128_samples_against_the_oracle(cud
                 r = _rel(grad[sl], og[sl])
                 report.append('%s %.2e' % (name, r))
                 assert r < tol, '%s (%s): gradient rel err %g' % (name, prec, r)
+        # per piece: the exact-fp32 kernels at the 'f32' gates, the bf16 path at the bf16-vs-fp32 ones -- its object MLPs at
+        # the 'f32' gates under pose optimisation, where the box-hit rays run in fp32 (the box-pose rows are held above)
+        pcs = LG.pieces_for(lay, ts)
+        gates = LG.GATES['f32'] if prec == 'f32' else LG.mixed_gates('bf16_vs_f32', 'f32' if pose_opt else 'bf16_vs_f32')
+        print(LG.compare(grad, og, pcs, gates,
+                         LG.structural_zeros(pcs, frozen_pose=not pose_opt, unhit=LG.unhit_objects(ob, ts)),
+                         title='reference batch B=%d K=%d pose_opt=%s %s' % (B, K, pose_opt, prec)))
         got = grad[lay.box[0]:lay.box[1]].view(lay.T, K, 6)
         if pose_opt:
             assert float(want[ts].abs().max()) > 0

@@ -9,6 +9,7 @@ import torch
 from durf_amd import obbpose_model, synthetic, train_boxpose, utils
 from oracle import durf_ref as R
 from tests import helpers as H
+from tests import layer_grads as LG
 
 pytestmark = pytest.mark.gpu
 
@@ -98,6 +99,8 @@ def test_train_step_without_view_directions(cuda, precision):
     lay = variables.layout
     o9 = lay.mlp_off['MLP_0'] + lay.mlp_size[obbpose_model.W_BKGD] - (256 * 3 + 3)
     assert float(og[o9:].norm()) > 0 and _rel(grad.cpu()[o9:], og[o9:]) < gt, 'the rgb head (Dense_9) on its own'
+    # every piece of the 10-Dense tree (weight decay is on: no structural zeros)
+    print(LG.compare(grad, og, LG.pieces_for(lay, b['ts']), LG.GATES[precision], title='no view directions, %s' % precision))
     newflat = torch.cat([x.reshape(-1) for x in R.params_leaves(p2)])
     assert _rel(new_state.variables.flat.cpu() - flat0.cpu(), newflat - flat0.cpu()) < (0.15 if precision == 'bf16' else 0.02)
     assert new_state.step == 1

@@ -9,6 +9,7 @@ import torch
 from durf_amd import obbpose_model, ops, synthetic, train_boxpose, utils
 from oracle import durf_ref as R
 from tests import helpers as H
+from tests import layer_grads as LG
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -192,6 +193,10 @@ def test_train_step(cuda, K, N, B):
         sl = slice(lay.mlp_off[name], lay.mlp_off[name] + lay.mlp_size[w])
         if float(og[sl].norm()) > 0:
             assert _rel(grad.cpu()[sl], og[sl]) < 5e-2, '%s grad rel err %g' % (name, _rel(grad.cpu()[sl], og[sl]))
+    # every Dense layer's kernel / bias (and row blocks) on its own (tests/layer_grads.py)
+    pcs = LG.pieces_for(lay, b['ts'])
+    print(LG.compare(grad, og, pcs, LG.GATES['bf16'], LG.structural_zeros(pcs, unhit=LG.unhit_objects(ob, b['ts'])),
+                     title='train_step K=%d N=%d B=%d' % (K, N, B)))
     torch.testing.assert_close(stats.grad_norm.cpu(), ostats['grad_norm'], rtol=3e-2, atol=0)
     # post-Adam parameters: the first Adam step moves every weight by ~lr*sign(g)
     newflat = torch.cat([x.reshape(-1) for x in R.params_leaves(p2)])
@@ -262,6 +267,16 @@ def test_box_pose_gradients(cuda, K, alpha, tv, knobs):
     og = torch.cat([x.reshape(-1) for x in ograds]).float()
     sl = slice(lay.mlp_off['MLP_0'], lay.mlp_off['MLP_0'] + lay.mlp_size[256])
     assert _rel(grad.cpu()[sl], og[sl]) < 5e-2
+    # per piece: the bf16 background against the plain oracle, the fp32 object MLPs at the fp32 gates (measured 1.4e-6..9.5e-6;
+    # the box-pose rows are held above, per object).  Un-integrated encodings: the float64 oracle, against which fp32 itself
+    # is the limit (see above) -- measured up to 6.4e-2 on the objects' Dense_0..2, falling with depth: held at 0.2
+    gates = LG.mixed_gates('bf16_vs_f32', 'f32')
+    if undamped:
+        gates.update({'BoxMLP.kernel': 0.2, 'BoxMLP.bias': 0.2})
+    pcs = LG.pieces_for(lay, ts)
+    print(LG.compare(grad, og, pcs, gates,
+                     LG.structural_zeros(pcs, frozen_pose=False, unhit=LG.unhit_objects(ob, ts)),
+                     title='box pose K=%d alpha=%g %s' % (K, alpha, knobs)))
 
 
 def test_pose_chain_fp32(cuda):
@@ -415,6 +430,9 @@ def test_train_step_with_other_level_counts(cuda, L, K):
         sl = slice(lay.mlp_off[name], lay.mlp_off[name] + lay.mlp_size[w])
         if float(og[sl].norm()) > 0:
             assert _rel(grad.cpu()[sl], og[sl]) < 5e-2, '%s grad rel err %g' % (name, _rel(grad.cpu()[sl], og[sl]))
+    pcs = LG.pieces_for(lay, b['ts'])
+    print(LG.compare(grad, og, pcs, LG.GATES['bf16'], LG.structural_zeros(pcs, unhit=LG.unhit_objects(ob, b['ts'])),
+                     title='other level counts L=%d K=%d' % (L, K)))
 
 
 @pytest.mark.parametrize('precision', ['bf16', 'f32'])
@@ -471,6 +489,10 @@ def test_train_step_random_configurations(cuda, seed, precision):
         if float(og[sl].norm()) > 0:
             assert _rel(grad.cpu()[sl], og[sl]) < (1e-3 if f32 else 5e-2), 'seed %d %s %s grad rel err %g' % (
                 seed, knobs, name, _rel(grad.cpu()[sl], og[sl]))
+    # per piece; structural zeros only without weight decay (its gradient reaches every leaf)
+    pcs = LG.pieces_for(lay, b['ts'])
+    zeros = LG.structural_zeros(pcs, unhit=LG.unhit_objects(ob, b['ts'])) if knobs['weight_decay_mult'] == 0 else ()
+    print(LG.compare(grad, og, pcs, LG.GATES[precision], zeros, title='random configuration seed %d %s' % (seed, precision)))
     state = train_boxpose.create_train_state(variables)
     new_state, stats, rng, pose = train_boxpose.train_step(model, config, 0, state, db, lr, eps, alpha, prev_d, noise=noise_d)
     for k in ('losses', 'd_losses', 'n_losses', 'e_losses', 's_losses', 'distr_losses'):

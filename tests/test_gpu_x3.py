@@ -10,6 +10,7 @@ import torch
 from durf_amd import obbpose_model, ops, synthetic, train_boxpose, utils
 from oracle import durf_ref as R
 from tests import helpers as H
+from tests import layer_grads as LG
 
 pytestmark = pytest.mark.gpu
 
@@ -54,6 +55,12 @@ def test_pose_and_object_gradients_against_the_oracle(cuda, K, alpha, tv, B, N):
         assert _rel(grad.cpu()[so], og[so]) < 5e-3, 'BoxMLP_%d grad rel err %g' % (k, _rel(grad.cpu()[so], og[so]))
     sl = slice(lay.mlp_off['MLP_0'], lay.mlp_off['MLP_0'] + lay.mlp_size[256])
     assert _rel(grad.cpu()[sl], og[sl]) < 5e-2
+    # per piece: the bf16 background against the plain oracle, the split-operand object MLPs at the fp32 gates (the box-pose
+    # rows are held above, per object)
+    pcs = LG.pieces_for(lay, ts)
+    print(LG.compare(grad, og, pcs, LG.mixed_gates('bf16_vs_f32', 'f32'),
+                     LG.structural_zeros(pcs, frozen_pose=False, unhit=LG.unhit_objects(ob, ts)),
+                     title='bf16x3 K=%d alpha=%g B=%d N=%d' % (K, alpha, B, N)))
 
 
 def test_split_operand_kernels_against_the_exact_ones(cuda):
