@@ -5,22 +5,16 @@
 struct Gauss { float x[3]; float var[3]; };
 struct BarfW { float w[10]; };
 
-// mip.cast_rays / conical_frustum_to_gaussian / lift_gaussian (mip.py:155-179,99-130,76-96);
-// only diag(cov) is ever consumed downstream.
-__device__ __forceinline__ Gauss frustum_gaussian(float t0, float t1, const float* o,
-                                                  const float* d, float radius, bool cylinder = false) {
-    if (cylinder) {                                   // mip.cylinder_to_gaussian (mip.py:133-152)
+// The moments of one frustum along the ray: t_mean, t_var and r_var of mip.conical_frustum_to_gaussian (mip.py:99-130,
+// stable=True) or mip.cylinder_to_gaussian (mip.py:133-152).  One source for the encoders' forward (frustum_gaussian) and
+// the box-pose backward (pose.hip, pose_bkgd.h).
+struct Moments { float t_mean, t_var, r_var; };
+__device__ __forceinline__ Moments frustum_moments(float t0, float t1, float radius, bool cylinder) {
+    if (cylinder) {
         const float t_mean = (t0 + t1) / 2.0f;
         const float r_var = (radius * radius) / 4.0f;
         const float t_var = ((t1 - t0) * (t1 - t0)) / 12.0f;
-        const float dmag = fmaxf(1e-10f, d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        Gauss g;
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            g.x[j] = d[j] * t_mean + o[j];
-            g.var[j] = t_var * (d[j] * d[j]) + r_var * (1.0f - d[j] * (d[j] / dmag));
-        }
-        return g;
+        return Moments{t_mean, t_var, r_var};
     }
     const float mu = (t0 + t1) / 2.0f;
     const float hw = (t1 - t0) / 2.0f;
@@ -30,14 +24,22 @@ __device__ __forceinline__ Gauss frustum_gaussian(float t0, float t1, const floa
     const float t_mean = mu + (2.0f * mu * hw2) / den;
     const float t_var = hw2 / 3.0f - (4.0f / 15.0f) * ((hw4 * (12.0f * mu2 - hw2)) / (den * den));
     const float r_var = (radius * radius) * (mu2 / 4.0f + (5.0f / 12.0f) * hw2 - (4.0f / 15.0f) * hw4 / den);
+    return Moments{t_mean, t_var, r_var};
+}
+
+// mip.cast_rays / lift_gaussian (mip.py:155-179,76-96) on those moments; only diag(cov) is ever consumed downstream
+// (SURVEY.md A.4).
+__device__ __forceinline__ Gauss frustum_gaussian(float t0, float t1, const float* o,
+                                                  const float* d, float radius, bool cylinder = false) {
+    const Moments mo = frustum_moments(t0, t1, radius, cylinder);
     const float dmag = fmaxf(1e-10f, d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
     Gauss g;
 #pragma unroll
     for (int j = 0; j < 3; j++) {
-        g.x[j] = d[j] * t_mean + o[j];
+        g.x[j] = d[j] * mo.t_mean + o[j];
         const float dd = d[j] * d[j];
         const float null_d = 1.0f - d[j] * (d[j] / dmag);
-        g.var[j] = t_var * dd + r_var * null_d;
+        g.var[j] = mo.t_var * dd + mo.r_var * null_d;
     }
     return g;
 }

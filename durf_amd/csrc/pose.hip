@@ -8,9 +8,53 @@
 // k_encode_obj_bwd: one wavefront per hit ray; per sample 60 sin/cos/exp (VALU-bound, but only
 // hit rays are processed); reduces over the ray's samples to d(o'), d(d'), then to the 21
 // per-ray sums that determine dL/dR and dL/dc.  Reduction over rays is a fixed-order row sum.
-#include "gauss.h"
+//
+// k_encode_bkgd_bwd (dynamics=False): the same 21 rows when the pose reaches the loss through the BACKGROUND encoding of
+// the box-hit rays instead: integrated_pos_enc (mip.py:226-282) -> mip360.new_space (mip360.py:47-79) -> cast_rays ->
+// world2object_rpy; plus the rendering's |d_s| (mip.py:305) for rays in several boxes.
+#include "enc_lane.h"
 
 enum { POSE_ROWS = 21 };   // [0..2] sum g_o ; [3..11] sum g_o (x) o ; [12..20] sum g_u (x) d
+
+// The shared tail of both backward kernels: one ray's d(loss)/d(o'), d(loss)/d(d') in the frame of the box `pk` [6] -> its 21
+// pose rows (column `out`, rows `stride` floats apart).  o' = R (o_w - c), u = R d_w, d' = u / |u|  (box_helpers.py:323-340).
+__device__ __forceinline__ void pose_rows(const float* __restrict__ pk, const float* __restrict__ ow_, const float* __restrict__ dw_,
+                                          const float (&go)[3], const float (&gd)[3], float* __restrict__ out, int stride) {
+    const float rx = pk[3], ry = pk[4], rz = pk[5];
+    float s = rx * rx + ry * ry + rz * rz;
+    s = (s < 1e-12f) ? 1e-12f : s;
+    const float th = sqrtf(s) + 1e-12f;
+    const float a = sinf(th) / th, bb = (1.0f - cosf(th)) / (th * th);
+    const float S[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
+    float R[9];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const float s2 = S[i * 3] * S[q] + S[i * 3 + 1] * S[3 + q] + S[i * 3 + 2] * S[6 + q];
+            R[i * 3 + q] = ((i == q) ? 1.0f : 0.0f) + a * S[i * 3 + q] + bb * s2;
+        }
+    const float ow[3] = {ow_[0], ow_[1], ow_[2]};
+    const float dw[3] = {dw_[0], dw_[1], dw_[2]};
+    float u[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) u[i] = R[i * 3] * dw[0] + R[i * 3 + 1] * dw[1] + R[i * 3 + 2] * dw[2];
+    const float nrm = sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    const float dp[3] = {u[0] / nrm, u[1] / nrm, u[2] / nrm};
+    const float dot = dp[0] * gd[0] + dp[1] * gd[1] + dp[2] * gd[2];
+    float gu[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) gu[i] = (gd[i] - dp[i] * dot) / nrm;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        out[(size_t)i * stride] = go[i];
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            out[(size_t)(3 + i * 3 + q) * stride] = go[i] * ow[q];
+            out[(size_t)(12 + i * 3 + q) * stride] = gu[i] * dw[q];
+        }
+    }
+}
 
 // One WORKGROUP per hit ray and object (blockIdx.x = compact ray, blockIdx.y = object of a batched call): the four waves
 // split the 60 encoding features (15 each: the per-sample chain of 60 sin / cos / exp is what a launch waits for -- with
@@ -60,13 +104,9 @@ k_encode_obj_bwd(int B, int N, int k_obj, const int32_t* __restrict__ idx, const
         const int n = lane * P + p;
         if (n >= N) continue;
         const float t0 = t_vals[(size_t)b * (N + 1) + n], t1 = t_vals[(size_t)b * (N + 1) + n + 1];
-        // forward quantities (same formulas as frustum_gaussian)
-        const float mu = (t0 + t1) / 2.0f, hw = (t1 - t0) / 2.0f;
-        const float mu2 = mu * mu, hw2 = hw * hw, den = 3.0f * mu2 + hw2, hw4 = hw2 * hw2;
-        float t_mean = mu + (2.0f * mu * hw2) / den;
-        float t_var = hw2 / 3.0f - (4.0f / 15.0f) * ((hw4 * (12.0f * mu2 - hw2)) / (den * den));
-        float r_var = (radius * radius) * (mu2 / 4.0f + (5.0f / 12.0f) * hw2 - (4.0f / 15.0f) * hw4 / den);
-        if (cyl) { t_mean = mu; r_var = (radius * radius) / 4.0f; t_var = ((t1 - t0) * (t1 - t0)) / 12.0f; }
+        // forward quantities (gauss.h: the encoders' own moments)
+        const Moments mo = frustum_moments(t0, t1, radius, cyl);
+        const float t_mean = mo.t_mean, t_var = mo.t_var, r_var = mo.r_var;
         float x[3], var[3];
 #pragma unroll
         for (int i = 0; i < 3; i++) {
@@ -116,46 +156,13 @@ k_encode_obj_bwd(int B, int N, int k_obj, const int32_t* __restrict__ idx, const
         go[i] = ((part[0][i] + part[1][i]) + part[2][i]) + part[3][i];
         gd[i] = ((part[0][3 + i] + part[1][3 + i]) + part[2][3 + i]) + part[3][3 + i];
     }
-    // o' = R (o_w - c), u = R d_w, d' = u / |u|  (box_helpers.py:323-340)
-    const float* pk = pose + k_obj * 6;
-    const float rx = pk[3], ry = pk[4], rz = pk[5];
-    float s = rx * rx + ry * ry + rz * rz;
-    s = (s < 1e-12f) ? 1e-12f : s;
-    const float th = sqrtf(s) + 1e-12f;
-    const float a = sinf(th) / th, bb = (1.0f - cosf(th)) / (th * th);
-    const float S[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
-    float R[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-            const float s2 = S[i * 3] * S[q] + S[i * 3 + 1] * S[3 + q] + S[i * 3 + 2] * S[6 + q];
-            R[i * 3 + q] = ((i == q) ? 1.0f : 0.0f) + a * S[i * 3 + q] + bb * s2;
-        }
-    const float ow[3] = {origins[b * 3], origins[b * 3 + 1], origins[b * 3 + 2]};
-    const float dw[3] = {dirs[b * 3], dirs[b * 3 + 1], dirs[b * 3 + 2]};
-    float u[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++) u[i] = R[i * 3] * dw[0] + R[i * 3 + 1] * dw[1] + R[i * 3 + 2] * dw[2];
-    const float nrm = sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-    const float dp[3] = {u[0] / nrm, u[1] / nrm, u[2] / nrm};
-    const float dot = dp[0] * gd[0] + dp[1] * gd[1] + dp[2] * gd[2];
-    float gu[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++) gu[i] = (gd[i] - dp[i] * dot) / nrm;
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        rows_out[(size_t)i * B + j] = go[i];
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-            rows_out[(size_t)(3 + i * 3 + q) * B + j] = go[i] * ow[q];
-            rows_out[(size_t)(12 + i * 3 + q) * B + j] = gu[i] * dw[q];
-        }
-    }
+    pose_rows(pose + k_obj * 6, origins + b * 3, dirs + b * 3, go, gd, rows_out + j, B);
     }   // thread 0
     __syncthreads();                                // part[] is reused by the next ray
     }   // rays
 }
+
+#include "pose_bkgd.h"         // k_encode_bkgd_bwd (dynamics=False)
 
 // (nlev levels in the order given: each level's row sum is formed and added exactly as a launch of its own would -- the same bits
 // as one launch per level)
@@ -290,6 +297,30 @@ int durf_encode_obj_bwd_levels(void* stream, int K, int B, int N, int nlevels, c
                                const float* pose, const float* barf_w, float* scratch, float* sums, int precise, int enc_flags) {
     return encode_obj_bwd_launch(stream, K, B, N, 0, idx, count, nullptr, (size_t)B * N * DURF_ENC_DIM, nullptr, origins_s,
                                  dirs_s, radii, origins, dirs, pose, barf_w, scratch, sums, precise, enc_flags, nlevels, d_enc, t_vals);
+}
+
+int durf_encode_bkgd_bwd_batch(void* stream, int K, int B, int N, const int32_t* idx, const int32_t* count,
+                               const float* d_enc, const int32_t* denc_slot, const float* t_vals, const float* origins_s,
+                               const float* dirs_s, const float* radii, const float* origins, const float* dirs,
+                               const float* pose, const float* raw, const float* draw, float density_bias, float* scratch,
+                               float* sums, int enc_flags) {
+    DURF_REQUIRE(N >= 1 && N <= 256, "1 <= N <= 256");
+    DURF_REQUIRE((raw == nullptr) == (draw == nullptr), "raw and draw go together");
+    DURF_REQUIRE((enc_flags & ~(DURF_ENC_CONTRACT | DURF_ENC_CYLINDER | DURF_ENC_NO_INTEGRATION)) == 0,
+                 "enc_flags: DURF_ENC_CONTRACT | DURF_ENC_CYLINDER | DURF_ENC_NO_INTEGRATION");
+    if (B <= 0 || K <= 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid(B < 256 ? B : 256, K), block(256);
+#define LAUNCH_E(P)                                                                                       \
+    hipLaunchKernelGGL((k_encode_bkgd_bwd<P>), grid, block, 0, s, B, N, idx, count, d_enc, denc_slot, t_vals, \
+                       origins_s, dirs_s, radii, origins, dirs, pose, raw, draw, density_bias, scratch, enc_flags)
+    if (N <= 64) LAUNCH_E(1); else if (N <= 128) LAUNCH_E(2); else LAUNCH_E(4);
+#undef LAUNCH_E
+    EncBwdLevels lv{};
+    lv.rows_out[0] = scratch;
+    hipLaunchKernelGGL(k_pose_reduce, dim3(POSE_ROWS, K), dim3(1024), 0, s, B, count, lv, 1, sums);
+    DURF_CHECK_LAUNCH("durf_encode_bkgd_bwd_batch");
+    return 0;
 }
 
 // sums [K,21] (all levels accumulated) -> adds d(loss)/d(box_centers[ts]) into grad6 [K,6]

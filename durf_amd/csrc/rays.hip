@@ -344,13 +344,13 @@ k_encode(int rays, int N, const int32_t* __restrict__ idx, const int32_t* __rest
     }
     // grid-stride over (sample, 8-feature vector) pairs: the object launches cap their grid (the hit count lives on the
     // device; a grid sized for the capacity is thousands of workgroups that only exit)
-    const int nrays = OBJ ? (*count < rays ? *count : rays) : rays;
+    const int nrays = (OBJ || idx) ? (*count < rays ? *count : rays) : rays;      // (idx: a compacted ray list)
     const size_t total = (size_t)nrays * N * 8;
     for (size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x; gid < total; gid += (size_t)gridDim.x * blockDim.x) {
     const size_t row = gid >> 3;          // sample row (ray-major)
     const int q = (int)(gid & 7);         // which 8-feature vector
     const int j = (int)(row / N), n = (int)(row % N);
-    const int b = OBJ ? idx[j] : j;
+    const int b = (OBJ || idx) ? idx[j] : j;
     const float t0 = t_vals[(size_t)b * (N + 1) + n], t1 = t_vals[(size_t)b * (N + 1) + n + 1];
     float o[3] = {origins_s[b * 3], origins_s[b * 3 + 1], origins_s[b * 3 + 2]};
     float d[3] = {dirs_s[b * 3], dirs_s[b * 3 + 1], dirs_s[b * 3 + 2]};
@@ -617,10 +617,10 @@ int durf_encode_bkgd(void* stream, int B, int N, const float* t_vals, const floa
     if (B <= 0) return 0;
     DURF_REQUIRE(((size_t)B * N) % 32 == 0 || out_tile == nullptr, "B*N must be a multiple of 32");
     DURF_REQUIRE((idx == nullptr) == (count == nullptr), "idx and count go together");
-    DURF_REQUIRE(idx == nullptr || out_f32 == nullptr, "the compacted ray list is for the bf16 tile output");
-    if (out_f32)
+    DURF_REQUIRE(idx == nullptr || out_tile == nullptr || out_f32 == nullptr, "a compacted ray list: bf16 tiles OR fp32 features");
+    if (out_f32)          // (idx / count: rows j*N + n of ray idx[j], fp32 -- the box-hit rays of durf_encode_bkgd_bwd_batch's fp32 route)
         hipLaunchKernelGGL((k_encode<false>), dim3(durf_cdiv((size_t)B * N * 8, 256)), dim3(256), 0,
-                           (hipStream_t)stream, B, N, nullptr, nullptr, t_vals, origins_s, dirs_s, radii,
+                           (hipStream_t)stream, B, N, idx, count, t_vals, origins_s, dirs_s, radii,
                            hit, K, contraction, BarfW{}, (bf16x8*)out_tile, out_f32, (size_t)0, (size_t)0);
     else
         hipLaunchKernelGGL((k_encode_lane<false>), dim3(durf_cdiv((size_t)B * N, ENC_BLOCK)), dim3(ENC_BLOCK), 0,

@@ -166,8 +166,18 @@ class MipNerfModel:
     # mlp_precision == 'bf16'.  'auto' = 'f32' when box-pose optimisation is on (no_pose_opt / no_yaw_opt False, cfg4),
     # else 'bf16': d(loss)/d(box pose) is a sum over the hit rays that cancels to ~1 % of its summed magnitudes, so the
     # bf16 rounding of the object branch shows up as tens of per cent on it -- the background MLP, whose
-    # weights only see MLP gradients, stays on the bf16 MFMA kernels either way.
+    # weights only see MLP gradients, stays on the bf16 MFMA kernels either way.  dynamics=False has no object branch; with
+    # pose optimisation the pose gradient runs through the background MLP's d(enc) of the box-hit rays, and this knob governs
+    # THAT evaluation: 'auto' / 'f32' = those rays' background forward, backward and share of MLP_0's weight gradient on the
+    # exact-fp32 kernels (static_hit_f32; the bf16 route measured 0.11-0.73 from the oracle), 'bf16' = the
+    # bf16 backward's d(enc); 'bf16x3' is refused there.
     obj_precision: str = 'auto'
+
+    def static_hit_f32(self, K):
+        """dynamics=False with box-pose optimisation under mlp_precision='bf16': the box-hit rays' background evaluation runs on
+        the exact-fp32 W = 256 kernels (obj_precision 'auto' / 'f32')"""
+        return (bool(K) and not self.dynamics and not (self.no_pose_opt and self.no_yaw_opt) and self.mlp_precision == 'bf16'
+                and self.obj_precision in ('auto', 'f32'))
 
     def object_precision(self):
         """'bf16' or 'f32': which kernels the object branch runs on ('bf16x3' is the fp32 branch's data flow on split bf16
@@ -190,10 +200,10 @@ class MipNerfModel:
         if self.obj_precision not in ('auto', 'bf16', 'f32', 'bf16x3'): bad.append('obj_precision')
         if self.ray_shape not in ('cone', 'cylinder'): bad.append('ray_shape')
         if (self.min_deg_point, self.max_deg_point, self.deg_view) != (0, 10, 4): bad.append('degrees')
-        if not self.dynamics and not (self.no_pose_opt and self.no_yaw_opt):
-            # (the reference's pose gradient then runs through the BACKGROUND encoding of the box-hit rays, whose origins are
-            # in box coordinates, obbpose_model.py:121-122: a backward through contraction + IPE that is not built)
-            bad.append('dynamics=False with box-pose optimisation')
+        if not self.dynamics and not (self.no_pose_opt and self.no_yaw_opt) and self.obj_precision == 'bf16x3':
+            # (the pose gradient then runs through the BACKGROUND MLP of the box-hit rays, static_hit_f32(): the split-bf16
+            # object kernels have no part in it)
+            bad.append("dynamics=False with box-pose optimisation and obj_precision='bf16x3'")
         if not self.stop_level_grad: bad.append('stop_level_grad=False')
         if self.num_samples % 32 or not (32 <= self.num_samples <= 256): bad.append('num_samples')
         if bad:
@@ -287,7 +297,8 @@ class MipNerfModel:
             (idx, count, slot), cls = ops.compact_all(hit, N)     # cls also counts the boxes each ray hits
         else:
             (idx, count, slot), cls = ops.compact_hits(hit), None
-        view27 = ops.view_enc(rays.viewdirs, want_f32=True)[1] if (f32 or obj_f32) else None
+        static_f32 = self.static_hit_f32(K)
+        view27 = ops.view_enc(rays.viewdirs, want_f32=True)[1] if (f32 or obj_f32 or static_f32) else None
         packs = {}
         if not f32:
             pk_b, pk_o = pro[-1]
@@ -306,8 +317,13 @@ class MipNerfModel:
             o0 = lay.mlp_off['BoxMLP_0']
             obj_flat = variables.flat[o0:o0 + Kd * lay.mlp_size[W_OBJ]]
             ctx['obj_ws'] = ops.mlp_f32_pack(W_OBJ, IN_OBJ, obj_flat, K=Kd, param_stride=lay.mlp_size[W_OBJ], x3=ctx['obj_x3'])
-        if f32:
+        if f32 or static_f32:
             ctx['bkgd_ws'] = ops.mlp_f32_pack(W_BKGD, IN_BKGD, variables.mlp_flat('MLP_0'))
+        if static_f32:
+            # the rays that hit any box, compacted (slot[b]: their position, -1 for the others): their background evaluation
+            # is redone on the exact-fp32 kernels at every level and replaces the bf16 one
+            hi, hc, hs = ops.compact_hits(hit.amax(dim=1, keepdim=True))
+            ctx['hit_rows'] = dict(idx=hi, count=hc, slot=hs.reshape(-1), mask=(hs.reshape(B, 1, 1) >= 0))
         raw_tail = None
         ret = []
         t_vals = weights = None
@@ -436,6 +452,16 @@ class MipNerfModel:
                         launch_objects()
                     side.join()
                 raws = slabs.raws() if Kb else (lvd['raws'] if obj_f32 else [])
+            if static_f32:
+                hr = ctx['hit_rows']
+                _, enc32 = ops.encode_bkgd(t_vals, o_s, d_s, radii, None, self.contraction, tile=False, f32=True,
+                                           disable_integration=self.disable_integration, cylinder=cyl, idx=hr['idx'], count=hr['count'])
+                out32 = ops.mlp_fwd_f32(W_BKGD, IN_BKGD, rows, N, enc32, view27, variables.mlp_flat('MLP_0'),
+                                        ray_idx=hr['idx'], count=hr['count'], want_act=train, wstream=ctx['bkgd_ws'])
+                raw32, act32 = out32 if train else (out32, None)
+                # (row j*N + n of the fp32 evaluation is sample n of ray idx[j]: gathered into the full layout by slot)
+                raw_b = torch.where(hr['mask'], raw32.view(B, N, 4)[hr['slot'].clamp(min=0)], raw_b.view(B, N, 4)).reshape(rows, 4)
+                lvd = dict(act_hit=act32)
             if randomized and self.density_noise > 0:    # :236-240: one launch (the draws: injected, the library's own
                 # under the host's key, or a torch.Generator's)
                 if 'density' in noise:

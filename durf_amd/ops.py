@@ -1096,6 +1096,21 @@ def encode_obj_bwd_batch(K, idx, count, d_enc, t_vals, origins_s, dirs_s, radii,
                'durf_encode_obj_bwd_batch')
 
 
+def encode_bkgd_bwd_batch(K, idx, count, d_enc, t_vals, origins_s, dirs_s, radii, origins, dirs, pose, sums, raw=None, draw=None,
+                          density_bias=-1.0, denc_slot=None, enc_flags=ENC_CONTRACT):
+    """dynamics=False: the box-pose rows of all K boxes of one level through the BACKGROUND encoding (durf_encode_bkgd_bwd_batch):
+    idx [K,B], count [K] (compact_hits); d_enc [rows,64]: row b*N + n, or denc_slot[b]*N + n (the fp32 evaluation of the box-hit
+    rays); raw / draw [B*N,4] add the rendering's |d_s| term.  Accumulates into sums [K,21]."""
+    B, N = t_vals.shape[0], t_vals.shape[1] - 1
+    scratch = torch.empty(K * 21 * B, device=t_vals.device)
+    _lib.check(_lib.lib().durf_encode_bkgd_bwd_batch(_stream(), int(K), B, N, _p(idx), _p(count), _p(_f32(d_enc)), _p(denc_slot),
+                                                     _p(_f32(t_vals)), _p(_f32(origins_s)), _p(_f32(dirs_s)), _p(_f32(radii)),
+                                                     _p(_f32(origins)), _p(_f32(dirs)), _p(_f32(pose)),
+                                                     _p(None if raw is None else _f32(raw)), _p(None if draw is None else _f32(draw)),
+                                                     float(density_bias), _p(scratch), _p(_f32(sums)), int(enc_flags)),
+               'durf_encode_bkgd_bwd_batch')
+
+
 def pose_finish(pose, sums, want_pos, want_rot, grad6):
     K = pose.shape[0]
     _lib.check(_lib.lib().durf_pose_finish(_stream(), K, _p(_f32(pose)), _p(_f32(sums)), int(want_pos),

@@ -267,6 +267,19 @@ def loss_and_grad(model, config, rng, variables, batch, eps, alpha, prev, noise=
                      (ops.ENC_CYLINDER if model.ray_shape == 'cylinder' else 0))              # through the object encoding
     pose_ts = variables['params']['box_centers'][ctx['ts']].contiguous()
     pose_sums = zbuf[n_par:].view(-1, 21) if n_sums else (torch.zeros(max(K, 1), 21, device=dev) if pose_opt else None)
+    # dynamics=False with pose optimisation: the boxes move the rays that hit them into box coordinates and the BACKGROUND MLP
+    # evaluates those; the pose gradient runs through its d(enc) of every level (durf_encode_bkgd_bwd_batch)
+    bkgd_pose = pose_opt and lay.K > 0 and K == 0
+    bkgd_enc_flags = ((ops.ENC_CONTRACT if model.contraction else 0) | obj_enc_flags)
+
+    hit_rows = ctx.get('hit_rows')              # the box-hit rays' background evaluation in fp32 (MipNerfModel.static_hit_f32)
+    hit_dz = [None] * L
+
+    def bkgd_pose_rows(lvl, d_enc, draw, denc_slot=None):
+        lv = ctx['levels'][lvl]
+        ops.encode_bkgd_bwd_batch(lay.K, ctx['idx'], ctx['count'], d_enc, lv['t_vals'], ctx['o_s'], ctx['d_s'], radii,
+                                  rays.origins, rays.directions, pose_ts, pose_sums, raw=lv['raw_b'], draw=draw,
+                                  density_bias=model.density_bias, denc_slot=denc_slot, enc_flags=bkgd_enc_flags)
 
     def level_loss(lvl):
         lv = ctx['levels'][lvl]
@@ -336,7 +349,10 @@ def loss_and_grad(model, config, rng, variables, batch, eps, alpha, prev, noise=
             fl = lv['f32']
             off = lay.mlp_off['MLP_0']
             dz = ops.mlp_bwd_f32(om.W_BKGD, om.IN_BKGD, rows, N, draw, variables.mlp_flat('MLP_0'), fl['act_b'],
-                                 wstream=ctx['bkgd_ws'])
+                                 want_d_enc=bkgd_pose, wstream=ctx['bkgd_ws'])
+            if bkgd_pose:
+                dz, d_enc = dz
+                bkgd_pose_rows(lvl, d_enc, draw)
             ops.mlp_dw_f32(om.W_BKGD, om.IN_BKGD, rows, N, fl['act_b'], dz, grad[off:off + lay.mlp_size[om.W_BKGD]])
         if obj_f32:                           # the object branch in fp32: backward + d(enc) -> pose sums, all K at once
             sl = lv['f32']['slabs32']
@@ -359,6 +375,19 @@ def loss_and_grad(model, config, rng, variables, batch, eps, alpha, prev, noise=
             dzs[lvl] = ops.mlp_bwd(om.W_BKGD, rows, N, draw, ctx['packs']['MLP_0'][1], lv['mask_b'], ray_idx=dd['idx'][0],
                                    count=dd['count'][0:1], tail_idx=dd['idx'][1], tail_count=dd['count'][1:2],
                                    draw_ray_sum=ray_sums[lvl])
+        elif hit_rows is not None:
+            # the box-hit rays: backward with d(enc) on the exact-fp32 kernels (their share of MLP_0's weight gradient below);
+            # the bf16 backward sees their head gradients zeroed, so it adds nothing for them
+            dz32, d_enc = ops.mlp_bwd_f32(om.W_BKGD, om.IN_BKGD, rows, N, draw, variables.mlp_flat('MLP_0'), lv['f32']['act_hit'],
+                                          ray_idx=hit_rows['idx'], count=hit_rows['count'], want_d_enc=True, wstream=ctx['bkgd_ws'])
+            hit_dz[lvl] = dz32
+            bkgd_pose_rows(lvl, d_enc, draw, denc_slot=hit_rows['slot'])
+            draw_rest = torch.where(hit_rows['mask'], 0.0, draw.view(B, N, 4)).reshape(rows, 4)
+            dzs[lvl] = ops.mlp_bwd(om.W_BKGD, rows, N, draw_rest, ctx['packs']['MLP_0'][1], lv['mask_b'])
+        elif bkgd_pose:                          # obj_precision='bf16': the bf16 backward's d(enc) epilogue (k_mlp_bwd<256, POSE>)
+            dz, dz_out, d_enc = ops.mlp_bwd(om.W_BKGD, rows, N, draw, ctx['packs']['MLP_0'][1], lv['mask_b'], want_d_enc=True)
+            dzs[lvl] = (dz, dz_out)
+            bkgd_pose_rows(lvl, d_enc, draw)
         else:
             dzs[lvl] = ops.mlp_bwd(om.W_BKGD, rows, N, draw, ctx['packs']['MLP_0'][1], lv['mask_b'])
         if Kb and not obj_bwd_done:           # all K object MLPs: one call (csrc/objects.hip)
@@ -435,6 +464,9 @@ def loss_and_grad(model, config, rng, variables, batch, eps, alpha, prev, noise=
                                 obj=(K, B, N, ctx['count'], L, po, bo, grad[o0:o0 + K * sz], sz, variables.flat[o0:o0 + K * sz]))
         else:
             ops.dw_finalize_all(*geo, *bufs, g_b, p_b)
+            for lvl in range(L) if hit_rows is not None else ():        # the box-hit rays' share, fp32 (added)
+                ops.mlp_dw_f32(om.W_BKGD, om.IN_BKGD, rows, N, levels[lvl]['f32']['act_hit'], hit_dz[lvl], g_b,
+                               count=hit_rows['count'])
             if Kb and objects_ready is None:
                 with side:
                     ops.obj_dw_batch([lv['slabs'] for lv in levels], ctx['view_tiles_obj'], ctx['count'],
@@ -447,11 +479,11 @@ def loss_and_grad(model, config, rng, variables, batch, eps, alpha, prev, noise=
     if config.weight_decay_mult != 0:                                          # :73-75
         # (one launch pair, durf_weight_decay: the gradient term on whatever has not left for its all-reduce yet + the scalar)
         weight_l2 = ops.weight_decay(flat, grad, config.weight_decay_mult, 0, flat.numel() if first_only is None else first_only)
-    if K > 0 and pose_opt:                      # no_pose_opt and no_yaw_opt: box_centers get no gradient (:100-104)
+    if lay.K > 0 and pose_opt:                  # no_pose_opt and no_yaw_opt: box_centers get no gradient (:100-104)
         # (k_pose_finish ADDS: straight into this timestep's rows of the zero-filled gradient when they are a view)
-        g_ts = grad[lay.box[0]:lay.box[1]].view(lay.T, K, 6)
+        g_ts = grad[lay.box[0]:lay.box[1]].view(lay.T, lay.K, 6)
         direct = not torch.is_tensor(ctx['ts'])          # an integer timestep: the rows are a view
-        g6 = g_ts[ctx['ts']] if direct else torch.zeros(K, 6, device=dev)
+        g6 = g_ts[ctx['ts']] if direct else torch.zeros(lay.K, 6, device=dev)
         ops.pose_finish(pose_ts, pose_sums, not model.no_pose_opt, not model.no_yaw_opt, g6)
         if not model.no_pose_opt and config.tv_loss_mult != 0:               # :136,:219
             # (the multiplier enters as the fp32 value the C entry point's `float tv_loss_mult` field carries, widened for

@@ -451,7 +451,8 @@ int durf_render_image(void* stream, const durf_forward_args* args, size_t n_rays
  * (durf_poison_multi_hit) and the logged scalars -- in the order durf_amd/train_boxpose.py issues them, on `stream`,
  * bit-identical to that path.  A data-parallel host all-reduces `grad` (and `stats` when it logs) and calls
  * durf_clip_adam (lax.pmean, train_boxpose.py:253-255); durf_train_step = durf_loss_backward + durf_clip_adam with
- * inv_world = 1 for a single device.  Scope: every BASELINE.json training configuration -- bf16 background MLP; the K
+ * inv_world = 1 for a single device.  Not covered: dynamics = False with box-pose optimisation (the pose gradient through the
+ * background MLP, durf_encode_bkgd_bwd_batch: the Python train_step runs it).  Scope: every BASELINE.json training configuration -- bf16 background MLP; the K
  * object MLPs on the bf16 kernels with frozen box poses (flags = 0: box_centers get a zero gradient; cfg2 / cfg3 / cfg5),
  * or on the exact-fp32 kernels (DURF_TRAIN_OBJ_FP32: MipNerfModel.object_precision() == 'f32' -- the box-hit rays'
  * object MLPs, their encodings and the background MLP's one evaluation of those rays in fp32) with, under
@@ -708,6 +709,21 @@ int durf_encode_obj_bwd_levels(void* stream, int K, int B, int N, int nlevels, c
                                const float* dirs_s, const float* radii, const float* origins, const float* dirs,
                                const float* pose, const float* barf_w /* host float[10] */, float* scratch, float* sums,
                                int precise, int enc_flags);
+/* MipNerfModel.dynamics = False with box-pose optimisation: the boxes own no network, they move the rays that hit them into
+ * box coordinates and the BACKGROUND MLP evaluates those (obbpose_model.py:116-122,229-236).  For all K boxes of a level in
+ * one launch pair (blockIdx.y = box): d_enc = d(loss)/d(background encoding) from durf_mlp_bwd_f32(..., d_enc) -> integrated_pos_enc,
+ * mip360.new_space (enc_flags DURF_ENC_CONTRACT), the Gaussian (DURF_ENC_CYLINDER | DURF_ENC_NO_INTEGRATION) -> (o', d') of
+ * every box a ray hits -> the 21 rows per (ray, box) that durf_encode_obj_bwd_batch makes, summed into sums [K,21]
+ * (durf_pose_finish then, unchanged).  d_enc row of sample n of ray b: denc_slot[b] * N + n (the compacted box-hit rays of
+ * the fp32 evaluation: durf_compact_hits' slot of the any-box list) or, denc_slot NULL, b * N + n.  raw / draw [B*N,4]
+ * (nullable together): the level's raw outputs and d(loss)/d(raw), for the way d_s reaches the loss through the rendering's
+ * delta = t_dists |d_s| (non-zero for rays in several boxes only).  idx [K,B] / count [K] from durf_compact_hits, scratch
+ * K*21*B floats.  libm exp / sin / cos. */
+int durf_encode_bkgd_bwd_batch(void* stream, int K, int B, int N, const int32_t* idx, const int32_t* count,
+                               const float* d_enc, const int32_t* denc_slot, const float* t_vals, const float* origins_s,
+                               const float* dirs_s, const float* radii, const float* origins, const float* dirs,
+                               const float* pose, const float* raw, const float* draw, float density_bias, float* scratch,
+                               float* sums, int enc_flags);
 int durf_pose_finish(void* stream, int K, const float* pose, const float* sums, int want_pos, int want_rot,
                      float* grad6);
 
