@@ -260,4 +260,11 @@ struct DwFinSpec {           // one class of MLPs of a finalize launch (launch_d
     size_t part_stride, bpart_stride, grad_stride, param_stride;
 };
 int launch_dw_finalize2(void* stream, const DwFinSpec& a, const DwFinSpec& b);
+// scene layers (csrc/layers.hip): the bookkeeping launches of durf_render_layers (csrc/forward.hip)
+int launch_layer_chunk(void* stream, int B, int K, const int32_t* hit, const float* rgb, const float* dist, const float* acc,
+                       int bkgd_mode, int32_t* instance, float* bg_rgb, float* bg_dist, float* bg_acc, float* obj_rgba);
+int launch_layer_compact(void* stream, int n, const int32_t* instance, int32_t* idx, int32_t* count);
+int launch_layer_gather(void* stream, int count, const int32_t* idx, const float* const* src, float* const* dst);   // 6 Rays fields
+int launch_layer_scatter(void* stream, int count, const int32_t* idx, const float* rgb, const float* dist, const float* acc,
+                         float* bg_rgb, float* bg_dist, float* bg_acc);
 }  // namespace durf

@@ -73,17 +73,18 @@ static int check_forward_args(const durf_forward_args* a, void* workspace) {
 }
 
 // the launches of one chunk (arguments checked, workspace carved by the caller)
-static int forward_launches(void* stream, const durf_forward_args* a, const FwdWs& w) {
+static int forward_launches(void* stream, const durf_forward_args* a, const FwdWs& w, const int32_t* box_enable = nullptr) {
     const int B = a->B, N = a->N, K = a->K, L = a->num_levels;
     const size_t rows = (size_t)B * N;
     int rc;
 #define STEP(call) do { rc = (call); if (rc != 0) return rc; } while (0)
     // ray setup + view encoding + level-0 sample positions (obbpose_model.py:99-131, mip.py:330-370) + the bf16 weight
     // streams of every MLP: one launch
-    STEP(durf_ray_prologue_pack(stream, B, K, N, a->origins, a->directions, a->pose, a->ext, w.o_s, w.d_s, w.hit, a->zo, a->viewdirs,
+    STEP(durf_ray_prologue_pack_masked(stream, B, K, N, a->origins, a->directions, a->pose, a->ext, w.o_s, w.d_s, w.hit, a->zo, a->viewdirs,
                                 w.view, a->near, a->far, a->t_rand, a->lindisp, a->t_vals[0], nullptr, nullptr, 0, a->seed_lo, a->seed_hi,
                                 a->draw_noise ? w.u_rand : nullptr, a->bkgd_params, 60, w.wf_bkgd, nullptr, K, a->obj_params,
-                                a->obj_param_stride, 63, w.wf_obj, nullptr, K == 0 ? (float*)a->dyn_mask : nullptr, K == 0 ? (size_t)B : 0));
+                                a->obj_param_stride, 63, w.wf_obj, nullptr, K == 0 ? (float*)a->dyn_mask : nullptr, K == 0 ? (size_t)B : 0,
+                                       K > 0 ? box_enable : nullptr));
     if (K > 0)      // per-object hit lists + the ray classes of the de-duplicated background evaluation: one launch
         STEP(durf_compact_all(stream, B, K, N, w.hit, w.idx_obj, w.count_obj, w.slot_obj, w.idx_cls, w.count_cls, w.slot_cls,
                               a->dyn_mask));
@@ -121,7 +122,7 @@ static int forward_launches(void* stream, const durf_forward_args* a, const FwdW
     return 0;
 }
 
-int durf_forward(void* stream, const durf_forward_args* a, void* workspace, size_t workspace_bytes) {
+int durf_forward_masked(void* stream, const durf_forward_args* a, const int32_t* box_enable, void* workspace, size_t workspace_bytes) {
     int rc = check_forward_args(a, workspace);
     if (rc != 0) return rc;
     const FwdWs w = carve(workspace, a->B, a->N, a->K);
@@ -130,7 +131,11 @@ int durf_forward(void* stream, const durf_forward_args* a, void* workspace, size
                        a->K, w.total);
         return -1;
     }
-    return forward_launches(stream, a, w);
+    return forward_launches(stream, a, w, box_enable);
+}
+
+int durf_forward(void* stream, const durf_forward_args* a, void* workspace, size_t workspace_bytes) {
+    return durf_forward_masked(stream, a, nullptr, workspace, workspace_bytes);
 }
 
 // ---- one C call per IMAGE (obbpose_model.py:421-479 render_image on one device) --------------------------------------
@@ -157,7 +162,38 @@ ImgWs carve_image(void* workspace, int chunk, int N, int K, int L) {
     w.total = (c.off + 255) & ~(size_t)255;
     return w;
 }
+// the per-image layer outputs a chunk's bookkeeping launch fills (csrc/layers.hip; instance is never null here)
+struct LayerOuts { int32_t* instance; float *bg_rgb, *bg_dist, *bg_acc, *obj_rgba; };
 }  // namespace
+
+// the chunk loop of durf_render_image / durf_render_layers (arguments checked, workspace carved by the caller)
+static int render_chunks(void* stream, const durf_forward_args* a, const int32_t* box_enable, size_t n_rays, int chunk, float* rgb,
+                         float* distance, float* acc, const ImgWs& w, void* workspace, const LayerOuts* lo) {
+    const int L = a->num_levels;
+    for (size_t i = 0; i < n_rays; i += (size_t)chunk) {
+        durf_forward_args c = *a;
+        c.B = (int)(n_rays - i < (size_t)chunk ? n_rays - i : (size_t)chunk);        // (the last chunk is the remainder, :451-453)
+        c.origins = a->origins + i * 3; c.directions = a->directions + i * 3; c.viewdirs = a->viewdirs + i * 3;
+        c.radii = a->radii + i; c.near = a->near + i; c.far = a->far + i;
+        for (int l = 0; l < L; l++) {
+            const bool last = l == L - 1;
+            c.rgb[l] = last ? rgb + i * 3 : w.rgb[l]; c.depth[l] = last ? distance + i : w.depth[l]; c.acc[l] = last ? acc + i : w.acc[l];
+            c.weights[l] = w.weights[l]; c.t_vals[l] = w.t_vals[l]; c.t_mids[l] = w.t_mids[l]; c.t_dists[l] = w.t_dists[l];
+        }
+        c.zo = w.zo; c.dyn_mask = w.dyn;
+        int rc = check_forward_args(&c, workspace);
+        if (rc != 0) return rc;
+        rc = forward_launches(stream, &c, w.f, box_enable);
+        if (rc != 0) return rc;
+        if (lo) {         // instance map, bg_* pre-filled with the composite, obj_rgba: one launch behind the chunk's composite
+            rc = durf::launch_layer_chunk(stream, c.B, c.K, w.f.hit, rgb + i * 3, distance + i, acc + i, a->bkgd_mode, lo->instance + i,
+                                          lo->bg_rgb ? lo->bg_rgb + i * 3 : nullptr, lo->bg_dist ? lo->bg_dist + i : nullptr,
+                                          lo->bg_acc ? lo->bg_acc + i : nullptr, lo->obj_rgba ? lo->obj_rgba + i * 4 : nullptr);
+            if (rc != 0) return rc;
+        }
+    }
+    return 0;
+}
 
 size_t durf_render_image_workspace_bytes(int chunk, int N, int K, int num_levels) {
     return carve_image(nullptr, chunk, N, K, num_levels).total;
@@ -177,23 +213,73 @@ int durf_render_image(void* stream, const durf_forward_args* a, size_t n_rays, i
                        workspace_bytes, chunk, a->N, a->K, L, w.total);
         return -1;
     }
-    for (size_t i = 0; i < n_rays; i += (size_t)chunk) {
-        durf_forward_args c = *a;
-        c.B = (int)(n_rays - i < (size_t)chunk ? n_rays - i : (size_t)chunk);        // (the last chunk is the remainder, :451-453)
-        c.origins = a->origins + i * 3; c.directions = a->directions + i * 3; c.viewdirs = a->viewdirs + i * 3;
-        c.radii = a->radii + i; c.near = a->near + i; c.far = a->far + i;
-        for (int l = 0; l < L; l++) {
-            const bool last = l == L - 1;
-            c.rgb[l] = last ? rgb + i * 3 : w.rgb[l]; c.depth[l] = last ? distance + i : w.depth[l]; c.acc[l] = last ? acc + i : w.acc[l];
-            c.weights[l] = w.weights[l]; c.t_vals[l] = w.t_vals[l]; c.t_mids[l] = w.t_mids[l]; c.t_dists[l] = w.t_dists[l];
-        }
-        c.zo = w.zo; c.dyn_mask = w.dyn;
-        int rc = check_forward_args(&c, workspace);
-        if (rc != 0) return rc;
-        rc = forward_launches(stream, &c, w.f);
-        if (rc != 0) return rc;
+    return render_chunks(stream, a, nullptr, n_rays, chunk, rgb, distance, acc, w, workspace, nullptr);
+}
+
+// ---- scene layers (include/durf_hip.h durf_render_layers; kernels: csrc/layers.hip) -------------------------------------
+namespace {
+struct LayerWs { ImgWs img; int32_t *instance, *idx, *count; float* rays[6]; float *rgb2, *dist2, *acc2; size_t total; };
+LayerWs carve_layers(void* workspace, size_t n_rays, int chunk, int N, int K, int L) {
+    LayerWs w{};
+    w.img = carve_image(workspace, chunk, N, K, L);         // (the second pass re-carves the same bytes for K = 0: never larger)
+    Carver c{(char*)workspace, w.img.total};
+    w.instance = (int32_t*)c.take(n_rays * 4);
+    w.idx = (int32_t*)c.take(n_rays * 4);
+    w.count = (int32_t*)c.take(64 * 4);
+    for (int f = 0; f < 6; f++) w.rays[f] = (float*)c.take(n_rays * (f < 3 ? 3 : 1) * 4);
+    w.rgb2 = (float*)c.take(n_rays * 3 * 4); w.dist2 = (float*)c.take(n_rays * 4); w.acc2 = (float*)c.take(n_rays * 4);
+    w.total = (c.off + 255) & ~(size_t)255;
+    return w;
+}
+}  // namespace
+
+size_t durf_render_layers_workspace_bytes(size_t n_rays, int chunk, int N, int K, int num_levels) {
+    return carve_layers(nullptr, n_rays, chunk, N, K, num_levels).total;
+}
+
+int durf_render_layers(void* stream, const durf_forward_args* a, const int32_t* box_enable, size_t n_rays, int chunk, float* rgb,
+                       float* distance, float* acc, int32_t* instance, float* bg_rgb, float* bg_distance, float* bg_acc,
+                       float* obj_rgba, void* workspace, size_t workspace_bytes) {
+    DURF_REQUIRE(a != nullptr && rgb && distance && acc, "arguments and the three image planes");
+    DURF_REQUIRE(chunk > 0 && n_rays > 0 && n_rays < ((size_t)1 << 27), "chunk > 0, 0 < n_rays < 2^27");
+    DURF_REQUIRE(a->t_rand == nullptr && a->u_rand == nullptr && !a->draw_noise && a->density_noise == 0.0f,
+                 "render_layers is test mode: randomized = False (obbpose_model.py:421-479)");
+    DURF_REQUIRE((bg_rgb != nullptr) == (bg_distance != nullptr) && (bg_rgb != nullptr) == (bg_acc != nullptr),
+                 "bg_rgb, bg_distance and bg_acc go together");
+    DURF_REQUIRE(((size_t)obj_rgba & 15) == 0, "obj_rgba aligned to 16 bytes");
+    const int L = a->num_levels;
+    DURF_REQUIRE(L >= 1 && L <= DURF_FORWARD_MAX_LEVELS, "1 <= num_levels <= DURF_FORWARD_MAX_LEVELS");
+    const LayerWs w = carve_layers(workspace, n_rays, chunk, a->N, a->K, L);
+    if (workspace_bytes < w.total) {
+        durf_set_error("durf_render_layers: workspace of %zu bytes, durf_render_layers_workspace_bytes(%zu, %d, %d, %d, %d) = %zu",
+                       workspace_bytes, n_rays, chunk, a->N, a->K, L, w.total);
+        return -1;
     }
-    return 0;
+    const ImgWs w0 = carve_image(workspace, chunk, a->N, 0, L);          // the second pass re-carves the image part for K = 0
+    DURF_REQUIRE(w0.total <= w.img.total, "the K = 0 workspace fits inside the K one");
+    const bool any = instance || bg_rgb || obj_rgba;
+    LayerOuts lo{instance ? instance : w.instance, bg_rgb, bg_distance, bg_acc, obj_rgba};
+    int rc = render_chunks(stream, a, box_enable, n_rays, chunk, rgb, distance, acc, w.img, workspace, any ? &lo : nullptr);
+    if (rc != 0 || !bg_rgb || a->K == 0) return rc;          // (K = 0: no box-hit rays, bg_* is the composite)
+    // the box-hit rays of the whole image, in ray order, and their number -- read back once per image: it sizes the second
+    // pass exactly (chunks, grids, the persistent kernels' row counts), where an upper bound would launch the whole
+    // forward sequence over n_rays / chunk mostly empty chunks
+    rc = durf::launch_layer_compact(stream, (int)n_rays, lo.instance, w.idx, w.count);
+    if (rc != 0) return rc;
+    int32_t n_hit = 0;
+    DURF_REQUIRE(hipMemcpyAsync(&n_hit, w.count, sizeof(n_hit), hipMemcpyDeviceToHost, (hipStream_t)stream) == hipSuccess &&
+                 hipStreamSynchronize((hipStream_t)stream) == hipSuccess, "reading the number of box-hit rays");
+    DURF_REQUIRE(n_hit >= 0 && (size_t)n_hit <= n_rays, "0 <= box-hit rays <= n_rays");
+    if (n_hit == 0) return 0;
+    const float* src[6] = {a->origins, a->directions, a->viewdirs, a->radii, a->near, a->far};
+    rc = durf::launch_layer_gather(stream, n_hit, w.idx, src, w.rays);
+    if (rc != 0) return rc;
+    durf_forward_args s = *a;                                 // the same model without boxes, over the dense buffer
+    s.K = 0; s.pose = nullptr; s.ext = nullptr; s.obj_params = nullptr;
+    s.origins = w.rays[0]; s.directions = w.rays[1]; s.viewdirs = w.rays[2]; s.radii = w.rays[3]; s.near = w.rays[4]; s.far = w.rays[5];
+    rc = render_chunks(stream, &s, nullptr, (size_t)n_hit, chunk, w.rgb2, w.dist2, w.acc2, w0, workspace, nullptr);
+    if (rc != 0) return rc;
+    return durf::launch_layer_scatter(stream, n_hit, w.idx, w.rgb2, w.dist2, w.acc2, bg_rgb, bg_distance, bg_acc);
 }
 
 }  // extern "C"

@@ -14,12 +14,16 @@ __device__ __forceinline__ void ray_setup_block(int blk, int B, int K, const flo
                                                 const float* __restrict__ dirs, const float* __restrict__ pose,
                                                 const float* __restrict__ ext, float* __restrict__ origins_s,
                                                 float* __restrict__ dirs_s, int32_t* __restrict__ hit,
-                                                float* __restrict__ zo) {
+                                                float* __restrict__ zo, const int32_t* __restrict__ enable = nullptr) {
+    // enable (nullable, [K] 0 / 1 on the device): a box with 0 is absent -- its column of `intersection` (model :112-115) is
+    // zero and it adds nothing to the ray's sums, exactly as if its rows were cut out of the parameter tree
     __shared__ float sR[DURF_MAX_OBJ][9];
+    __shared__ int sOn[DURF_MAX_OBJ];
     __shared__ float sT[DURF_MAX_OBJ][3];   // R * (-c)
     __shared__ float sE[DURF_MAX_OBJ][3];
     if (threadIdx.x < K) {
         const int k = threadIdx.x;
+        sOn[k] = enable ? (enable[k] != 0) : 1;
         // box_helpers.aa2matrix (:148-167)
         const float rx = pose[k * 6 + 3], ry = pose[k * 6 + 4], rz = pose[k * 6 + 5];
         float s = rx * rx + ry * ry + rz * rz;
@@ -55,6 +59,7 @@ __device__ __forceinline__ void ray_setup_block(int blk, int B, int K, const flo
     float zsum = 0.f;
     int nhit = 0;
     for (int k = 0; k < K; k++) {
+        if (!sOn[k]) { hit[b * K + k] = 0; continue; }
         const float* R = sR[k];
         float po[3], pd[3];
 #pragma unroll
@@ -100,8 +105,8 @@ __global__ void __launch_bounds__(256)
 k_ray_setup(int B, int K, const float* __restrict__ origins, const float* __restrict__ dirs,
             const float* __restrict__ pose, const float* __restrict__ ext,
             float* __restrict__ origins_s, float* __restrict__ dirs_s,
-            int32_t* __restrict__ hit, float* __restrict__ zo) {
-    ray_setup_block(blockIdx.x, B, K, origins, dirs, pose, ext, origins_s, dirs_s, hit, zo);
+            int32_t* __restrict__ hit, float* __restrict__ zo, const int32_t* __restrict__ enable) {
+    ray_setup_block(blockIdx.x, B, K, origins, dirs, pose, ext, origins_s, dirs_s, hit, zo, enable);
 }
 
 // ---------------------------------------------------------------------------
@@ -290,7 +295,8 @@ k_ray_prologue(int B, int K, int N, const float* __restrict__ origins, const flo
                const float* __restrict__ near, const float* __restrict__ far, const float* __restrict__ t_rand,
                int lindisp, float* __restrict__ t_vals, float* __restrict__ pose_copy, float* __restrict__ zero_buf,
                size_t zero_count, unsigned seed_lo, unsigned seed_hi, float* __restrict__ u_rand_out, PackAll pk, int nb_pro,
-               int pack_blocks_bkgd, int pack_blocks_obj, float* __restrict__ zero_buf2, size_t zero_count2) {
+               int pack_blocks_bkgd, int pack_blocks_obj, float* __restrict__ zero_buf2, size_t zero_count2,
+               const int32_t* __restrict__ enable) {
     // Workgroups behind the nb_pro of the prologue proper pack the step's bf16 weight streams (durf_ray_prologue_pack): the
     // packing depends on the parameters only, so it shares this launch instead of being the next one (12 us of a 0.4-0.7 ms
     // small-batch step).  MLP-major: the background MLP's vectors, then each object's.
@@ -318,7 +324,7 @@ k_ray_prologue(int B, int K, int N, const float* __restrict__ origins, const flo
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < zero_count2; i += nthr) zero_buf2[i] = 0.0f;
     }
     if ((int)blockIdx.x < (B + 255) / 256)                            // block-uniform: ray_setup_block has a barrier
-        ray_setup_block(blockIdx.x, B, K, origins, dirs, pose, ext, origins_s, dirs_s, hit, zo);
+        ray_setup_block(blockIdx.x, B, K, origins, dirs, pose, ext, origins_s, dirs_s, hit, zo, enable);
     if ((int)blockIdx.x < (B * DURF_VIEW_DIM + 255) / 256) view_enc_block(blockIdx.x, B, viewdirs, view_bf16, nullptr);
     sample_t_block(blockIdx.x, B, N, near, far, t_rand, lindisp, t_vals, u_rand_out != nullptr, seed_lo, seed_hi, u_rand_out);
 }
@@ -476,15 +482,22 @@ k_density_noise(size_t rows, float* __restrict__ raw, float scale, const float* 
 
 extern "C" {
 
-int durf_ray_setup(void* stream, int B, int K, const float* origins, const float* dirs,
-                   const float* pose, const float* ext, float* origins_s, float* dirs_s,
-                   int32_t* hit, float* zo) {
+int durf_ray_setup_masked(void* stream, int B, int K, const float* origins, const float* dirs,
+                          const float* pose, const float* ext, const int32_t* box_enable, float* origins_s, float* dirs_s,
+                          int32_t* hit, float* zo) {
     DURF_REQUIRE(K >= 0 && K <= DURF_MAX_OBJ, "0 <= K <= DURF_MAX_OBJ");
     if (B <= 0) return 0;
     hipLaunchKernelGGL(k_ray_setup, dim3(durf_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, B, K,
-                       origins, dirs, pose, ext, origins_s, dirs_s, hit, zo);
+                       origins, dirs, pose, ext, origins_s, dirs_s, hit, zo, box_enable);
     DURF_CHECK_LAUNCH("durf_ray_setup");
+    if (box_enable) durf::note_dispatch(DURF_LAYERLOG_BOX_MASK);
     return 0;
+}
+
+int durf_ray_setup(void* stream, int B, int K, const float* origins, const float* dirs,
+                   const float* pose, const float* ext, float* origins_s, float* dirs_s,
+                   int32_t* hit, float* zo) {
+    return durf_ray_setup_masked(stream, B, K, origins, dirs, pose, ext, nullptr, origins_s, dirs_s, hit, zo);
 }
 
 static int launch_prologue(void* stream, int B, int K, int N, const float* origins, const float* dirs, const float* pose,
@@ -492,7 +505,7 @@ static int launch_prologue(void* stream, int B, int K, int N, const float* origi
                            const float* viewdirs, void* view_bf16, const float* near, const float* far, const float* t_rand,
                            int lindisp, float* t_vals, float* pose_copy, float* zero_buf, size_t zero_count,
                            uint32_t seed_lo, uint32_t seed_hi, float* u_rand_out, const PackAll* pack, int K_pack,
-                           float* zero_buf2 = nullptr, size_t zero_count2 = 0) {
+                           float* zero_buf2 = nullptr, size_t zero_count2 = 0, const int32_t* enable = nullptr) {
     DURF_REQUIRE(K >= 0 && K <= DURF_MAX_OBJ, "0 <= K <= DURF_MAX_OBJ");
     DURF_REQUIRE(zero_buf == nullptr || ((size_t)zero_buf & 15) == 0, "zero_buf aligned to 16 bytes");
     DURF_REQUIRE(u_rand_out == nullptr || t_rand == nullptr, "the draws come from t_rand OR from the launch's own generator");
@@ -520,8 +533,9 @@ static int launch_prologue(void* stream, int B, int K, int N, const float* origi
     hipLaunchKernelGGL(k_ray_prologue, dim3(nb_pro + pack_blocks), dim3(256), 0, (hipStream_t)stream, B,
                        K, N, origins, dirs, pose, ext, origins_s, dirs_s, hit, zo, viewdirs, (__bf16*)view_bf16, near,
                        far, t_rand, lindisp, t_vals, pose_copy, zero_buf, zero_buf ? zero_count : (size_t)0, seed_lo, seed_hi,
-                       u_rand_out, pk, nb_pro, pb_bkgd, pb_obj > 0 ? pb_obj : 1, zero_buf2, zero_buf2 ? zero_count2 : (size_t)0);
+                       u_rand_out, pk, nb_pro, pb_bkgd, pb_obj > 0 ? pb_obj : 1, zero_buf2, zero_buf2 ? zero_count2 : (size_t)0, enable);
     DURF_CHECK_LAUNCH("durf_ray_prologue");
+    if (enable) durf::note_dispatch(DURF_LAYERLOG_BOX_MASK);
     return 0;
 }
 
@@ -534,14 +548,14 @@ int durf_ray_prologue(void* stream, int B, int K, int N, const float* origins, c
                            t_rand, lindisp, t_vals, pose_copy, zero_buf, zero_count, seed_lo, seed_hi, u_rand_out, nullptr, 0);
 }
 
-int durf_ray_prologue_pack(void* stream, int B, int K, int N, const float* origins, const float* dirs, const float* pose,
+int durf_ray_prologue_pack_masked(void* stream, int B, int K, int N, const float* origins, const float* dirs, const float* pose,
                            const float* ext, float* origins_s, float* dirs_s, int32_t* hit, float* zo,
                            const float* viewdirs, void* view_bf16, const float* near, const float* far, const float* t_rand,
                            int lindisp, float* t_vals, float* pose_copy, float* zero_buf, size_t zero_count,
                            uint32_t seed_lo, uint32_t seed_hi, float* u_rand_out,
                            const float* bkgd_params, int in_bkgd, void* bkgd_fwd, void* bkgd_bwd, int K_pack,
                            const float* obj_params, size_t obj_param_stride, int in_obj, void* obj_fwd, void* obj_bwd,
-                           float* zero_buf2, size_t zero_count2) {
+                           float* zero_buf2, size_t zero_count2, const int32_t* box_enable) {
     DURF_REQUIRE(bkgd_params == nullptr || (bkgd_fwd != nullptr && in_bkgd > 0 && in_bkgd <= DURF_ENC_DIM),
                  "background MLP: forward stream and 1 <= in_dim <= 64");
     DURF_REQUIRE(K_pack >= 0 && (K_pack == 0 || (obj_params != nullptr && obj_fwd != nullptr && in_obj > 0 && in_obj <= DURF_ENC_DIM)),
@@ -552,7 +566,21 @@ int durf_ray_prologue_pack(void* stream, int B, int K, int N, const float* origi
     a.p_stride = obj_param_stride; a.f_stride = durf_wpack_fwd_bytes(128); a.b_stride = durf_wpack_bwd_bytes(128);
     return launch_prologue(stream, B, K, N, origins, dirs, pose, ext, origins_s, dirs_s, hit, zo, viewdirs, view_bf16, near, far,
                            t_rand, lindisp, t_vals, pose_copy, zero_buf, zero_count, seed_lo, seed_hi, u_rand_out, &a, K_pack, zero_buf2,
-                           zero_count2);
+                           zero_count2, box_enable);
+}
+
+int durf_ray_prologue_pack(void* stream, int B, int K, int N, const float* origins, const float* dirs, const float* pose,
+                           const float* ext, float* origins_s, float* dirs_s, int32_t* hit, float* zo,
+                           const float* viewdirs, void* view_bf16, const float* near, const float* far, const float* t_rand,
+                           int lindisp, float* t_vals, float* pose_copy, float* zero_buf, size_t zero_count,
+                           uint32_t seed_lo, uint32_t seed_hi, float* u_rand_out,
+                           const float* bkgd_params, int in_bkgd, void* bkgd_fwd, void* bkgd_bwd, int K_pack,
+                           const float* obj_params, size_t obj_param_stride, int in_obj, void* obj_fwd, void* obj_bwd,
+                           float* zero_buf2, size_t zero_count2) {
+    return durf_ray_prologue_pack_masked(stream, B, K, N, origins, dirs, pose, ext, origins_s, dirs_s, hit, zo, viewdirs, view_bf16,
+                                         near, far, t_rand, lindisp, t_vals, pose_copy, zero_buf, zero_count, seed_lo, seed_hi,
+                                         u_rand_out, bkgd_params, in_bkgd, bkgd_fwd, bkgd_bwd, K_pack, obj_params, obj_param_stride,
+                                         in_obj, obj_fwd, obj_bwd, zero_buf2, zero_count2, nullptr);
 }
 
 int durf_compact_hits(void* stream, int B, int K, const int32_t* hit, int32_t* idx,

@@ -225,9 +225,27 @@ class MipNerfModel:
         from . import noview
         return noview.embed(variables)
 
+    def _scene_edit(self, variables, ts, pose, box_enable, train=False):
+        """-> (pose [K,6] the render uses, box_enable int32 [K] on the device or None).  pose=None: box_centers[ts]; otherwise
+        the given [K,6] tensor in its place (the notebook's sliders; inference only, no gradient).  box_enable: K values 0 / 1;
+        a box with 0 is absent from the scene (ops.ray_setup)."""
+        K = variables.layout.K
+        dev = variables.flat.device
+        if train and (pose is not None or box_enable is not None):
+            raise NotImplementedError('box_enable / pose edit the scene of an inference render: training has no such knob')
+        if pose is None:
+            pose = variables['params']['box_centers'][int(ts)].contiguous()
+        else:
+            pose = torch.as_tensor(pose)
+            if tuple(pose.shape) != (K, 6):
+                raise ValueError('pose: shape %s, expected (%d, 6)' % (tuple(pose.shape), K))
+            pose = pose.detach().to(device=dev, dtype=torch.float32).contiguous()
+        en = ops._enable(box_enable, K, dev)
+        return pose, (en if K > 0 else None)
+
     # -- forward -------------------------------------------------------------
     def _forward(self, variables, rng, rays, init, ext, ts, randomized, rand_bkgd, white_bkgd, alpha,
-                 train=False, noise=None, loss_prep=None, zero_fill=None):
+                 train=False, noise=None, loss_prep=None, zero_fill=None, box_enable=None, pose=None):
         """loss_prep (training, num_levels >= 2): dict(lossmult, gt_depth, sky, eps, box_loss_mult, disable_multiscale,
         norms [L,5]) -- the inputs of durf_loss_prep; the fused per-ray launches then fill `norms` for every level.
         zero_fill: a flat fp32 tensor (the step's gradient buffer) the prologue launch zero fills on its way."""
@@ -239,8 +257,7 @@ class MipNerfModel:
         B = rays.origins.shape[0]
         dev = rays.origins.device
         ts = int(ts)
-        pc = variables['params']['box_centers']
-        pose = pc[ts].contiguous()
+        pose, box_enable = self._scene_edit(variables, ts, pose, box_enable, train)
         ext = ext.reshape(-1, 3).contiguous() if K > 0 else torch.zeros(0, 3, device=dev)
         radii = rays.radii.reshape(-1).contiguous()
         near, far = rays.near.reshape(-1).contiguous(), rays.far.reshape(-1).contiguous()
@@ -289,7 +306,7 @@ class MipNerfModel:
                         lay.mlp_size[W_OBJ], train)
         pro = ops.ray_prologue(rays.origins, rays.directions, pose, ext, rays.viewdirs, near, far, N,
                                noise['t_rand'] if (randomized and seed is None) else None, self.lindisp,
-                               pose_copy=pose_used, zero=zero_fill, seed=seed, pack=pack_arg)
+                               pose_copy=pose_used, zero=zero_fill, seed=seed, pack=pack_arg, box_enable=box_enable)
         o_s, d_s, hit, zo, view, t_vals0 = pro[:6]
         if seed is not None:
             noise = dict(t_rand=None, u_rand=pro[6])
@@ -540,12 +557,14 @@ class MipNerfModel:
         return (self.mlp_precision == 'bf16' and not (K and (not self.dynamics or self.object_precision() != 'bf16')) and
                 variables.flat.device.type == 'cuda')
 
-    def apply_one_call(self, variables, rng, rays, init, ext, ts, randomized, rand_bkgd, white_bkgd, alpha, noise=None):
+    def apply_one_call(self, variables, rng, rays, init, ext, ts, randomized, rand_bkgd, white_bkgd, alpha, noise=None, *,
+                       box_enable=None, pose=None):
         """`apply` through ONE library call (durf_forward, csrc/forward.hip): the orchestration of `_forward(train=False)`
         done in C for hosts that are not Python; same arguments, same list of 10-tuples, bit-identical results
         (tests/test_gpu_forward_call.py).  bf16 MLPs, objects on the bf16 kernels.  noise: dict(t_rand, u_rand[, density:
         the standard-normal draws [B,N] per level]) injected draws; otherwise `rng` keys the library's own (an int) or is the
-        torch.Generator they come from."""
+        torch.Generator they come from.
+        box_enable (K values 0 / 1) / pose ([K,6] in place of box_centers[ts]): as in apply() -- durf_forward_masked."""
         self._check()
         variables = self._kernel_variables(variables)
         lay = variables.layout
@@ -568,7 +587,7 @@ class MipNerfModel:
         if dn and seed is None and 'density' not in noise:      # injected sampling draws only: the generator apply() falls back to
             gd = _make_generator(rng, dev)
             noise = dict(noise, density=[torch.randn(B, N, device=dev, generator=gd) for _ in range(self.num_levels)])
-        pose = variables['params']['box_centers'][int(ts)].contiguous()
+        pose, box_enable = self._scene_edit(variables, ts, pose, box_enable)
         flags = ((ops.ENC_CONTRACT if self.contraction else 0) | (ops.ENC_NO_INTEGRATION if self.disable_integration else 0) |
                  (ops.ENC_CYLINDER if self.ray_shape == 'cylinder' else 0))
         o0 = lay.mlp_off['BoxMLP_0'] if K else 0
@@ -578,7 +597,7 @@ class MipNerfModel:
             variables.flat[o0:o0 + K * lay.mlp_size[W_OBJ]] if K else None, lay.mlp_size[W_OBJ], N, self.num_levels, alpha, flags,
             lindisp=self.lindisp, bkgd_mode=bk, density_bias=self.density_bias, resample_padding=self.resample_padding,
             t_rand=noise['t_rand'] if randomized else None, u_rand=noise['u_rand'] if randomized else None, seed=seed,
-            density_noise=dn, density_rand=noise.get('density') if dn else None)
+            density_noise=dn, density_rand=noise.get('density') if dn else None, box_enable=box_enable)
         box_rot0 = pose[0, 3:] if K > 0 else ops.const_tensor(dev, (3,))
         return [tuple(o) + ([pose[:, :3], box_rot0], dyn, zo) for o in outs]
 
@@ -606,13 +625,48 @@ class MipNerfModel:
             density_bias=self.density_bias, resample_padding=self.resample_padding)
         return rgb.reshape(height, width, 3), dist_.reshape(height, width), acc.reshape(height, width)
 
+    def render_layers(self, variables, rays, init, ext, ts, white_bkgd, alpha, chunk=8192, box_enable=None, pose=None,
+                      layers=ops.LAYER_NAMES):
+        """render_image_one_call plus the scene's layers, ONE library call (durf_render_layers, csrc/forward.hip) -> dict of
+        [H,W,.] tensors: rgb, distance, acc (the composite under box_enable / pose: what render_image_one_call returns);
+        'instance' in layers: instance int32 (k: the pixel shows exactly the enabled box k, -1 none, -2 several);
+        'background': bg_rgb, bg_distance, bg_acc (the image with every box disabled: a second pass over the box-hit rays alone);
+        'objects': obj_rgba (the composite without the background colour and acc as alpha on the box-hit rays, 0 elsewhere).
+        Same scope as render_image_one_call (supports_one_call)."""
+        layers = tuple(layers)
+        unknown = [n for n in layers if n not in ops.LAYER_NAMES]
+        if unknown:
+            raise ValueError('unknown layers %s: choose from %s' % (unknown, list(ops.LAYER_NAMES)))
+        self._check()
+        variables = self._kernel_variables(variables)
+        lay = variables.layout
+        K = lay.K
+        pose, box_enable = self._scene_edit(variables, ts, pose, box_enable)
+        if not self.supports_one_call(variables):
+            raise NotImplementedError('durf_render_layers covers the bf16 inference path (dynamics=True, bf16 object MLPs)')
+        height, width = rays[0].shape[:2]
+        flat = utils.namedtuple_map(lambda r: r.reshape(height * width, -1), rays)
+        flags = ((ops.ENC_CONTRACT if self.contraction else 0) | (ops.ENC_NO_INTEGRATION if self.disable_integration else 0) |
+                 (ops.ENC_CYLINDER if self.ray_shape == 'cylinder' else 0))
+        o0 = lay.mlp_off['BoxMLP_0'] if K else 0
+        out = ops.render_layers_call(
+            flat, pose, ext.reshape(-1, 3).contiguous() if K else None, variables.mlp_flat('MLP_0'),
+            variables.flat[o0:o0 + K * lay.mlp_size[W_OBJ]] if K else None, lay.mlp_size[W_OBJ], self.num_samples, self.num_levels,
+            alpha, flags, chunk, lindisp=self.lindisp, bkgd_mode=ops.BKGD_WHITE if white_bkgd else ops.BKGD_GREY,
+            density_bias=self.density_bias, resample_padding=self.resample_padding, box_enable=box_enable, layers=layers)
+        return {k: v.reshape((height, width) + tuple(v.shape[1:])) for k, v in out.items()}
+
     def apply(self, variables, rng, rays, init, ext, ts, randomized, rand_bkgd, white_bkgd, alpha,
-              noise=None):
+              noise=None, *, box_enable=None, pose=None):
         """model.apply(variables, key, rays, init, ext, ts, randomized=, rand_bkgd=, white_bkgd=,
         alpha=) -> list[num_levels] of (rgb, depth, acc, weights, t_vals, t_mids, t_dists,
-        [box_pose, box_rot0], dyn_mask, zo)   (train_boxpose.py:82-92, obbpose_model.py:258)."""
+        [box_pose, box_rot0], dyn_mask, zo)   (train_boxpose.py:82-92, obbpose_model.py:258).
+        Scene edits (not reference arguments; the reference's notebooks/durf_render_traj.ipynb does them by rebuilding the
+        tree): box_enable = K values 0 / 1, a box with 0 is absent -- every per-ray output equals the model whose tree has
+        that box cut out, bit for bit; pose = a [K,6] tensor used in place of box_centers[ts] (no gradient).  box_pose /
+        box_rot0 keep all K rows: they report the poses rendered with, the disabled boxes' included."""
         return self._forward(variables, rng, rays, init, ext, ts, randomized, rand_bkgd, white_bkgd,
-                             alpha, train=False, noise=noise)[0]
+                             alpha, train=False, noise=noise, box_enable=box_enable, pose=pose)[0]
 
     __call__ = apply
 

@@ -79,14 +79,31 @@ def _f32(t):
     return t
 
 
-def ray_setup(origins, dirs, pose, ext):
-    """-> origins_s[B,3], dirs_s[B,3], hit[B,K] int32, zo[B]"""
+def _enable(box_enable, K, dev):
+    """box_enable (None or K values 0 / 1) -> None or a contiguous int32 [K] tensor on `dev`: the device-side switch of the box
+    test (durf_ray_setup_masked).  A tensor already on the device is used where it is: no copy, no synchronisation."""
+    if box_enable is None:
+        return None
+    e = torch.as_tensor(box_enable)
+    if e.dim() != 1 or e.shape[0] != K:
+        raise ValueError('box_enable: %d values for K = %d boxes' % (e.numel(), K))
+    return e.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def ray_setup(origins, dirs, pose, ext, box_enable=None):
+    """-> origins_s[B,3], dirs_s[B,3], hit[B,K] int32, zo[B]; box_enable: durf_ray_setup_masked (a box with 0 is a miss)"""
     B, K = origins.shape[0], pose.shape[0]
     dev = origins.device
     o_s = torch.empty(B, 3, device=dev)
     d_s = torch.empty(B, 3, device=dev)
     hit = torch.empty(B, K, dtype=torch.int32, device=dev)
     zo = torch.empty(B, device=dev)
+    if box_enable is not None:
+        en = _enable(box_enable, K, dev)
+        _lib.check(_lib.lib().durf_ray_setup_masked(_stream(), B, K, _p(_f32(origins)), _p(_f32(dirs)), _p(_f32(pose)),
+                                                    _p(_f32(ext)), _p(en), _p(o_s), _p(d_s), _p(hit), _p(zo)),
+                   'durf_ray_setup_masked')
+        return o_s, d_s, hit, zo
     _lib.check(_lib.lib().durf_ray_setup(_stream(), B, K, _p(_f32(origins)), _p(_f32(dirs)),
                                          _p(_f32(pose)), _p(_f32(ext)), _p(o_s), _p(d_s), _p(hit),
                                          _p(zo)), 'durf_ray_setup')
@@ -94,8 +111,9 @@ def ray_setup(origins, dirs, pose, ext):
 
 
 def ray_prologue(origins, dirs, pose, ext, viewdirs, near, far, N, t_rand=None, lindisp=False, pose_copy=None, zero=None,
-                 seed=None, pack=None):
+                 seed=None, pack=None, box_enable=None):
     """ray_setup + view_enc (bf16) + sample_t as ONE launch (durf_ray_prologue)
+    box_enable (int32 [K] on the device): the box test of durf_ray_setup_masked (durf_ray_prologue_pack_masked)
     -> origins_s[B,3], dirs_s[B,3], hit[B,K] int32, zo[B], view[B,32] bf16, t_vals[B,N+1]
     pose_copy [K,6]: receives a snapshot of `pose`; zero: a contiguous fp32 tensor the launch zero fills (the gradient)
     seed (int, instead of t_rand): the launch draws the step's stratified-sampling noise itself (Philox under this key) and
@@ -124,6 +142,10 @@ def ray_prologue(origins, dirs, pose, ext, viewdirs, near, far, N, t_rand=None, 
               0 if zero is None else zero.numel(), lo, hi, _p(u_out))
     out = (o_s, d_s, hit, zo, view, t) if seed is None else (o_s, d_s, hit, zo, view, t, u_out)
     if pack is None:
+        if box_enable is not None:        # (no weight streams to pack: the masked launch with an empty packing list)
+            _lib.check(_lib.lib().durf_ray_prologue_pack_masked(*common, None, 0, None, None, 0, None, 0, 0, None, None, None, 0,
+                                                                _p(box_enable)), 'durf_ray_prologue_pack_masked')
+            return out
         _lib.check(_lib.lib().durf_ray_prologue(*common), 'durf_ray_prologue')
         return out
     bkgd_params, Kp, obj_params, obj_param_stride, want_bwd = pack
@@ -135,9 +157,12 @@ def ray_prologue(origins, dirs, pose, ext, viewdirs, near, far, N, t_rand=None, 
     if Kp:
         of = u8(Kp * int(L.durf_wpack_fwd_bytes(W_OBJ_)))
         ob = u8(Kp * int(L.durf_wpack_bwd_bytes(W_OBJ_))) if want_bwd else None
-    _lib.check(L.durf_ray_prologue_pack(*common, _p(_f32(bkgd_params)), IN_BKGD, _p(bf), _p(bb), int(Kp),
-                                        _p(obj_params) if Kp else None, int(obj_param_stride), IN_OBJ_, _p(of), _p(ob), None, 0),
-               'durf_ray_prologue_pack')
+    pack_args = (_p(_f32(bkgd_params)), IN_BKGD, _p(bf), _p(bb), int(Kp), _p(obj_params) if Kp else None, int(obj_param_stride),
+                 IN_OBJ_, _p(of), _p(ob), None, 0)
+    if box_enable is not None:
+        _lib.check(L.durf_ray_prologue_pack_masked(*common, *pack_args, _p(box_enable)), 'durf_ray_prologue_pack_masked')
+    else:
+        _lib.check(L.durf_ray_prologue_pack(*common, *pack_args), 'durf_ray_prologue_pack')
     return out + (((bf, bb), ((of, ob) if Kp else None)),)
 
 
@@ -230,6 +255,8 @@ DISPATCH = dict(FWD256_8W=0x1, FWD256_4W=0x2, FWD128_SAMPLE=0x4, FWD128_MSPLIT=0
                 BWD128_SAMPLE=0x40, BWD128_MSPLIT=0x80, DW256_256WG=0x100, DW256_512WG=0x200, DW128_128WG=0x400,
                 DW128_256WG=0x800, FWD_ENC=0x1000, FWD_RAW_FULL=0x2000, FWD_TAIL=0x4000, F32_DW_TILE=0x8000,
                 F32_DW_B2=0x10000, BWD_POSE=0x20000, FWD_MIX=0x40000, BWD_MIX=0x80000)
+# include/durf_hip.h DURF_LAYERLOG_*: marks of the scene-layer launches in the same log word (tests/test_gpu_layers.py)
+LAYER_LOG = dict(SELECT=0x100000, PASS2=0x200000, BOX_MASK=0x400000)
 
 
 def dispatch_reset():
@@ -240,6 +267,12 @@ def dispatch_seen():
     """names of the size-selected kernel variants launched since dispatch_reset() (durf_dispatch_seen)"""
     m = int(_lib.lib().durf_dispatch_seen())
     return {k for k, b in DISPATCH.items() if m & b}
+
+
+def layer_log_seen():
+    """which scene-layer launches ran since dispatch_reset() (DURF_LAYERLOG_*)"""
+    m = int(_lib.lib().durf_dispatch_seen())
+    return {k for k, b in LAYER_LOG.items() if m & b}
 
 
 ENC_CONTRACT, ENC_NO_INTEGRATION, ENC_CYLINDER = 1, 2, 4
@@ -1367,8 +1400,8 @@ def _fill_forward_args(a, rays, pose, ext, bkgd_params, obj_params, obj_param_st
 
 def forward_call(rays, pose, ext, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags, lindisp=False,
                  bkgd_mode=BKGD_GREY, density_bias=-1.0, resample_padding=0.01, t_rand=None, u_rand=None, seed=None,
-                 density_noise=0.0, density_rand=None):
-    """MipNerfModel.__call__ in inference as ONE library call (durf_forward): -> list[num_levels] of
+                 density_noise=0.0, density_rand=None, box_enable=None):
+    """MipNerfModel.__call__ in inference as ONE library call (durf_forward; box_enable int32 [K]: durf_forward_masked): -> list[num_levels] of
     (rgb, depth, acc, weights, t_vals, t_mids, t_dists), dyn_mask [B,1] int32, zo [B]"""
     B, K = rays.origins.shape[0], pose.shape[0]
     dev = rays.origins.device
@@ -1383,7 +1416,10 @@ def forward_call(rays, pose, ext, bkgd_params, obj_params, obj_param_stride, N, 
                        density_noise=density_noise, density_rand=density_rand)
     ws = _workspace(dev, int(L.durf_forward_workspace_bytes(B, N, K)))
     with _Timed('forward_call'):
-        _lib.check(L.durf_forward(_stream(), C.byref(a), _p(ws), ws.numel()), 'durf_forward')
+        if box_enable is not None:
+            _lib.check(L.durf_forward_masked(_stream(), C.byref(a), _p(box_enable), _p(ws), ws.numel()), 'durf_forward_masked')
+        else:
+            _lib.check(L.durf_forward(_stream(), C.byref(a), _p(ws), ws.numel()), 'durf_forward')
     return outs, dyn, zo
 
 
@@ -1406,6 +1442,40 @@ def render_image_call(rays, pose, ext, bkgd_params, obj_params, obj_param_stride
         _lib.check(L.durf_render_image(_stream(), C.byref(a), n, min(chunk, n), _p(rgb), _p(dist_), _p(acc), _p(ws), ws.numel()),
                    'durf_render_image')
     return rgb, dist_, acc
+
+
+LAYER_NAMES = ('instance', 'background', 'objects')
+
+
+def render_layers_call(rays, pose, ext, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags, chunk,
+                       lindisp=False, bkgd_mode=BKGD_GREY, density_bias=-1.0, resample_padding=0.01, box_enable=None,
+                       layers=LAYER_NAMES):
+    """render_image_call plus the scene layers of the image, ONE library call (durf_render_layers) -> dict: rgb [n,3],
+    distance [n], acc [n]; 'instance' in layers: instance [n] int32; 'background': bg_rgb / bg_distance / bg_acc;
+    'objects': obj_rgba [n,4].  box_enable: int32 [K] on the device or None.  A layer that is not asked for costs nothing."""
+    n, K = rays.origins.shape[0], pose.shape[0]
+    dev = rays.origins.device
+    L = _lib.lib()
+    f = lambda *sh: torch.empty(*sh, device=dev)
+    out = dict(rgb=f(n, 3), distance=f(n), acc=f(n))
+    if 'instance' in layers:
+        out['instance'] = torch.empty(n, dtype=torch.int32, device=dev)
+    if 'background' in layers:
+        out.update(bg_rgb=f(n, 3), bg_distance=f(n), bg_acc=f(n))
+    if 'objects' in layers:
+        out['obj_rgba'] = f(n, 4)
+    a = ForwardArgs()
+    keep = []
+    rays = type(rays)(*[t.contiguous() for t in rays])
+    _fill_forward_args(a, rays, pose, ext, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags, lindisp,
+                       bkgd_mode, density_bias, resample_padding, None, None, None, None, None, keep)
+    a.B = min(chunk, n)
+    ws = _workspace(dev, int(L.durf_render_layers_workspace_bytes(n, min(chunk, n), N, K, num_levels)))
+    with _Timed('render_layers_call'):
+        _lib.check(L.durf_render_layers(_stream(), C.byref(a), _p(box_enable), n, min(chunk, n), _p(out['rgb']), _p(out['distance']),
+                                        _p(out['acc']), _p(out.get('instance')), _p(out.get('bg_rgb')), _p(out.get('bg_distance')),
+                                        _p(out.get('bg_acc')), _p(out.get('obj_rgba')), _p(ws), ws.numel()), 'durf_render_layers')
+    return out
 
 
 _WORKSPACE = {}

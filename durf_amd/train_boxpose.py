@@ -789,10 +789,19 @@ def make_render_fn(model, config, variables, one_call=None):
     return render_fn
 
 
-def evaluate(model, config, variables, test_case, alpha, chunk=8192, rng=0):
-    """One test image (train_boxpose.py:535-563): render, PSNR, SSIM.  -> dict(psnr, ssim, rgb, distance, acc, rays)"""
+def evaluate(model, config, variables, test_case, alpha, chunk=8192, rng=0, layers=False):
+    """One test image (train_boxpose.py:535-563): render, PSNR, SSIM.  -> dict(psnr, ssim, rgb, distance, acc, rays)
+    layers=True (one device, supports_one_call): the image through MipNerfModel.render_layers, and the dict also carries
+    instance, bg_rgb / bg_distance / bg_acc and obj_rgba"""
     from . import metrics
-    if _dist() is None and model.supports_one_call(variables):
+    extra = {}
+    if layers:
+        if _dist() is not None:
+            raise NotImplementedError('evaluate(layers=True) renders on one device')
+        extra = model.render_layers(variables, test_case['rays'], test_case['init'], test_case['ext'], test_case['ts'],
+                                    config.white_bkgd, alpha, chunk=chunk)
+        rgb, dist_, acc = extra.pop('rgb'), extra.pop('distance'), extra.pop('acc')
+    elif _dist() is None and model.supports_one_call(variables):
         # one device: the whole image as ONE C call (durf_render_image: the chunk loop over the resident ray buffer)
         rgb, dist_, acc = model.render_image_one_call(variables, test_case['rays'], test_case['init'], test_case['ext'],
                                                       test_case['ts'], config.white_bkgd, alpha, chunk=chunk)
@@ -802,7 +811,7 @@ def evaluate(model, config, variables, test_case, alpha, chunk=8192, rng=0):
     gt = test_case['pixels'][..., :3]
     psnr = dmath.mse_to_psnr(((rgb - gt) ** 2).mean())                                   # :562
     ssim = metrics.compute_ssim(rgb, gt, 1.0) if rgb.is_cuda else None                   # :563
-    return dict(psnr=psnr, ssim=ssim, rgb=rgb, distance=dist_, acc=acc, rays=rgb.shape[0] * rgb.shape[1])
+    return dict(psnr=psnr, ssim=ssim, rgb=rgb, distance=dist_, acc=acc, rays=rgb.shape[0] * rgb.shape[1], **extra)
 
 
 def train_loop(model, config, state, dataset, test_dataset=None, train_dir=None, render_every=0, chunk=8192,

@@ -38,6 +38,9 @@ def bind(path='durf_amd/libdurf_hip.so'):
     L.durf_ray_setup.restype = i32
     L.durf_ray_setup.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     #   (stream, B, K, origins, dirs, pose, ext, origins_s, dirs_s, hit, zo)
+    L.durf_ray_setup_masked.restype = i32
+    L.durf_ray_setup_masked.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    #   (stream, B, K, origins, dirs, pose, ext, box_enable, origins_s, dirs_s, hit, zo)
     L.durf_compact_hits.restype = i32
     L.durf_compact_hits.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     #   (stream, B, K, hit, idx, count, slot)
@@ -53,6 +56,9 @@ def bind(path='durf_amd/libdurf_hip.so'):
     L.durf_ray_prologue_pack.restype = i32
     L.durf_ray_prologue_pack.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp, i32, vp, vp, i32, vp, u64, i32, vp, vp, vp, u64]
     #   (stream, B, K, N, origins, dirs, pose, ext, origins_s, dirs_s, hit, zo, viewdirs, view_bf16, near, far, t_rand, lindisp, t_vals, pose_copy, zero_buf, zero_count, seed_lo, seed_hi, u_rand_out, bkgd_params, in_bkgd, bkgd_fwd, bkgd_bwd, K_pack, obj_params, obj_param_stride, in_obj, obj_fwd, obj_bwd, zero_buf2, zero_count2)
+    L.durf_ray_prologue_pack_masked.restype = i32
+    L.durf_ray_prologue_pack_masked.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp, i32, vp, vp, i32, vp, u64, i32, vp, vp, vp, u64, vp]
+    #   (stream, B, K, N, origins, dirs, pose, ext, origins_s, dirs_s, hit, zo, viewdirs, view_bf16, near, far, t_rand, lindisp, t_vals, pose_copy, zero_buf, zero_count, seed_lo, seed_hi, u_rand_out, bkgd_params, in_bkgd, bkgd_fwd, bkgd_bwd, K_pack, obj_params, obj_param_stride, in_obj, obj_fwd, obj_bwd, zero_buf2, zero_count2, box_enable)
     L.durf_sample_t.restype = i32
     L.durf_sample_t.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp]
     #   (stream, B, N, near, far, t_rand, lindisp, t_vals)
@@ -146,6 +152,15 @@ def bind(path='durf_amd/libdurf_hip.so'):
     L.durf_render_image.restype = i32
     L.durf_render_image.argtypes = [vp, vp, u64, i32, vp, vp, vp, vp, u64]
     #   (stream, args, n_rays, chunk, rgb, distance, acc, workspace, workspace_bytes)
+    L.durf_forward_masked.restype = i32
+    L.durf_forward_masked.argtypes = [vp, vp, vp, vp, u64]
+    #   (stream, args, box_enable, workspace, workspace_bytes)
+    L.durf_render_layers_workspace_bytes.restype = u64
+    L.durf_render_layers_workspace_bytes.argtypes = [u64, i32, i32, i32, i32]
+    #   (n_rays, chunk, N, K, num_levels)
+    L.durf_render_layers.restype = i32
+    L.durf_render_layers.argtypes = [vp, vp, vp, u64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64]
+    #   (stream, args, box_enable, n_rays, chunk, rgb, distance, acc, instance, bg_rgb, bg_distance, bg_acc, obj_rgba, workspace, workspace_bytes)
     L.durf_train_workspace_bytes.restype = u64
     L.durf_train_workspace_bytes.argtypes = [i32, i32, i32, i32, u64]
     #   (B, N, K, num_levels, n_params)

@@ -66,6 +66,11 @@ int durf_version(void);
 #define DURF_DISPATCH_BWD_POSE 0x20000     /* k_mlp_bwd<.., POSE>: d(enc) for the box-pose gradient */
 #define DURF_DISPATCH_FWD_MIX 0x40000      /* k_mlp_fwd<256, .., MIX>: background blocks + the object MLPs' items in ONE launch */
 #define DURF_DISPATCH_BWD_MIX 0x80000      /* k_mlp_bwd<256, .., MIX>: the same for the backward */
+/* Marks of the scene-layer launches in the same log word (not size-selected variants: they say that the launch ran at all,
+ * so that "a layer that is not asked for costs no launch" can be tested). */
+#define DURF_LAYERLOG_SELECT 0x100000       /* durf_render_layers: instance map / image-wide compaction of the box-hit rays */
+#define DURF_LAYERLOG_PASS2 0x200000        /* durf_render_layers: gather / scatter around the second (K = 0) pass */
+#define DURF_LAYERLOG_BOX_MASK 0x400000     /* the box test ran with a device-side box_enable */
 int durf_dispatch_seen(void);
 int durf_dispatch_reset(void);
 
@@ -98,6 +103,14 @@ int durf_pack_weights_all(void* stream, const float* bkgd_params, int in_bkgd, v
 int durf_ray_setup(void* stream, int B, int K, const float* origins, const float* dirs,
                    const float* pose, const float* ext, float* origins_s, float* dirs_s,
                    int32_t* hit, float* zo);
+
+/* durf_ray_setup with a device-side switch per box: box_enable [K] int32 0 / 1 (nullable = every box on).  A box with 0 is
+ * ABSENT: its column of `intersection` (obbpose_model.py:112-115) is zero and it adds nothing to origins_s / dirs_s / zo --
+ * the results are those of the model whose parameter tree has that box's rows cut out, bit for bit, with hit keeping its K
+ * columns.  All ones (or NULL) is durf_ray_setup. */
+int durf_ray_setup_masked(void* stream, int B, int K, const float* origins, const float* dirs,
+                          const float* pose, const float* ext, const int32_t* box_enable /* nullable */, float* origins_s,
+                          float* dirs_s, int32_t* hit, float* zo);
 
 /* deterministic stream compaction of hit[:,k]: idx[k*B + j] = j-th ray hitting k,
  * count[k] = number of such rays, slot[b*K+k] = position of ray b in list k or -1. */
@@ -143,6 +156,16 @@ int durf_ray_prologue_pack(void* stream, int B, int K, int N, const float* origi
                            void* bkgd_bwd /* nullable */, int K_pack, const float* obj_params, size_t obj_param_stride,
                            int in_obj, void* obj_fwd, void* obj_bwd /* nullable */,
                            float* zero_buf2 /* nullable: a second, small region to zero fill (4-byte words) */, size_t zero_count2);
+/* durf_ray_prologue_pack whose box test reads box_enable (durf_ray_setup_masked); NULL: durf_ray_prologue_pack. */
+int durf_ray_prologue_pack_masked(void* stream, int B, int K, int N, const float* origins, const float* dirs, const float* pose,
+                                  const float* ext, float* origins_s, float* dirs_s, int32_t* hit, float* zo,
+                                  const float* viewdirs, void* view_bf16, const float* near, const float* far,
+                                  const float* t_rand /* nullable */, int lindisp, float* t_vals, float* pose_copy /* nullable */,
+                                  float* zero_buf /* nullable */, size_t zero_count, uint32_t seed_lo, uint32_t seed_hi,
+                                  float* u_rand_out /* nullable */, const float* bkgd_params, int in_bkgd, void* bkgd_fwd,
+                                  void* bkgd_bwd /* nullable */, int K_pack, const float* obj_params, size_t obj_param_stride,
+                                  int in_obj, void* obj_fwd, void* obj_bwd /* nullable */,
+                                  float* zero_buf2 /* nullable */, size_t zero_count2, const int32_t* box_enable /* nullable */);
 
 /* mip.sample_along_rays t_vals (mip.py:353-368). t_rand nullable (randomized=False). */
 int durf_sample_t(void* stream, int B, int N, const float* near, const float* far,
@@ -444,6 +467,31 @@ int durf_forward(void* stream, const durf_forward_args* args, void* workspace, s
 size_t durf_render_image_workspace_bytes(int chunk, int N, int K, int num_levels);
 int durf_render_image(void* stream, const durf_forward_args* args, size_t n_rays, int chunk, float* rgb, float* distance,
                       float* acc, void* workspace, size_t workspace_bytes);
+/* durf_forward with boxes switched off on the device: box_enable [K] int32 0 / 1 (nullable = durf_forward).  The outputs are
+ * those of the model without the disabled boxes (their box_centers columns, ext rows and BoxMLP_k deleted), bit for bit;
+ * multi-hit rays keep the reference's summing quirk over the ENABLED boxes.  Same workspace as durf_forward. */
+int durf_forward_masked(void* stream, const durf_forward_args* args, const int32_t* box_enable /* nullable */, void* workspace,
+                        size_t workspace_bytes);
+/* Scene layers of an image in one call: durf_render_image under box_enable (nullable) and args->pose (any [K,6] device
+ * buffer: edited poses need no parameter tree), plus, each NULLABLE and skipped when NULL:
+ *   instance [n_rays] int32     k if the ray hits exactly the enabled box k, -1 none, -2 several;
+ *   bg_rgb [n_rays,3], bg_distance, bg_acc [n_rays] (all three or none)
+ *                               the image with EVERY box disabled: copies of the composite where instance == -1, elsewhere
+ *                               a second pass of durf_forward's launch sequence with K = 0 over the box-hit rays alone,
+ *                               gathered into a dense buffer and rendered in chunks of `chunk` -- bit-identical to
+ *                               durf_render_image of the K = 0 model;
+ *   obj_rgba [n_rays,4]         where instance != -1: rgb - bg * (1 - acc) (the composite of bkgd_mode 2) and acc; else 0.
+ *                               16-byte aligned (one vector store per ray).
+ * With every layer pointer and box_enable NULL the call issues durf_render_image's launches and nothing else.  The
+ * number of box-hit rays is read back ONCE per image (4 bytes; the stream is synchronised there) to size the second
+ * pass, so the call cannot be captured into a graph when bg_* is requested.  n_rays < 2^27; the image-wide compaction is ONE
+ * workgroup (4096 rays per round), sized for images of up to a few million rays, not for the limit.
+ * workspace: durf_render_layers_workspace_bytes(n_rays, chunk, N, K, num_levels) bytes, 256-byte aligned, size checked. */
+size_t durf_render_layers_workspace_bytes(size_t n_rays, int chunk, int N, int K, int num_levels);
+int durf_render_layers(void* stream, const durf_forward_args* args, const int32_t* box_enable /* nullable */, size_t n_rays,
+                       int chunk, float* rgb, float* distance, float* acc, int32_t* instance /* nullable */,
+                       float* bg_rgb /* nullable */, float* bg_distance /* nullable */, float* bg_acc /* nullable */,
+                       float* obj_rgba /* nullable */, void* workspace, size_t workspace_bytes);
 
 /* ---- one shard's training step as ONE call (csrc/train.hip) ------------------------------------------------
  * durf_loss_backward: value_and_grad(loss_fn) of train_step (train_boxpose.py:67-252) -- the forward with activations
