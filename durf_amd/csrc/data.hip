@@ -2,6 +2,7 @@
 // the SSIM evaluation metric (internal/math.py:66-137): the callers / data formats either side of the
 // hot path.  HBM-bound gathers and small stencils; fp32 like the reference.
 #include "durf_common.h"
+#include "pinhole.h"
 
 struct CamTable { float v[DURF_MAX_CAMS][17]; int first[DURF_MAX_CAMS + 1]; int n; };
 
@@ -19,34 +20,8 @@ k_gen_batch(int B, CamTable cams, const int32_t* __restrict__ ray_idx, float nea
     int c = 0;
     for (int k = 1; k < cams.n; k++) c += (r >= cams.first[k]) ? 1 : 0;
     const float* cam = cams.v[c];
-    const int w = (int)cam[16], h = (int)cam[15];
-    const int p = r - cams.first[c];
-    const int y = p / w, x = p - y * w;
-    auto dir = [&](int yy, float* d) {           // :1882-1889: d = sum_j cam_dirs_j * R[:, j], in that order
-        const float cd[3] = {((float)x - cam[13]) / cam[12], -((float)yy - cam[14]) / cam[12], -1.0f};
-#pragma unroll
-        for (int a = 0; a < 3; a++) d[a] = (cd[0] * cam[4 * a] + cd[1] * cam[4 * a + 1]) + cd[2] * cam[4 * a + 2];
-    };
-    float d[3], dn[3];
-    dir(y, d);
-    // radius: distance to the next row's direction; the last row repeats the previous one (:1896-1902)
-    const int y0 = (y < h - 1) ? y : h - 2;
-    float d0[3];
-    dir(y0, d0);
-    dir(y0 + 1, dn);
-    const float dx = sqrtf(((d0[0] - dn[0]) * (d0[0] - dn[0]) + (d0[1] - dn[1]) * (d0[1] - dn[1])) +
-                           (d0[2] - dn[2]) * (d0[2] - dn[2]));
-    const float nrm = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        origins[i * 3 + a] = cam[4 * a + 3];
-        dirs[i * 3 + a] = d[a];
-        viewdirs[i * 3 + a] = d[a] / nrm;
-    }
-    radii[i] = dx * 2.0f / 3.4641016151377544f;       // 2 / sqrt(12)
+    pinhole_ray(cam, r - cams.first[c], near, far, i, origins, dirs, viewdirs, radii, near_o, far_o);      // csrc/pinhole.h
     lossmult[i] = 1.0f;
-    near_o[i] = near;
-    far_o[i] = far;
     if (pixels) for (int a = 0; a < img_channels; a++) pixels[(size_t)i * img_channels + a] = images[(size_t)r * img_channels + a];
     if (depth_o) depth_o[i] = depth[r];
     if (sky_o) sky_o[i] = sky[r];

@@ -282,4 +282,110 @@ int durf_render_layers(void* stream, const durf_forward_args* a, const int32_t* 
     return durf::launch_layer_scatter(stream, n_hit, w.idx, w.rgb2, w.dist2, w.acc2, bg_rgb, bg_distance, bg_acc);
 }
 
+// ---- a camera trajectory (include/durf_hip.h durf_render_trajectory; kernels: csrc/trajectory.hip) ----------------------
+namespace {
+struct TrajWs { ImgWs img; float* rays[6]; float* poses; size_t total; };
+TrajWs carve_trajectory(void* workspace, int F, int chunk, int N, int K, int L) {
+    TrajWs w{};
+    w.img = carve_image(workspace, chunk, N, K, L);
+    Carver c{(char*)workspace, w.img.total};
+    for (int f = 0; f < 6; f++) w.rays[f] = (float*)c.take((size_t)chunk * (f < 3 ? 3 : 1) * 4);       // one chunk's rays
+    w.poses = (float*)c.take((size_t)(F > 0 ? F : 0) * (K > 0 ? K : 0) * 6 * 4);                        // (when poses_out is NULL)
+    w.total = (c.off + 255) & ~(size_t)255;
+    return w;
+}
+}  // namespace
+
+int durf_camera_rays(void* stream, const float* cams_host, int first, int count, float near, float far, float* origins,
+                     float* directions, float* viewdirs, float* radii, float* near_out, float* far_out) {
+    DURF_REQUIRE(cams_host && origins && directions && viewdirs && radii && near_out && far_out, "the camera row and the six ray fields");
+    DURF_REQUIRE(cams_host[15] >= 2 && cams_host[16] >= 1, "camera height >= 2, width >= 1");
+    const long n = (long)(int)cams_host[15] * (int)cams_host[16];
+    DURF_REQUIRE(first >= 0 && count >= 0 && (long)first + count <= n, "pixels [first, first + count) inside the image");
+    float* const rays[6] = {origins, directions, viewdirs, radii, near_out, far_out};
+    return durf::launch_camera_rays(stream, cams_host, first, count, near, far, rays);
+}
+
+size_t durf_render_trajectory_workspace_bytes(int F, int chunk, int N, int K, int num_levels) {
+    return carve_trajectory(nullptr, F, chunk, N, K, num_levels).total;
+}
+
+int durf_render_trajectory(void* stream, const durf_forward_args* a, const int32_t* box_enable, const float* box_centers, int T, int F,
+                           const float* cams_host, const float* times_host, float near, float far, int chunk, uint8_t* rgb8, float* rgb,
+                           float* distance, float* acc, float* poses_out, void* workspace, size_t workspace_bytes) {
+    DURF_REQUIRE(a != nullptr && workspace != nullptr, "arguments and workspace");
+    DURF_REQUIRE(F > 0 && times_host != nullptr, "F > 0 frames and their times");
+    const bool image = rgb8 || rgb || distance || acc;
+    DURF_REQUIRE(image || poses_out, "at least one output");
+    DURF_REQUIRE(chunk > 0, "chunk > 0");
+    DURF_REQUIRE(a->t_rand == nullptr && a->u_rand == nullptr && !a->draw_noise && a->density_noise == 0.0f,
+                 "render_trajectory is test mode: randomized = False (obbpose_model.py:421-479)");
+    const int L = a->num_levels, K = a->K;
+    DURF_REQUIRE(L >= 1 && L <= DURF_FORWARD_MAX_LEVELS, "1 <= num_levels <= DURF_FORWARD_MAX_LEVELS");
+    DURF_REQUIRE(K >= 0 && K <= DURF_MAX_OBJ, "0 <= K <= DURF_MAX_OBJ");
+    DURF_REQUIRE(T >= 1 && (K == 0 || box_centers != nullptr), "T >= 1 timesteps of box_centers");
+    for (int f = 0; f < F; f++)
+        if (!(times_host[f] >= 0.0f && times_host[f] <= (float)(T - 1))) {
+            durf_set_error("durf_render_trajectory: time %g of frame %d is outside [0, %d] (T = %d timesteps)", (double)times_host[f], f,
+                           T - 1, T);
+            return -1;
+        }
+    int h = 0, wd = 0;
+    if (image) {
+        DURF_REQUIRE(cams_host != nullptr, "the camera rows");
+        h = (int)cams_host[15]; wd = (int)cams_host[16];
+        DURF_REQUIRE(cams_host[15] >= 2 && cams_host[16] >= 1, "camera height >= 2, width >= 1");
+        DURF_REQUIRE((size_t)h * wd < ((size_t)1 << 27), "h * w < 2^27");
+        for (int f = 1; f < F; f++)
+            if ((int)cams_host[f * 17 + 15] != h || (int)cams_host[f * 17 + 16] != wd) {
+                durf_set_error("durf_render_trajectory: frame %d is %d x %d, frame 0 is %d x %d: all frames share one image size", f,
+                               (int)cams_host[f * 17 + 15], (int)cams_host[f * 17 + 16], h, wd);
+                return -1;
+            }
+    }
+    const TrajWs w = carve_trajectory(workspace, F, chunk, a->N, K, L);
+    if (workspace_bytes < w.total) {
+        durf_set_error("durf_render_trajectory: workspace of %zu bytes, durf_render_trajectory_workspace_bytes(%d, %d, %d, %d, %d) = %zu",
+                       workspace_bytes, F, chunk, a->N, K, L, w.total);
+        return -1;
+    }
+    int rc;
+    if (image) {                                    // (every chunk passes the same checks: nothing is refused after a launch)
+        durf_forward_args c0 = *a;
+        c0.B = 1;
+        if ((rc = check_forward_args(&c0, workspace)) != 0) return rc;
+    }
+    float* poses = poses_out ? poses_out : w.poses;
+    rc = durf::launch_pose_interp(stream, F, K, times_host, box_centers, poses);
+    if (rc != 0 || !image) return rc;
+    const size_t n = (size_t)h * wd;
+    for (int f = 0; f < F; f++) {
+        for (size_t i = 0; i < n; i += (size_t)chunk) {
+            durf_forward_args c = *a;
+            c.B = (int)(n - i < (size_t)chunk ? n - i : (size_t)chunk);
+            rc = durf::launch_camera_rays(stream, cams_host + (size_t)f * 17, (int)i, c.B, near, far, w.rays);
+            if (rc != 0) return rc;
+            c.origins = w.rays[0]; c.directions = w.rays[1]; c.viewdirs = w.rays[2]; c.radii = w.rays[3]; c.near = w.rays[4]; c.far = w.rays[5];
+            c.pose = K > 0 ? poses + (size_t)f * K * 6 : nullptr;
+            const size_t at = (size_t)f * n + i;
+            for (int l = 0; l < L; l++) {           // an output that is not asked for stays in the workspace, per chunk
+                const bool last = l == L - 1;
+                c.rgb[l] = last && rgb ? rgb + at * 3 : w.img.rgb[l]; c.depth[l] = last && distance ? distance + at : w.img.depth[l];
+                c.acc[l] = last && acc ? acc + at : w.img.acc[l];
+                c.weights[l] = w.img.weights[l]; c.t_vals[l] = w.img.t_vals[l]; c.t_mids[l] = w.img.t_mids[l]; c.t_dists[l] = w.img.t_dists[l];
+            }
+            c.zo = w.img.zo; c.dyn_mask = w.img.dyn;
+            rc = check_forward_args(&c, workspace);
+            if (rc != 0) return rc;
+            rc = forward_launches(stream, &c, w.img.f, box_enable);
+            if (rc != 0) return rc;
+            if (rgb8) {
+                rc = durf::launch_frame_pack(stream, c.B, c.rgb[L - 1], rgb8 + at * 3);
+                if (rc != 0) return rc;
+            }
+        }
+    }
+    return 0;
+}
+
 }  // extern "C"

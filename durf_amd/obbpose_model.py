@@ -656,6 +656,50 @@ class MipNerfModel:
             density_bias=self.density_bias, resample_padding=self.resample_padding, box_enable=box_enable, layers=layers)
         return {k: v.reshape((height, width) + tuple(v.shape[1:])) for k, v in out.items()}
 
+    def _trajectory_call(self, variables, cams, times, ext, white_bkgd, alpha, near, far, chunk, box_enable, outputs, out=None):
+        self._check()
+        variables = self._kernel_variables(variables)
+        lay = variables.layout
+        K = lay.K
+        if not self.supports_one_call(variables):
+            raise NotImplementedError('durf_render_trajectory covers the bf16 inference path (dynamics=True, bf16 object MLPs)')
+        en = ops._enable(box_enable, K, variables.flat.device) if K > 0 else None
+        flags = ((ops.ENC_CONTRACT if self.contraction else 0) | (ops.ENC_NO_INTEGRATION if self.disable_integration else 0) |
+                 (ops.ENC_CYLINDER if self.ray_shape == 'cylinder' else 0))
+        o0 = lay.mlp_off['BoxMLP_0'] if K else 0
+        return ops.render_trajectory(
+            cams, times, variables['params']['box_centers'], ext.reshape(-1, 3).contiguous() if (K and ext is not None) else None,
+            variables.mlp_flat('MLP_0'), variables.flat[o0:o0 + K * lay.mlp_size[W_OBJ]] if K else None, lay.mlp_size[W_OBJ],
+            self.num_samples, self.num_levels, alpha, flags, chunk, near, far, lindisp=self.lindisp,
+            bkgd_mode=ops.BKGD_WHITE if white_bkgd else ops.BKGD_GREY, density_bias=self.density_bias,
+            resample_padding=self.resample_padding, box_enable=en, outputs=outputs, out=out)
+
+    def render_trajectory(self, variables, cams, times, ext, white_bkgd, alpha, *, near, far, chunk=8192, box_enable=None,
+                          outputs=('rgb8', 'distance', 'acc'), out=None):
+        """A camera flown through the scene while the boxes move (the reference's notebooks/durf_render_traj.ipynb loop), ONE
+        library call (durf_render_trajectory, csrc/forward.hip): cams [F,17] host camera rows (raygen.camera_row; one image
+        size), times [F] in [0, T - 1], fractional times take the boxes between two labelled timesteps (interpolate_pose) ->
+        dict of [F,h,w,.] tensors for the requested `outputs` ('rgb8' uint8, 'rgb', 'distance', 'acc') plus 'poses' [F,K,6].
+        The rays are generated per chunk on the device and the frames written in place: no image-sized ray buffer, nothing
+        that grows with F but the outputs.  Float outputs are bit-identical to render_layers(camera_rays(cam_f), ts=floor(t_f),
+        pose=poses[f], box_enable=...).  out: dict of preallocated [F,h*w,.] tensors.  Same scope as render_image_one_call."""
+        import numpy as np
+        outputs = tuple(outputs)
+        if not outputs:           # poses only: nothing is rendered and no camera is looked at
+            return self._trajectory_call(variables, None, times, ext, white_bkgd, alpha, near, far, chunk, box_enable, (), out)
+        cams = np.asarray(cams, np.float32).reshape(-1, 17)
+        res = self._trajectory_call(variables, cams, times, ext, white_bkgd, alpha, near, far, chunk, box_enable, outputs, out)
+        h, w = int(cams[0, 15]), int(cams[0, 16])
+        return {k: (v if k == 'poses' else v.reshape((v.shape[0], h, w) + tuple(v.shape[2:]))) for k, v in res.items()}
+
+    def interpolate_pose(self, variables, t):
+        """box poses [K,6] at the (fractional) time t in [0, T - 1], by the kernel render_trajectory uses (k_pose_interp, F = 1):
+        positions lerped, each angle along the shorter arc, an integer t copies box_centers[t] verbatim.  What to hand to
+        render_layers(pose=) for a single in-between frame."""
+        if variables.layout.K == 0 and self.supports_one_call(variables):
+            return variables['params']['box_centers'].new_empty(0, 6)
+        return self._trajectory_call(variables, None, [float(t)], None, False, 0.0, 0.0, 1.0, 1, None, ())['poses'][0]
+
     def apply(self, variables, rng, rays, init, ext, ts, randomized, rand_bkgd, white_bkgd, alpha,
               noise=None, *, box_enable=None, pose=None):
         """model.apply(variables, key, rays, init, ext, ts, randomized=, rand_bkgd=, white_bkgd=,

@@ -256,7 +256,7 @@ DISPATCH = dict(FWD256_8W=0x1, FWD256_4W=0x2, FWD128_SAMPLE=0x4, FWD128_MSPLIT=0
                 DW128_256WG=0x800, FWD_ENC=0x1000, FWD_RAW_FULL=0x2000, FWD_TAIL=0x4000, F32_DW_TILE=0x8000,
                 F32_DW_B2=0x10000, BWD_POSE=0x20000, FWD_MIX=0x40000, BWD_MIX=0x80000)
 # include/durf_hip.h DURF_LAYERLOG_*: marks of the scene-layer launches in the same log word (tests/test_gpu_layers.py)
-LAYER_LOG = dict(SELECT=0x100000, PASS2=0x200000, BOX_MASK=0x400000)
+LAYER_LOG = dict(SELECT=0x100000, PASS2=0x200000, BOX_MASK=0x400000, TRAJ_RAYS=0x800000, TRAJ_POSE=0x1000000, TRAJ_PACK=0x2000000)
 
 
 def dispatch_reset():
@@ -1476,6 +1476,62 @@ def render_layers_call(rays, pose, ext, bkgd_params, obj_params, obj_param_strid
                                         _p(out['acc']), _p(out.get('instance')), _p(out.get('bg_rgb')), _p(out.get('bg_distance')),
                                         _p(out.get('bg_acc')), _p(out.get('obj_rgba')), _p(ws), ws.numel()), 'durf_render_layers')
     return out
+
+
+TRAJECTORY_OUTPUTS = ('rgb8', 'rgb', 'distance', 'acc')
+
+
+def render_trajectory(cams, times, box_centers, ext, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags,
+                      chunk, near, far, lindisp=False, bkgd_mode=BKGD_GREY, density_bias=-1.0, resample_padding=0.01,
+                      box_enable=None, outputs=('rgb8', 'distance', 'acc'), out=None):
+    """A camera trajectory as ONE library call (durf_render_trajectory): cams [F,17] host rows (durf_gen_batch's layout, one
+    image size), times [F] host floats in [0, T - 1], box_centers [T,K,6] on the device (read there: no host copy) -> dict:
+    the requested `outputs` of rgb8 [F,n,3] uint8, rgb [F,n,3], distance [F,n], acc [F,n], and poses [F,K,6], the box poses
+    every frame was rendered with.  outputs = (): poses only, nothing is rendered (cams may be None).  out: dict of
+    preallocated contiguous tensors to write into.  The call only enqueues work."""
+    import numpy as np
+    outputs = tuple(outputs)
+    unknown = [o for o in outputs if o not in TRAJECTORY_OUTPUTS]
+    if unknown:
+        raise ValueError('unknown outputs %s: choose from %s' % (unknown, list(TRAJECTORY_OUTPUTS)))
+    times = np.ascontiguousarray(np.asarray(times, np.float32).reshape(-1))
+    F = int(times.shape[0])
+    T, K = int(box_centers.shape[0]), int(box_centers.shape[1])
+    dev = box_centers.device
+    L = _lib.lib()
+    n = 0
+    cam_arr = None
+    if outputs:
+        cams = np.ascontiguousarray(np.asarray(cams, np.float32).reshape(-1, 17))
+        if cams.shape[0] != F:
+            raise ValueError('%d camera rows for %d frame times' % (cams.shape[0], F))
+        n = int(cams[0, 15]) * int(cams[0, 16]) if F else 0
+        cam_arr = (C.c_float * cams.size)(*cams.reshape(-1).tolist())
+    shapes = dict(rgb8=((F, n, 3), torch.uint8), rgb=((F, n, 3), torch.float32), distance=((F, n), torch.float32),
+                  acc=((F, n), torch.float32), poses=((F, K, 6), torch.float32))
+    res = {}
+    for name in outputs + ('poses',):
+        shape, dtype = shapes[name]
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        assert tuple(t.shape) == shape and t.dtype == dtype and t.is_cuda and t.is_contiguous(), (name, tuple(t.shape), t.dtype)
+        res[name] = t
+    a = ForwardArgs()
+    a.B, a.N, a.K, a.num_levels, a.enc_flags, a.lindisp, a.bkgd_mode = min(chunk, max(n, 1)), N, K, num_levels, enc_flags, int(lindisp), bkgd_mode
+    a.density_bias, a.resample_padding = density_bias, resample_padding
+    a.barf_w = (C.c_float * 10)(*[float(x) for x in barf_weights(alpha)])
+    a.ext = _p(_f32(ext)) if (K and ext is not None) else None      # (poses only: nothing is rendered)
+    a.bkgd_params = _p(_f32(bkgd_params))
+    a.obj_params, a.obj_param_stride = (_p(_f32(obj_params)) if K else None), int(obj_param_stride)
+    ck = min(chunk, max(n, 1))
+    ws = _workspace(dev, int(L.durf_render_trajectory_workspace_bytes(F, ck, N, K, num_levels)))
+    with _Timed('render_trajectory'):
+        _lib.check(L.durf_render_trajectory(_stream(), C.byref(a), _p(box_enable), _p(_f32(box_centers)) if K else None, T, F, cam_arr,
+                                            (C.c_float * max(F, 1))(*times.tolist()), float(near), float(far), ck, _p(res.get('rgb8')),
+                                            _p(res.get('rgb')), _p(res.get('distance')), _p(res.get('acc')), _p(res['poses']),
+                                            _p(ws), ws.numel()), 'durf_render_trajectory')
+    return res
 
 
 _WORKSPACE = {}

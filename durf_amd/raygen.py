@@ -52,6 +52,28 @@ def generate_batch(ts_data, ray_indices, near, far):
     return utils.BoxRays(o, d, v, r, lm, nr, fr), px, dp, sk
 
 
+def camera_row(c2w, focal, principal_point, h, w):
+    """one camera as the 17 floats of durf_gen_batch's table: c2w [3,4] row-major, focal, principal point x / y, h, w"""
+    row = np.zeros(17, np.float32)
+    row[:12] = np.asarray(c2w, np.float32)[:3, :4].reshape(-1)
+    row[12:] = (focal, principal_point[0], principal_point[1], h, w)
+    return row
+
+
+def camera_rays(cam17, near, far, device='cuda'):
+    """-> BoxRays of [h, w, .] fields on the device for ONE camera row (camera_row): the pinhole generator of generate_batch
+    through k_camera_rays (durf_camera_rays) -- bit-identical to generate_batch(ray_indices=None) on a one-camera timestep,
+    with no TimestepData to build.  What render_image_one_call / render_layers take as `rays`."""
+    cam = np.ascontiguousarray(np.asarray(cam17, np.float32).reshape(17))
+    h, w = int(cam[15]), int(cam[16])
+    dev = torch.device(device)
+    f = lambda c: torch.empty(h, w, c, device=dev)
+    o, d, v, r, nr, fr = f(3), f(3), f(3), f(1), f(1), f(1)
+    _lib.check(_lib.lib().durf_camera_rays(_stream(), (C.c_float * 17)(*cam.tolist()), 0, h * w, float(near), float(far), _p(o),
+                                           _p(d), _p(v), _p(r), _p(nr), _p(fr)), 'durf_camera_rays')
+    return utils.BoxRays(o, d, v, r, torch.ones(h, w, 1, device=dev), nr, fr)
+
+
 # ---------------------------------------------------------------------------
 # coarse-to-fine multi-resolution schedule (c2f_obb_dataset.py:306-313, 843-891; SURVEY.md 8f-4)
 # ---------------------------------------------------------------------------

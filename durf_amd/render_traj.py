@@ -1,0 +1,95 @@
+"""Render a camera trajectory of a trained scene to a directory -- the reference's `--eval_dir` ('where to render traj to',
+internal/utils.py:155) and the loop of notebooks/durf_render_traj.ipynb as a command:
+
+    python -m durf_amd.render_traj --gin_file configs/waymo.gin --data_dir DATA --train_dir CKPT --traj traj.npz --eval_dir OUT
+                                   [--cam 0] [--disable_box k ...] [--chunk 8192]
+    python -m durf_amd.render_traj --synthetic --eval_dir OUT [--frames 8] [--traj traj.npz]
+
+The checkpoint in --train_dir is restored, the intrinsics (focal, principal point, image size) are those of image --cam of the
+dataset's test split, the half extents of the boxes are one timestep's for every frame, and the cameras and times come from
+--traj (durf_amd.trajectory.load_trajectory: the notebook's npz or a plain {c2w, times} one; fractional times render the
+boxes between two labelled timesteps).  The whole trajectory is ONE
+MipNerfModel.render_trajectory call; OUT/%04d.ppm (binary P6) and OUT/distance.npy [F,h,w] are written.  --synthetic renders
+train_boxpose.SyntheticTimestepDataset's scene instead (no data directory; without --train_dir the freshly initialised
+model, without --traj a sweep between the scene's first and last camera), which exercises the command end to end."""
+import argparse
+import os
+import sys
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(prog='python -m durf_amd.render_traj', description=__doc__.split('\n\n')[0])
+    ap.add_argument('--gin_file', action='append', default=[])
+    ap.add_argument('--gin_param', action='append', default=[])
+    ap.add_argument('--train_dir', default=None, help='checkpoint directory (required unless --synthetic)')
+    ap.add_argument('--data_dir', default=None, help='dataset directory (loaders: durf_amd.datasets)')
+    ap.add_argument('--traj', default=None, help='trajectory npz: the notebook\'s (c2w, ts) pairs or {c2w, times}')
+    ap.add_argument('--eval_dir', required=True, help='where to render traj to')
+    ap.add_argument('--cam', type=int, default=0, help='index into the dataset\'s image list: the frames use that image\'s intrinsics')
+    ap.add_argument('--disable_box', type=int, action='append', default=[], help='box index to switch off (repeatable)')
+    ap.add_argument('--chunk', type=int, default=8192)
+    ap.add_argument('--synthetic', action='store_true', help='render the synthetic scene (no data directory needed)')
+    ap.add_argument('--objects', type=int, default=3, help='dynamic boxes of the synthetic scene')
+    ap.add_argument('--frames', type=int, default=8, help='--synthetic without --traj: frames of the generated sweep')
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    import numpy as np
+    import torch
+    from . import checkpoints, obbpose_model as om, train_boxpose, trajectory, utils
+    if not args.synthetic and (args.data_dir is None or args.train_dir is None or args.traj is None):
+        raise SystemExit('render_traj: --data_dir, --train_dir and --traj are required (or --synthetic)')
+    dev = torch.device('cuda', 0)
+    torch.cuda.set_device(dev)
+    utils.clear_gin()
+    config = utils.load_config(args.gin_file, args.gin_param)
+    if args.synthetic:
+        dataset = train_boxpose.SyntheticTimestepDataset(config, K=args.objects, device=dev, split='test')
+        cam_rows = dataset.ts_data[0].cams
+        ext = dataset.ext
+        key_c2w = [dataset.ts_data[0].cams[0, :12].reshape(3, 4), dataset.ts_data[-1].cams[-1, :12].reshape(3, 4)]
+        key_t = [0.0, float(dataset.T - 1)]
+    else:
+        from . import datasets
+        dataset = datasets.get_dataset('test', args.data_dir, config, device=dev)
+        cam_rows = np.concatenate([np.asarray(dataset.camtoworlds, np.float32).reshape(-1, 12),
+                                   np.stack([dataset.focal, dataset.principal_point[:, 0], dataset.principal_point[:, 1],
+                                             dataset.h, dataset.w], -1).astype(np.float32)], -1)
+        ext = dataset.peek()['ext']             # ONE set of half extents for every frame (the first test image's timestep), as the
+                                                # notebook renders with timestep 1's: the boxes move between timesteps, they do not resize
+    if not 0 <= args.cam < len(cam_rows):
+        raise SystemExit('render_traj: --cam %d of %d cameras' % (args.cam, len(cam_rows)))
+    focal, ppx, ppy, h, w = [float(x) for x in cam_rows[args.cam][12:]]
+    model, variables = om.construct_mipnerf(20200823, dataset.peek(), device=dev)
+    state = train_boxpose.create_train_state(variables)
+    if args.train_dir is not None:
+        state = checkpoints.restore_checkpoint(args.train_dir, state)
+    variables = state.variables
+    alpha = train_boxpose.make_schedules(config)[2](max(int(state.step), 1))
+    if args.traj is not None:
+        c2w, times = trajectory.load_trajectory(args.traj)
+    else:
+        c2w, times = trajectory.make_trajectory(key_c2w, key_t, args.frames)
+    K = variables.layout.K
+    enable = None
+    if args.disable_box:
+        bad = [k for k in args.disable_box if not 0 <= k < K]
+        if bad:
+            raise SystemExit('render_traj: --disable_box %s of K = %d boxes' % (bad, K))
+        enable = [0 if k in args.disable_box else 1 for k in range(K)]
+    cams = trajectory.camera_rows(c2w, focal, (ppx, ppy), int(h), int(w))
+    out = model.render_trajectory(variables, cams, times, ext, config.white_bkgd, alpha, near=config.near, far=config.far,
+                                  chunk=args.chunk, box_enable=enable, outputs=('rgb8', 'distance'))
+    os.makedirs(args.eval_dir, exist_ok=True)
+    rgb8 = out['rgb8'].cpu().numpy()
+    for f in range(rgb8.shape[0]):
+        trajectory.write_ppm(os.path.join(args.eval_dir, '%04d.ppm' % f), rgb8[f])
+    np.save(os.path.join(args.eval_dir, 'distance.npy'), out['distance'].cpu().numpy())
+    print('render_traj: %d frames of %d x %d written to %s' % (rgb8.shape[0], int(h), int(w), args.eval_dir))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

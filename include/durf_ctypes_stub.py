@@ -161,6 +161,15 @@ def bind(path='durf_amd/libdurf_hip.so'):
     L.durf_render_layers.restype = i32
     L.durf_render_layers.argtypes = [vp, vp, vp, u64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64]
     #   (stream, args, box_enable, n_rays, chunk, rgb, distance, acc, instance, bg_rgb, bg_distance, bg_acc, obj_rgba, workspace, workspace_bytes)
+    L.durf_camera_rays.restype = i32
+    L.durf_camera_rays.argtypes = [vp, C.POINTER(f32), i32, i32, f32, f32, vp, vp, vp, vp, vp, vp]
+    #   (stream, cams_host, first, count, near, far, origins, directions, viewdirs, radii, near_out, far_out)
+    L.durf_render_trajectory_workspace_bytes.restype = u64
+    L.durf_render_trajectory_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+    #   (F, chunk, N, K, num_levels)
+    L.durf_render_trajectory.restype = i32
+    L.durf_render_trajectory.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(f32), C.POINTER(f32), f32, f32, i32, vp, vp, vp, vp, vp, vp, u64]
+    #   (stream, args, box_enable, box_centers, T, F, cams_host, times_host, near, far, chunk, rgb8, rgb, distance, acc, poses_out, workspace, workspace_bytes)
     L.durf_train_workspace_bytes.restype = u64
     L.durf_train_workspace_bytes.argtypes = [i32, i32, i32, i32, u64]
     #   (B, N, K, num_levels, n_params)

@@ -71,6 +71,9 @@ int durf_version(void);
 #define DURF_LAYERLOG_SELECT 0x100000       /* durf_render_layers: instance map / image-wide compaction of the box-hit rays */
 #define DURF_LAYERLOG_PASS2 0x200000        /* durf_render_layers: gather / scatter around the second (K = 0) pass */
 #define DURF_LAYERLOG_BOX_MASK 0x400000     /* the box test ran with a device-side box_enable */
+#define DURF_LAYERLOG_TRAJ_RAYS 0x800000    /* k_camera_rays: a chunk's rays generated from a camera row (durf_render_trajectory) */
+#define DURF_LAYERLOG_TRAJ_POSE 0x1000000   /* k_pose_interp: box poses between the labelled timesteps */
+#define DURF_LAYERLOG_TRAJ_PACK 0x2000000   /* k_frame_pack: the 8-bit epilogue (absent when rgb8 is NULL) */
 int durf_dispatch_seen(void);
 int durf_dispatch_reset(void);
 
@@ -492,6 +495,41 @@ int durf_render_layers(void* stream, const durf_forward_args* args, const int32_
                        int chunk, float* rgb, float* distance, float* acc, int32_t* instance /* nullable */,
                        float* bg_rgb /* nullable */, float* bg_distance /* nullable */, float* bg_acc /* nullable */,
                        float* obj_rgba /* nullable */, void* workspace, size_t workspace_bytes);
+
+/* ---- a camera trajectory in one call (csrc/forward.hip; kernels: csrc/trajectory.hip) --------------------------------
+ * The loop of the reference's notebooks/durf_render_traj.ipynb -- a list of (c2w, ts) pairs, rays built on the host and
+ * render_image frame by frame -- with cameras and times in and frames out.
+ *
+ * durf_camera_rays: the six ray fields of pixels [first, first + count) of ONE camera row (17 host floats in
+ * durf_gen_batch's layout: c2w [3,4] row-major, focal, principal point x / y, height, width), through the device function
+ * durf_gen_batch's pinhole path runs: bit-identical to what durf_gen_batch writes for ray_idx = NULL on a one-camera
+ * timestep.  origins / directions / viewdirs [count,3], radii / near_out / far_out [count]. */
+int durf_camera_rays(void* stream, const float* cams_host /* 17 */, int first, int count, float near, float far,
+                     float* origins, float* directions, float* viewdirs, float* radii, float* near_out, float* far_out);
+/* durf_render_trajectory: F frames; frame f is seen from camera row f of cams_host [F,17] (all of one height h and width w;
+ * n = h * w) at time times_host[f] in [0, T - 1].  `args` as for durf_render_image with the ray fields AND args->pose ignored:
+ * the frame's rays are generated chunk by chunk into the workspace (no image-sized ray buffer exists), and its box poses are
+ * interpolated on the device from box_centers [T,K,6] -- a DEVICE pointer, the head of the flat parameter buffer, so a
+ * trajectory can follow a training step with no host copy.  For t = i + w (i = floor t): position p_i + w (p_{i+1} - p_i),
+ * each of the three angles a_i + w wrap(a_{i+1} - a_i) with wrap onto [-pi, pi) (the shorter arc); w == 0 copies row i
+ * verbatim and reads no other row.  Every frame then runs durf_render_layers' composite path (durf_forward's launch
+ * sequence per chunk under box_enable, nullable, and the frame's pose; no layer, no second pass, no read-back): float
+ * outputs are bit-identical to durf_render_layers on durf_camera_rays' rays with args->pose = poses_out[f].
+ * Outputs, each NULLABLE and not written when NULL (at least one is required):
+ *   rgb8 [F,n,3] uint8          (uint8) rintf(clamp(rgb, 0, 1) * 255), NaN -> 0: a chunk epilogue launched only when asked for;
+ *   rgb [F,n,3], distance [F,n], acc [F,n]   the last level's planes;
+ *   poses_out [F,K,6]           the poses rendered with.  With poses_out alone the call interpolates and renders nothing
+ *                               (cams_host may then be NULL).
+ * The call only enqueues work: no stream synchronisation, no device-to-host copy (the frame times travel as kernel
+ * arguments: one pose launch per 512 frames).  Refused (-1, durf_last_error): F <= 0, no output, a time outside [0, T - 1], frames of different sizes, a
+ * workspace smaller than durf_render_trajectory_workspace_bytes(F, chunk, N, K, num_levels) -- which does not grow with the
+ * image and grows with F by the poses only (F * K * 24 bytes) -- checked before the first launch, both sizes named. */
+size_t durf_render_trajectory_workspace_bytes(int F, int chunk, int N, int K, int num_levels);
+int durf_render_trajectory(void* stream, const durf_forward_args* args, const int32_t* box_enable /* nullable */,
+                           const float* box_centers /* device [T,K,6] */, int T, int F, const float* cams_host /* F x 17 */,
+                           const float* times_host /* F */, float near, float far, int chunk, uint8_t* rgb8 /* nullable */,
+                           float* rgb /* nullable */, float* distance /* nullable */, float* acc /* nullable */,
+                           float* poses_out /* nullable */, void* workspace, size_t workspace_bytes);
 
 /* ---- one shard's training step as ONE call (csrc/train.hip) ------------------------------------------------
  * durf_loss_backward: value_and_grad(loss_fn) of train_step (train_boxpose.py:67-252) -- the forward with activations

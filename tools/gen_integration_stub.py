@@ -27,7 +27,7 @@ def ctype_of(param):
     base = t.replace('*', '').strip()
     if stars == 0:
         return SCALARS[base], name
-    if stars == 1 and base == 'float' and name in ('barf_w', 'mults', 'cams_host'):
+    if stars == 1 and base == 'float' and name in ('barf_w', 'mults', 'cams_host', 'times_host'):
         return 'C.POINTER(f32)', name          # HOST float arrays (documented as such in the header)
     if stars == 1 and base == 'size_t':
         return 'C.POINTER(u64)', name          # HOST array (per-segment row capacities)
