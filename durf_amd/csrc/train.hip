@@ -2,7 +2,9 @@
 // C call -- the orchestration durf_amd/train_boxpose.py (loss_and_grad, train_step) and obbpose_model.py (_forward, train)
 // do in Python, for hosts that are not Python (durf_forward / durf_loss_backward / durf_clip_adam).  No kernel
 // of its own: the stage entry points of this library in the order the Python path issues them on ONE stream, every
-// intermediate carved out of a caller-owned workspace.  Scope: every BASELINE.json training configuration -- bf16 background
+// intermediate carved out of a caller-owned workspace (workspace.h: the carver and the ray-head buffers shared with
+// forward.hip; TailIn: what the step's tail launches read, built once per call).
+// Scope: every BASELINE.json training configuration -- bf16 background
 // MLP; object MLPs on the bf16 kernels (frozen poses: cfg2 / cfg3 / cfg5) or, with obj_fp32, on the exact-fp32 kernels with
 // the box-pose gradient behind them (cfg4: want_pos / want_rot, the TV prior); >= 2 levels; density noise (f.density_noise),
 // weight decay (weight_decay_mult) and every background mode included.  Results are bit-identical to
@@ -10,22 +12,9 @@
 #include "durf_common.h"
 #include "../../include/durf_hip.h"
 #include "side_stream.h"
+#include "workspace.h"
 
 namespace {
-
-struct Carver {
-    char* base;
-    size_t off;
-    void* take(size_t bytes) {
-        // (large buffers start on 2 MB boundaries, as the host allocator's own blocks do: the forward ran 2-3 % slower on
-        // streams that started at arbitrary 256-byte offsets of one big block)
-        const size_t al = bytes >= ((size_t)1 << 20) ? ((size_t)2 << 20) : (size_t)256;
-        off = (off + al - 1) & ~(al - 1);
-        void* p = base ? base + off : nullptr;
-        off += bytes;
-        return p;
-    }
-};
 
 constexpr int ML = DURF_FORWARD_MAX_LEVELS;
 constexpr int OBJ32_NSPLIT = 8;        // ops.objf32_dw_batch's default: same split-K partial order as the Python path
@@ -40,12 +29,11 @@ __global__ void k_tv_rows(int K, const float* __restrict__ pose, const float* __
     g[k * 6 + q] = g[k * 6 + q] + t2;
 }
 
-struct TrainWs {
-    float *o_s, *d_s, *norms, *prep, *ray_sums, *sums, *part, *bpart, *opart, *obpart, *scratch, *u_rand, *weight_l2;
+struct TrainWs : durf::RayHeadWs {
+    float *norms, *prep, *ray_sums, *sums, *part, *bpart, *opart, *obpart, *scratch, *u_rand, *weight_l2;
     float* draw[ML];      // d(loss)/d(raw) of every level (ONE loss launch fills them all: durf_loss_bwd_levels)
     float *raw_c[ML], *raw_b[ML], *obj_raw[ML], *terms[ML];
-    int32_t *hit, *idx_obj, *count_obj, *slot_obj, *idx_cls, *count_cls, *slot_cls;
-    void *view, *wf_bkgd, *wb_bkgd, *wf_obj, *wb_obj, *view_tile, *obj_view_tile;
+    void *wf_bkgd, *wb_bkgd, *wf_obj, *wb_obj, *view_tile, *obj_view_tile;
     void *enc[ML], *stash[ML], *mask[ML], *dz[ML], *dz_out[ML];
     void *obj_enc[ML], *obj_stash[ML], *obj_mask[ML], *obj_dz[ML], *obj_dz_out[ML];
     // object branch on the exact-fp32 kernels (obj_fp32): view features, the background's fp32 evaluation of the box-hit
@@ -57,19 +45,12 @@ struct TrainWs {
 
 TrainWs carve(void* workspace, int B, int N, int K, int L, size_t n_params, int flags = 0) {
     const bool f32o = K > 0 && (flags & DURF_TRAIN_OBJ_FP32) != 0, pose = f32o && (flags & DURF_TRAIN_POSE_OPT) != 0;
-    Carver c{(char*)workspace, 0};
+    // (large buffers start on 2 MB boundaries, as the host allocator's own blocks do: the forward ran 2-3 % slower on
+    // streams that started at arbitrary 256-byte offsets of one big block)
+    durf::Carver c{(char*)workspace, 0, true};
     TrainWs w{};
     const size_t rows = (size_t)B * N, Kc = K > 0 ? K : 1, trows = (rows + 31) / 32 * 32;
-    w.o_s = (float*)c.take((size_t)B * 3 * 4);
-    w.d_s = (float*)c.take((size_t)B * 3 * 4);
-    w.hit = (int32_t*)c.take((size_t)B * Kc * 4);
-    w.view = c.take((size_t)B * 32 * 2);
-    w.idx_obj = (int32_t*)c.take(Kc * B * 4);
-    w.count_obj = (int32_t*)c.take(Kc * 4);
-    w.slot_obj = (int32_t*)c.take((size_t)B * Kc * 4);
-    w.idx_cls = (int32_t*)c.take((size_t)2 * B * 4);
-    w.count_cls = (int32_t*)c.take(8 * 4);
-    w.slot_cls = (int32_t*)c.take((size_t)2 * B * 4);
+    durf::carve_ray_head(c, w, B, K);
     w.wf_bkgd = c.take(durf_wpack_fwd_bytes(256));
     w.wb_bkgd = c.take(durf_wpack_bwd_bytes(256));
     w.wf_obj = c.take(Kc * durf_wpack_fwd_bytes(128));
@@ -120,7 +101,7 @@ TrainWs carve(void* workspace, int B, int N, int K, int L, size_t n_params, int 
         w.pose_sums = (float*)c.take((size_t)K * 21 * 4);
         w.pose_scratch = (float*)c.take(pose ? (size_t)L * K * 21 * B * 4 : 0);      // (every level's rows: one launch pair)
     }
-    w.total = (c.off + 255) & ~(size_t)255;
+    w.total = c.total();
     return w;
 }
 
@@ -133,10 +114,8 @@ TrainWs workspace_of(const durf_train_args* a, void* workspace) {
 
 // a workspace the caller sized for another shape is refused, not overrun (the intermediates of a step are up to ~10 GB)
 int check_workspace(const char* who, const durf_train_args* a, const TrainWs& w, size_t workspace_bytes) {
-    if (workspace_bytes >= w.total) return 0;
-    durf_set_error("%s: workspace of %zu bytes, durf_train_workspace_bytes_flags(%d, %d, %d, %d, %zu, %d) = %zu", who, workspace_bytes,
-                   a->f.B, a->f.N, a->f.K, a->f.num_levels, a->n_params, a->flags, w.total);
-    return -1;
+    return durf::check_workspace(who, workspace_bytes, w.total, "durf_train_workspace_bytes_flags(%d, %d, %d, %d, %zu, %d)", a->f.B,
+                                 a->f.N, a->f.K, a->f.num_levels, a->n_params, a->flags);
 }
 
 int check_args(const durf_train_args* a, void* workspace) {
@@ -185,9 +164,22 @@ __global__ void k_scale(int n, float* __restrict__ x, float c) {
     if (i < n) x[i] *= c;
 }
 
+// what the launches of the step's tail (durf_train_stats / durf_stats_scrub) read besides the gradient: once per call
+struct TailIn {
+    const float *tv[ML], *terms[ML];
+    const float *wl2, *pose, *prev6, *target6;
+    TailIn(const durf_train_args* a, const TrainWs& w) {
+        const bool K = a->f.K != 0;
+        for (int l = 0; l < a->f.num_levels; l++) { tv[l] = a->f.t_vals[l]; terms[l] = w.terms[l]; }
+        wl2 = a->weight_decay_mult != 0.0f ? w.weight_l2 : nullptr;        // (written by durf_weight_decay, loss_backward)
+        pose = K ? a->f.pose : nullptr; prev6 = K ? a->prev6 : nullptr; target6 = K ? a->target6 : nullptr;
+    }
+};
+
 // tail: the multi-hit outcome and the logged scalars as launches of their own (durf_loss_backward: the caller gets the
-// un-post-processed gradient); durf_train_step folds both into the optimizer's first launch (durf_stats_scrub)
-int loss_backward(void* stream, const durf_train_args* a, const TrainWs& w, bool tail = true) {
+// un-post-processed gradient); null: durf_train_step folds both into the optimizer's first launch (durf_stats_scrub).
+// (The forward part shares nothing with forward.hip's forward_launches on purpose: a common routine would be all flags.)
+int loss_backward(void* stream, const durf_train_args* a, const TrainWs& w, const TailIn* tail) {
     const durf_forward_args& f = a->f;
     const int B = f.B, N = f.N, K = f.K, L = f.num_levels;
     const size_t rows = (size_t)B * N;
@@ -381,11 +373,8 @@ int loss_backward(void* stream, const durf_train_args* a, const TrainWs& w, bool
                               Km ? N : 0, Km ? w.count_obj : nullptr, Km ? L : 1, 63, Km ? w.opart : nullptr, Km ? w.obpart : nullptr,
                               Km ? g_obj : nullptr, Km ? a->obj_floats : 0, Km ? f.obj_params : nullptr));
     STEP(ov.join());
-    const float* wl2 = nullptr;
-    if (a->weight_decay_mult != 0.0f) {       // train_boxpose.py:73-75 (in front of the pose rows' additions, as the Python path orders it)
+    if (a->weight_decay_mult != 0.0f)         // train_boxpose.py:73-75 (in front of the pose rows' additions, as the Python path orders it)
         STEP(durf_weight_decay(stream, a->n_params, a->params, a->grad, 0, a->n_params, a->weight_decay_mult, w.scratch, w.weight_l2));
-        wl2 = w.weight_l2;
-    }
     if (pose_opt) {             // d(loss)/d(box_centers[ts]) (obbpose_model.py:99-131) + the TV prior, into this timestep's rows
         float* g_rows = a->grad + (f.pose - a->params);
         STEP(durf_pose_finish(stream, K, f.pose, w.pose_sums, a->want_pos, a->want_rot, g_rows));
@@ -399,12 +388,8 @@ int loss_backward(void* stream, const durf_train_args* a, const TrainWs& w, bool
     if (K > 1)                  // rays that hit two boxes: the reference's NaN -> zero update (durf_poison_multi_hit)
         STEP(durf_poison_multi_hit(stream, a->n_params, a->grad, w.count_cls, a->box_floats, K, a->mlp0_floats, a->obj_floats));
     // ---- the logged scalars (utils.Stats), one launch ----
-    const float* tv[ML];
-    const float* terms[ML];
-    for (int l = 0; l < L; l++) { tv[l] = f.t_vals[l]; terms[l] = w.terms[l]; }
-    STEP(durf_train_stats(stream, L, K, N, w.norms, w.sums, wl2, K ? f.pose : nullptr, K ? a->prev6 : nullptr,
-                          K ? a->target6 : nullptr, tv, a->stat_mults, 3 /* assemble | psnr */, a->stats, terms, B));
-    return 0;
+    return durf_train_stats(stream, L, K, N, w.norms, w.sums, tail->wl2, tail->pose, tail->prev6, tail->target6, tail->tv, a->stat_mults,
+                            3 /* assemble | psnr */, a->stats, tail->terms, B);
 }
 
 }  // namespace
@@ -423,7 +408,8 @@ int durf_loss_backward(void* stream, const durf_train_args* a, void* workspace, 
     if (rc != 0) return rc;
     const TrainWs w = workspace_of(a, workspace);
     STEP(check_workspace("durf_loss_backward", a, w, workspace_bytes));
-    return loss_backward(stream, a, w);
+    const TailIn t(a, w);
+    return loss_backward(stream, a, w, &t);
 }
 
 static int train_step_body(void* stream, const durf_train_args* a, void* workspace, size_t workspace_bytes);
@@ -450,53 +436,43 @@ static int train_step_body(void* stream, const durf_train_args* a, void* workspa
     DURF_REQUIRE(a->adam_m && a->adam_v && a->grad_stats, "Adam moments and grad_stats");
     const TrainWs w = workspace_of(a, workspace);
     STEP(check_workspace("durf_train_step", a, w, workspace_bytes));
-    STEP(loss_backward(stream, a, w, false));
+    STEP(loss_backward(stream, a, w, nullptr));
     STEP(durf::join_prefetch(stream));       // (a step without the fp32 object branch behind one with it: nothing has joined yet)
+    const durf_forward_args& f = a->f;
+    const int K = f.K, L = f.num_levels;
+    const TailIn t(a, w);
     if (a->comm != nullptr) {
         // One rank's share of a data-parallel step (train_boxpose.py:253-255; durf_amd/train_boxpose.py train_step): the
         // multi-hit NaNs have to exist BEFORE the exchange (the reference's pmean sees them), then ONE all-reduce of the flat
         // gradient in this stream, and the optimizer on the mean.
         DURF_REQUIRE(a->world >= 1, "world: the ranks of comm");
-        const durf_forward_args& f = a->f;
-        const int K = f.K, L = f.num_levels;
         const float inv_world = 1.0f / (float)a->world;
-        const float* tv[ML];
-        const float* terms[ML];
-        for (int l = 0; l < L; l++) { tv[l] = f.t_vals[l]; terms[l] = w.terms[l]; }
-        const float* wl2 = a->weight_decay_mult != 0.0f ? w.weight_l2 : nullptr;
         if (K > 1)
             STEP(durf_poison_multi_hit(stream, a->n_params, a->grad, w.count_cls, a->box_floats, K, a->mlp0_floats, a->obj_floats));
         STEP(durf_allreduce_sum(stream, a->comm, a->grad, a->n_params));
         if (!a->reduce_stats) {          // shard-local scalars (the reference reads them every print_every steps only)
-            STEP(durf_stats_scrub(stream, L, K, f.N, w.norms, w.sums, wl2, K ? f.pose : nullptr, K ? a->prev6 : nullptr,
-                                  K ? a->target6 : nullptr, tv, a->stat_mults, 3, a->stats, terms, f.B, a->n_params, a->grad,
-                                  inv_world, a->max_val, w.scratch, nullptr, 0, 0, 0, 0));
+            STEP(durf_stats_scrub(stream, L, K, f.N, w.norms, w.sums, t.wl2, t.pose, t.prev6, t.target6, t.tv, a->stat_mults, 3, a->stats,
+                                  t.terms, f.B, a->n_params, a->grad, inv_world, a->max_val, w.scratch, nullptr, 0, 0, 0, 0));
             return durf_adam_apply(stream, a->n_params, a->params, a->adam_m, a->adam_v, a->grad, a->max_norm, a->lr, a->step,
                                    w.scratch, a->grad_stats);
         }
         // lax.pmean(stats) (:255), then the PSNRs from the averaged losses (:291-292)
         const int ns = 2 + 17 * L;
-        STEP(durf_train_stats(stream, L, K, f.N, w.norms, w.sums, wl2, K ? f.pose : nullptr, K ? a->prev6 : nullptr,
-                              K ? a->target6 : nullptr, tv, a->stat_mults, 1, a->stats, terms, f.B));
+        STEP(durf_train_stats(stream, L, K, f.N, w.norms, w.sums, t.wl2, t.pose, t.prev6, t.target6, t.tv, a->stat_mults, 1, a->stats,
+                              t.terms, f.B));
         STEP(durf_allreduce_sum(stream, a->comm, a->stats, (size_t)ns));
         hipLaunchKernelGGL(k_scale, dim3(1), dim3(256), 0, (hipStream_t)stream, ns, a->stats, inv_world);
         DURF_CHECK_LAUNCH("durf_train_step (pmean of the logged scalars)");
-        STEP(durf_train_stats(stream, L, K, f.N, w.norms, w.sums, nullptr, nullptr, nullptr, nullptr, tv, a->stat_mults, 2, a->stats,
+        STEP(durf_train_stats(stream, L, K, f.N, w.norms, w.sums, nullptr, nullptr, nullptr, nullptr, t.tv, a->stat_mults, 2, a->stats,
                               nullptr, 0));
         return durf_clip_adam(stream, a->n_params, a->params, a->adam_m, a->adam_v, a->grad, inv_world, a->max_val, a->max_norm,
                               a->lr, a->step, w.scratch, a->grad_stats);
     }
     // the step's tail in two launches (as durf_amd/train_boxpose.py issues it on one device): the logged scalars + the
     // multi-hit outcome + the optimizer's scrub pass, then Adam
-    const durf_forward_args& f = a->f;
-    const int K = f.K, L = f.num_levels;
-    const float* tv[ML];
-    const float* terms[ML];
-    for (int l = 0; l < L; l++) { tv[l] = f.t_vals[l]; terms[l] = w.terms[l]; }
-    STEP(durf_stats_scrub(stream, L, K, f.N, w.norms, w.sums, a->weight_decay_mult != 0.0f ? w.weight_l2 : nullptr, K ? f.pose : nullptr, K ? a->prev6 : nullptr,
-                          K ? a->target6 : nullptr, tv, a->stat_mults, 3 /* assemble | psnr */, a->stats, terms, f.B, a->n_params,
-                          a->grad, 1.0f, a->max_val, w.scratch, K > 1 ? w.count_cls : nullptr, a->box_floats, K > 1 ? K : 0,
-                          a->mlp0_floats, a->obj_floats));
+    STEP(durf_stats_scrub(stream, L, K, f.N, w.norms, w.sums, t.wl2, t.pose, t.prev6, t.target6, t.tv, a->stat_mults,
+                          3 /* assemble | psnr */, a->stats, t.terms, f.B, a->n_params, a->grad, 1.0f, a->max_val, w.scratch,
+                          K > 1 ? w.count_cls : nullptr, a->box_floats, K > 1 ? K : 0, a->mlp0_floats, a->obj_floats));
     return durf_adam_apply(stream, a->n_params, a->params, a->adam_m, a->adam_v, a->grad, a->max_norm, a->lr, a->step, w.scratch,
                            a->grad_stats);
 }

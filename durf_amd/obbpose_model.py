@@ -557,48 +557,66 @@ class MipNerfModel:
         return (self.mlp_precision == 'bf16' and not (K and (not self.dynamics or self.object_precision() != 'bf16')) and
                 variables.flat.device.type == 'cuda')
 
-    def apply_one_call(self, variables, rng, rays, init, ext, ts, randomized, rand_bkgd, white_bkgd, alpha, noise=None, *,
-                       box_enable=None, pose=None):
-        """`apply` through ONE library call (durf_forward, csrc/forward.hip): the orchestration of `_forward(train=False)`
-        done in C for hosts that are not Python; same arguments, same list of 10-tuples, bit-identical results
-        (tests/test_gpu_forward_call.py).  bf16 MLPs, objects on the bf16 kernels.  noise: dict(t_rand, u_rand[, density:
-        the standard-normal draws [B,N] per level]) injected draws; otherwise `rng` keys the library's own (an int) or is the
-        torch.Generator they come from.
-        box_enable (K values 0 / 1) / pose ([K,6] in place of box_centers[ts]): as in apply() -- durf_forward_masked."""
+    def enc_flags(self):
+        """the ENC_* bits of this model's encodings (include/durf_hip.h DURF_ENC_*)"""
+        return ((ops.ENC_CONTRACT if self.contraction else 0) | (ops.ENC_NO_INTEGRATION if self.disable_integration else 0) |
+                (ops.ENC_CYLINDER if self.ray_shape == 'cylinder' else 0))
+
+    @staticmethod
+    def bkgd_mode(rand_bkgd, white_bkgd):
+        return ops.BKGD_RAND if rand_bkgd else (ops.BKGD_WHITE if white_bkgd else ops.BKGD_GREY)
+
+    def _one_call_args(self, entry, variables, ext, alpha, white_bkgd, rand_bkgd=False):
+        """what every inference binding of ops (forward_call, render_*_call, render_trajectory) takes from the model ->
+        (the variables the kernels evaluate; the positional block ext, bkgd_params, obj_params, obj_param_stride, N, num_levels,
+        alpha, enc_flags; the keywords lindisp, bkgd_mode, density_bias, resample_padding).  Refuses in `entry`'s name what
+        supports_one_call does not cover."""
         self._check()
         variables = self._kernel_variables(variables)
+        if not self.supports_one_call(variables):
+            raise NotImplementedError('%s covers the bf16 inference path (dynamics=True, bf16 object MLPs)' % entry)
         lay = variables.layout
-        K = lay.K
-        if not self.supports_one_call(variables, randomized):
-            raise NotImplementedError('durf_forward covers the bf16 inference path (dynamics=True, bf16 object MLPs)')
-        B, N = rays.origins.shape[0], self.num_samples
-        dev = rays.origins.device
-        seed = None
+        K, stride = lay.K, lay.mlp_size[W_OBJ]
+        o0 = lay.mlp_off['BoxMLP_0'] if K else 0
+        args = (ext.reshape(-1, 3).contiguous() if (K and ext is not None) else None, variables.mlp_flat('MLP_0'),
+                variables.flat[o0:o0 + K * stride] if K else None, stride, self.num_samples, self.num_levels, alpha, self.enc_flags())
+        return variables, args, dict(lindisp=self.lindisp, bkgd_mode=self.bkgd_mode(rand_bkgd, white_bkgd),
+                                     density_bias=self.density_bias, resample_padding=self.resample_padding)
+
+    def _step_draws(self, rng, randomized, noise, B, dev):
+        """where the draws of a one-call step come from -> the keywords t_rand, u_rand, seed, density_noise, density_rand of
+        ops.forward_call / ops.train_call.  noise: dict(t_rand, u_rand[, density: the standard-normal draws [B,N] per level])
+        injected draws; otherwise `rng` is the torch.Generator they are taken from here, or (an int) keys the library's own
+        (durf_forward_args.draw_noise), as in apply() and train_step."""
+        N, L, seed = self.num_samples, self.num_levels, None
         if randomized and noise is None:
             if isinstance(rng, torch.Generator):
                 u = torch.rand(2, B, N + 1, device=dev, generator=rng)
                 noise = dict(t_rand=u[0], u_rand=u[1])
                 if self.density_noise > 0:          # (level by level, as apply() draws them)
-                    noise['density'] = [torch.randn(B, N, device=dev, generator=rng) for _ in range(self.num_levels)]
-            else:                                   # the library draws (durf_forward_args.draw_noise), as in apply()
+                    noise['density'] = [torch.randn(B, N, device=dev, generator=rng) for _ in range(L)]
+            else:
                 seed = int(rng) if rng is not None else 0
                 noise = dict(t_rand=None, u_rand=None)
         dn = self.density_noise if (randomized and self.density_noise > 0) else 0.0
         if dn and seed is None and 'density' not in noise:      # injected sampling draws only: the generator apply() falls back to
             gd = _make_generator(rng, dev)
-            noise = dict(noise, density=[torch.randn(B, N, device=dev, generator=gd) for _ in range(self.num_levels)])
+            noise = dict(noise, density=[torch.randn(B, N, device=dev, generator=gd) for _ in range(L)])
+        return dict(t_rand=noise['t_rand'] if randomized else None, u_rand=noise['u_rand'] if randomized else None, seed=seed,
+                    density_noise=dn, density_rand=noise.get('density') if dn else None)
+
+    def apply_one_call(self, variables, rng, rays, init, ext, ts, randomized, rand_bkgd, white_bkgd, alpha, noise=None, *,
+                       box_enable=None, pose=None):
+        """`apply` through ONE library call (durf_forward, csrc/forward.hip): the orchestration of `_forward(train=False)`
+        done in C for hosts that are not Python; same arguments, same list of 10-tuples, bit-identical results
+        (tests/test_gpu_forward_call.py).  bf16 MLPs, objects on the bf16 kernels.  noise / rng: _step_draws.
+        box_enable (K values 0 / 1) / pose ([K,6] in place of box_centers[ts]): as in apply() -- durf_forward_masked."""
+        variables, args, kw = self._one_call_args('durf_forward', variables, ext, alpha, white_bkgd, rand_bkgd)
+        dev = rays.origins.device
+        draws = self._step_draws(rng, randomized, noise, rays.origins.shape[0], dev)
         pose, box_enable = self._scene_edit(variables, ts, pose, box_enable)
-        flags = ((ops.ENC_CONTRACT if self.contraction else 0) | (ops.ENC_NO_INTEGRATION if self.disable_integration else 0) |
-                 (ops.ENC_CYLINDER if self.ray_shape == 'cylinder' else 0))
-        o0 = lay.mlp_off['BoxMLP_0'] if K else 0
-        bk = ops.BKGD_RAND if rand_bkgd else (ops.BKGD_WHITE if white_bkgd else ops.BKGD_GREY)
-        outs, dyn, zo = ops.forward_call(
-            rays, pose, ext.reshape(-1, 3).contiguous() if K else None, variables.mlp_flat('MLP_0'),
-            variables.flat[o0:o0 + K * lay.mlp_size[W_OBJ]] if K else None, lay.mlp_size[W_OBJ], N, self.num_levels, alpha, flags,
-            lindisp=self.lindisp, bkgd_mode=bk, density_bias=self.density_bias, resample_padding=self.resample_padding,
-            t_rand=noise['t_rand'] if randomized else None, u_rand=noise['u_rand'] if randomized else None, seed=seed,
-            density_noise=dn, density_rand=noise.get('density') if dn else None, box_enable=box_enable)
-        box_rot0 = pose[0, 3:] if K > 0 else ops.const_tensor(dev, (3,))
+        outs, dyn, zo = ops.forward_call(rays, pose, *args, box_enable=box_enable, **kw, **draws)
+        box_rot0 = pose[0, 3:] if variables.layout.K > 0 else ops.const_tensor(dev, (3,))
         return [tuple(o) + ([pose[:, :3], box_rot0], dyn, zo) for o in outs]
 
     def render_image_one_call(self, variables, rays, init, ext, ts, white_bkgd, alpha, chunk=8192):
@@ -606,23 +624,11 @@ class MipNerfModel:
         chunk loop runs in C over the image's rays where they are -- no per-chunk slicing, output allocation or argument
         marshalling in the interpreter.  rays: [H, W, .] fields -> (rgb [H,W,3], distance [H,W], acc [H,W]), bit-identical to
         render_image over apply_one_call chunks.  Same scope as apply_one_call (supports_one_call)."""
-        self._check()
-        variables = self._kernel_variables(variables)
-        lay = variables.layout
-        K = lay.K
-        if not self.supports_one_call(variables):
-            raise NotImplementedError('durf_render_image covers the bf16 inference path (dynamics=True, bf16 object MLPs)')
+        variables, args, kw = self._one_call_args('durf_render_image', variables, ext, alpha, white_bkgd)
         height, width = rays[0].shape[:2]
         flat = utils.namedtuple_map(lambda r: r.reshape(height * width, -1), rays)
         pose = variables['params']['box_centers'][int(ts)].contiguous()
-        flags = ((ops.ENC_CONTRACT if self.contraction else 0) | (ops.ENC_NO_INTEGRATION if self.disable_integration else 0) |
-                 (ops.ENC_CYLINDER if self.ray_shape == 'cylinder' else 0))
-        o0 = lay.mlp_off['BoxMLP_0'] if K else 0
-        rgb, dist_, acc = ops.render_image_call(
-            flat, pose, ext.reshape(-1, 3).contiguous() if K else None, variables.mlp_flat('MLP_0'),
-            variables.flat[o0:o0 + K * lay.mlp_size[W_OBJ]] if K else None, lay.mlp_size[W_OBJ], self.num_samples, self.num_levels,
-            alpha, flags, chunk, lindisp=self.lindisp, bkgd_mode=ops.BKGD_WHITE if white_bkgd else ops.BKGD_GREY,
-            density_bias=self.density_bias, resample_padding=self.resample_padding)
+        rgb, dist_, acc = ops.render_image_call(flat, pose, *args, chunk, **kw)
         return rgb.reshape(height, width, 3), dist_.reshape(height, width), acc.reshape(height, width)
 
     def render_layers(self, variables, rays, init, ext, ts, white_bkgd, alpha, chunk=8192, box_enable=None, pose=None,
@@ -638,41 +644,19 @@ class MipNerfModel:
         if unknown:
             raise ValueError('unknown layers %s: choose from %s' % (unknown, list(ops.LAYER_NAMES)))
         self._check()
-        variables = self._kernel_variables(variables)
-        lay = variables.layout
-        K = lay.K
-        pose, box_enable = self._scene_edit(variables, ts, pose, box_enable)
-        if not self.supports_one_call(variables):
-            raise NotImplementedError('durf_render_layers covers the bf16 inference path (dynamics=True, bf16 object MLPs)')
+        pose, box_enable = self._scene_edit(self._kernel_variables(variables), ts, pose, box_enable)
+        variables, args, kw = self._one_call_args('durf_render_layers', variables, ext, alpha, white_bkgd)
         height, width = rays[0].shape[:2]
         flat = utils.namedtuple_map(lambda r: r.reshape(height * width, -1), rays)
-        flags = ((ops.ENC_CONTRACT if self.contraction else 0) | (ops.ENC_NO_INTEGRATION if self.disable_integration else 0) |
-                 (ops.ENC_CYLINDER if self.ray_shape == 'cylinder' else 0))
-        o0 = lay.mlp_off['BoxMLP_0'] if K else 0
-        out = ops.render_layers_call(
-            flat, pose, ext.reshape(-1, 3).contiguous() if K else None, variables.mlp_flat('MLP_0'),
-            variables.flat[o0:o0 + K * lay.mlp_size[W_OBJ]] if K else None, lay.mlp_size[W_OBJ], self.num_samples, self.num_levels,
-            alpha, flags, chunk, lindisp=self.lindisp, bkgd_mode=ops.BKGD_WHITE if white_bkgd else ops.BKGD_GREY,
-            density_bias=self.density_bias, resample_padding=self.resample_padding, box_enable=box_enable, layers=layers)
+        out = ops.render_layers_call(flat, pose, *args, chunk, box_enable=box_enable, layers=layers, **kw)
         return {k: v.reshape((height, width) + tuple(v.shape[1:])) for k, v in out.items()}
 
     def _trajectory_call(self, variables, cams, times, ext, white_bkgd, alpha, near, far, chunk, box_enable, outputs, out=None):
-        self._check()
-        variables = self._kernel_variables(variables)
-        lay = variables.layout
-        K = lay.K
-        if not self.supports_one_call(variables):
-            raise NotImplementedError('durf_render_trajectory covers the bf16 inference path (dynamics=True, bf16 object MLPs)')
+        variables, args, kw = self._one_call_args('durf_render_trajectory', variables, ext, alpha, white_bkgd)
+        K = variables.layout.K
         en = ops._enable(box_enable, K, variables.flat.device) if K > 0 else None
-        flags = ((ops.ENC_CONTRACT if self.contraction else 0) | (ops.ENC_NO_INTEGRATION if self.disable_integration else 0) |
-                 (ops.ENC_CYLINDER if self.ray_shape == 'cylinder' else 0))
-        o0 = lay.mlp_off['BoxMLP_0'] if K else 0
-        return ops.render_trajectory(
-            cams, times, variables['params']['box_centers'], ext.reshape(-1, 3).contiguous() if (K and ext is not None) else None,
-            variables.mlp_flat('MLP_0'), variables.flat[o0:o0 + K * lay.mlp_size[W_OBJ]] if K else None, lay.mlp_size[W_OBJ],
-            self.num_samples, self.num_levels, alpha, flags, chunk, near, far, lindisp=self.lindisp,
-            bkgd_mode=ops.BKGD_WHITE if white_bkgd else ops.BKGD_GREY, density_bias=self.density_bias,
-            resample_padding=self.resample_padding, box_enable=en, outputs=outputs, out=out)
+        return ops.render_trajectory(cams, times, variables['params']['box_centers'], *args, chunk, near, far, box_enable=en,
+                                     outputs=outputs, out=out, **kw)
 
     def render_trajectory(self, variables, cams, times, ext, white_bkgd, alpha, *, near, far, chunk=8192, box_enable=None,
                           outputs=('rgb8', 'distance', 'acc'), out=None):

@@ -1369,20 +1369,25 @@ def _step_timing(num_levels, keep):
     return tm
 
 
-def _fill_forward_args(a, rays, pose, ext, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags, lindisp,
-                       bkgd_mode, density_bias, resample_padding, t_rand, u_rand, outs, dyn, zo, keep, seed=None,
-                       density_noise=0.0, density_rand=None):
-    B, K = rays.origins.shape[0], pose.shape[0]
-    a.B, a.N, a.K, a.num_levels, a.enc_flags, a.lindisp, a.bkgd_mode = B, N, K, num_levels, enc_flags, int(lindisp), bkgd_mode
+def _fill_model_args(a, K, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags, lindisp, bkgd_mode,
+                     density_bias, resample_padding):
+    """the fields of durf_forward_args that say which model renders, whatever the rays"""
+    a.N, a.K, a.num_levels, a.enc_flags, a.lindisp, a.bkgd_mode = N, K, num_levels, enc_flags, int(lindisp), bkgd_mode
     a.density_bias, a.resample_padding = density_bias, resample_padding
     a.barf_w = (C.c_float * 10)(*[float(x) for x in barf_weights(alpha)])
-    flat = [t.reshape(-1).contiguous() for t in (rays.radii, rays.near, rays.far)]
-    keep.extend(flat)
+    a.bkgd_params = _p(_f32(bkgd_params))
+    a.obj_params, a.obj_param_stride = (_p(_f32(obj_params)) if K else None), int(obj_param_stride)
+
+
+def _fill_ray_args(a, rays, pose, ext, t_rand=None, u_rand=None, seed=None, density_noise=0.0, density_rand=None, outputs=True):
+    """behind _fill_model_args: the rays, the boxes, the draws and freshly allocated output buffers of one call -> the per-level
+    outputs, dyn_mask, zo (None with outputs=False: an image call keeps them in its workspace), the tensors made on the way"""
+    a.B = B = rays.origins.shape[0]
+    N, K, num_levels = a.N, a.K, a.num_levels
+    keep = flat = [t.reshape(-1).contiguous() for t in (rays.radii, rays.near, rays.far)]
     a.origins, a.directions, a.viewdirs = _p(_f32(rays.origins)), _p(_f32(rays.directions)), _p(_f32(rays.viewdirs))
     a.radii, a.near, a.far = (_p(_f32(t)) for t in flat)
     a.pose, a.ext = (_p(_f32(pose)) if K else None), (_p(_f32(ext)) if K else None)
-    a.bkgd_params = _p(_f32(bkgd_params))
-    a.obj_params, a.obj_param_stride = (_p(_f32(obj_params)) if K else None), int(obj_param_stride)
     a.t_rand, a.u_rand = _p(t_rand), _p(u_rand)
     a.draw_noise = int(seed is not None)
     a.seed_lo, a.seed_hi = (0, 0) if seed is None else split_seed(seed)
@@ -1392,10 +1397,25 @@ def _fill_forward_args(a, rays, pose, ext, bkgd_params, obj_params, obj_param_st
         assert len(dr) == num_levels and all(t.numel() == B * N for t in dr)
         keep.extend(dr)
         a.density_rand = _vp4(*([t.data_ptr() for t in dr] + [None] * (FORWARD_MAX_LEVELS - num_levels)))
-    if outs is not None:          # (durf_render_image keeps the per-chunk outputs in its workspace)
+    outs = dyn = zo = None
+    if outputs:
+        f = lambda *sh: torch.empty(*sh, device=rays.origins.device)
+        outs = [(f(B, 3), f(B), f(B), f(B, N), f(B, N + 1), f(B, N), f(B, N)) for _ in range(num_levels)]
+        dyn, zo = torch.empty(B, 1, dtype=torch.int32, device=rays.origins.device), f(B)
         for i, name in enumerate(('rgb', 'depth', 'acc', 'weights', 't_vals', 't_mids', 't_dists')):
             setattr(a, name, _vp4(*([o[i].data_ptr() for o in outs] + [None] * (FORWARD_MAX_LEVELS - num_levels))))
     a.dyn_mask, a.zo = _p(dyn), _p(zo)
+    return outs, dyn, zo, keep
+
+
+def _image_args(rays, chunk, pose, ext, *model):
+    """a whole-image call's durf_forward_args over contiguous [n, .] ray fields (C slices them by pointer) -> a, what it points at, the chunk"""
+    a = ForwardArgs()
+    rays = type(rays)(*[t.contiguous() for t in rays])
+    _fill_model_args(a, pose.shape[0], *model)
+    keep = _fill_ray_args(a, rays, pose, ext, outputs=False)[3] + [rays]
+    a.B = ck = min(chunk, rays.origins.shape[0])
+    return a, keep, ck
 
 
 def forward_call(rays, pose, ext, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags, lindisp=False,
@@ -1406,14 +1426,10 @@ def forward_call(rays, pose, ext, bkgd_params, obj_params, obj_param_stride, N, 
     B, K = rays.origins.shape[0], pose.shape[0]
     dev = rays.origins.device
     L = _lib.lib()
-    f = lambda *sh: torch.empty(*sh, device=dev)
-    outs = [(f(B, 3), f(B), f(B), f(B, N), f(B, N + 1), f(B, N), f(B, N)) for _ in range(num_levels)]
-    dyn, zo = torch.empty(B, 1, dtype=torch.int32, device=dev), f(B)
     a = ForwardArgs()
-    keep = []
-    _fill_forward_args(a, rays, pose, ext, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags, lindisp,
-                       bkgd_mode, density_bias, resample_padding, t_rand, u_rand, outs, dyn, zo, keep, seed=seed,
-                       density_noise=density_noise, density_rand=density_rand)
+    _fill_model_args(a, K, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags, lindisp, bkgd_mode,
+                     density_bias, resample_padding)
+    outs, dyn, zo, keep = _fill_ray_args(a, rays, pose, ext, t_rand, u_rand, seed, density_noise, density_rand)
     ws = _workspace(dev, int(L.durf_forward_workspace_bytes(B, N, K)))
     with _Timed('forward_call'):
         if box_enable is not None:
@@ -1431,15 +1447,11 @@ def render_image_call(rays, pose, ext, bkgd_params, obj_params, obj_param_stride
     dev = rays.origins.device
     L = _lib.lib()
     rgb, dist_, acc = torch.empty(n, 3, device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev)
-    a = ForwardArgs()
-    keep = []
-    rays = type(rays)(*[t.contiguous() for t in rays])
-    _fill_forward_args(a, rays, pose, ext, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags, lindisp,
-                       bkgd_mode, density_bias, resample_padding, None, None, None, None, None, keep)
-    a.B = min(chunk, n)
-    ws = _workspace(dev, int(L.durf_render_image_workspace_bytes(min(chunk, n), N, K, num_levels)))
+    a, keep, ck = _image_args(rays, chunk, pose, ext, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags,
+                              lindisp, bkgd_mode, density_bias, resample_padding)
+    ws = _workspace(dev, int(L.durf_render_image_workspace_bytes(ck, N, K, num_levels)))
     with _Timed('render_image_call'):
-        _lib.check(L.durf_render_image(_stream(), C.byref(a), n, min(chunk, n), _p(rgb), _p(dist_), _p(acc), _p(ws), ws.numel()),
+        _lib.check(L.durf_render_image(_stream(), C.byref(a), n, ck, _p(rgb), _p(dist_), _p(acc), _p(ws), ws.numel()),
                    'durf_render_image')
     return rgb, dist_, acc
 
@@ -1464,15 +1476,11 @@ def render_layers_call(rays, pose, ext, bkgd_params, obj_params, obj_param_strid
         out.update(bg_rgb=f(n, 3), bg_distance=f(n), bg_acc=f(n))
     if 'objects' in layers:
         out['obj_rgba'] = f(n, 4)
-    a = ForwardArgs()
-    keep = []
-    rays = type(rays)(*[t.contiguous() for t in rays])
-    _fill_forward_args(a, rays, pose, ext, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags, lindisp,
-                       bkgd_mode, density_bias, resample_padding, None, None, None, None, None, keep)
-    a.B = min(chunk, n)
-    ws = _workspace(dev, int(L.durf_render_layers_workspace_bytes(n, min(chunk, n), N, K, num_levels)))
+    a, keep, ck = _image_args(rays, chunk, pose, ext, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags,
+                              lindisp, bkgd_mode, density_bias, resample_padding)
+    ws = _workspace(dev, int(L.durf_render_layers_workspace_bytes(n, ck, N, K, num_levels)))
     with _Timed('render_layers_call'):
-        _lib.check(L.durf_render_layers(_stream(), C.byref(a), _p(box_enable), n, min(chunk, n), _p(out['rgb']), _p(out['distance']),
+        _lib.check(L.durf_render_layers(_stream(), C.byref(a), _p(box_enable), n, ck, _p(out['rgb']), _p(out['distance']),
                                         _p(out['acc']), _p(out.get('instance')), _p(out.get('bg_rgb')), _p(out.get('bg_distance')),
                                         _p(out.get('bg_acc')), _p(out.get('obj_rgba')), _p(ws), ws.numel()), 'durf_render_layers')
     return out
@@ -1518,13 +1526,10 @@ def render_trajectory(cams, times, box_centers, ext, bkgd_params, obj_params, ob
         assert tuple(t.shape) == shape and t.dtype == dtype and t.is_cuda and t.is_contiguous(), (name, tuple(t.shape), t.dtype)
         res[name] = t
     a = ForwardArgs()
-    a.B, a.N, a.K, a.num_levels, a.enc_flags, a.lindisp, a.bkgd_mode = min(chunk, max(n, 1)), N, K, num_levels, enc_flags, int(lindisp), bkgd_mode
-    a.density_bias, a.resample_padding = density_bias, resample_padding
-    a.barf_w = (C.c_float * 10)(*[float(x) for x in barf_weights(alpha)])
+    _fill_model_args(a, K, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags, lindisp, bkgd_mode,
+                     density_bias, resample_padding)
+    a.B = ck = min(chunk, max(n, 1))
     a.ext = _p(_f32(ext)) if (K and ext is not None) else None      # (poses only: nothing is rendered)
-    a.bkgd_params = _p(_f32(bkgd_params))
-    a.obj_params, a.obj_param_stride = (_p(_f32(obj_params)) if K else None), int(obj_param_stride)
-    ck = min(chunk, max(n, 1))
     ws = _workspace(dev, int(L.durf_render_trajectory_workspace_bytes(F, ck, N, K, num_levels)))
     with _Timed('render_trajectory'):
         _lib.check(L.durf_render_trajectory(_stream(), C.byref(a), _p(box_enable), _p(_f32(box_centers)) if K else None, T, F, cam_arr,
@@ -1575,16 +1580,12 @@ def train_call(rays, pose, ext, params_flat, m, v, box_floats, mlp0_floats, obj_
     B, K = rays.origins.shape[0], pose.shape[0]
     dev = rays.origins.device
     L = _lib.lib()
-    f = lambda *sh: torch.empty(*sh, device=dev)
-    outs = [(f(B, 3), f(B), f(B), f(B, N), f(B, N + 1), f(B, N), f(B, N)) for _ in range(num_levels)]
-    dyn, zo = torch.empty(B, 1, dtype=torch.int32, device=dev), f(B)
-    grad, stats, gstats = torch.empty_like(params_flat), f(2 + 17 * num_levels), f(4)
+    grad, stats, gstats = torch.empty_like(params_flat), torch.empty(2 + 17 * num_levels, device=dev), torch.empty(4, device=dev)
     a = TrainArgs()
-    keep = []
     o0 = box_floats + mlp0_floats
-    _fill_forward_args(a.f, rays, pose, ext, params_flat[box_floats:o0], params_flat[o0:] if K else None, obj_floats, N, num_levels,
-                       alpha, enc_flags, lindisp, bkgd_mode, density_bias, resample_padding, t_rand, u_rand, outs, dyn, zo, keep, seed=seed,
-                       density_noise=density_noise, density_rand=density_rand)
+    _fill_model_args(a.f, K, params_flat[box_floats:o0], params_flat[o0:] if K else None, obj_floats, N, num_levels, alpha, enc_flags,
+                     lindisp, bkgd_mode, density_bias, resample_padding)
+    outs, dyn, zo, keep = _fill_ray_args(a.f, rays, pose, ext, t_rand, u_rand, seed, density_noise, density_rand)
     a.weight_decay_mult = float(weight_decay_mult)
     hold = [t.reshape(-1).contiguous() for t in (lossmult, gt_depth, sky)] + [pixels.contiguous()]
     a.lossmult, a.gt_depth, a.sky, a.pixels = (_p(_f32(t)) for t in hold)

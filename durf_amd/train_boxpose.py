@@ -636,25 +636,10 @@ def train_step_one_call(model, config, rng, state, batch, lr, eps, alpha, prev, 
     rays = batch['rays']
     B = rays.origins.shape[0]
     dev = variables.flat.device
-    seed = None
-    if config.randomized and noise is None:
-        if isinstance(rng, torch.Generator):
-            u = torch.rand(2, B, N + 1, device=dev, generator=rng)
-            noise = dict(t_rand=u[0], u_rand=u[1])
-            if model.density_noise > 0:             # (level by level, as the model draws them)
-                noise['density'] = [torch.randn(B, N, device=dev, generator=rng) for _ in range(L)]
-        else:                                       # the library draws (durf_forward_args.draw_noise), as train_step does
-            seed = int(rng) if rng is not None else 0
-            noise = dict(t_rand=None, u_rand=None)
-    dn = model.density_noise if (config.randomized and model.density_noise > 0) else 0.0
-    if dn and seed is None and 'density' not in noise:      # injected sampling draws only: the generator the model falls back to
-        gd = om._make_generator(rng, dev)
-        noise = dict(noise, density=[torch.randn(B, N, device=dev, generator=gd) for _ in range(L)])
+    draws = model._step_draws(rng, config.randomized, noise, B, dev)
     ts = int(batch['ts'])
     pose = variables['params']['box_centers'][ts]          # a view of the parameters: the pose gradient goes to the same rows
     assert pose.is_contiguous()
-    flags = ((ops.ENC_CONTRACT if model.contraction else 0) | (ops.ENC_NO_INTEGRATION if model.disable_integration else 0) |
-             (ops.ENC_CYLINDER if model.ray_shape == 'cylinder' else 0))
     # The constant trunk of the fp32 hit-ray branch (a function of the parameters alone) across steps: the call refills the
     # buffer behind its update, on its side stream, and the next call uses it if nothing wrote the parameters in between --
     # through torch (version counter) or through this library (ops.param_generation), exactly MipNerfModel.prefetch_const_trunk's
@@ -669,20 +654,17 @@ def train_step_one_call(model, config, rng, state, batch, lr, eps, alpha, prev, 
     # ray classes' counts: no launch of their own)
     outs, dyn, zo, grad, out, gs, pose_used, cls = ops.train_call(
         rays, pose, batch['ext'].reshape(-1, 3).contiguous() if K else None, variables.flat, state.m, state.v,
-        lay.box[1] - lay.box[0], lay.mlp_size[om.W_BKGD], lay.mlp_size[om.W_OBJ], N, L, alpha, flags,
+        lay.box[1] - lay.box[0], lay.mlp_size[om.W_BKGD], lay.mlp_size[om.W_OBJ], N, L, alpha, model.enc_flags(),
         rays.lossmult, batch['pixels'][..., :3], batch['depth'], batch['sky'], batch['target'] if K else None,
         prev[0] if K else None, eps, config.box_loss_mult, 0.0 if config.rand_bkgd else (1.0 if config.white_bkgd else 0.5),
         config.disable_multiscale_loss,
         [level_multipliers(config, lvl, L) for lvl in range(L)], _stat_mults(config), lr, config.grad_max_val,
         config.grad_max_norm, state.step, lindisp=model.lindisp,
-        bkgd_mode=ops.BKGD_RAND if config.rand_bkgd else (ops.BKGD_WHITE if config.white_bkgd else ops.BKGD_GREY),
-        density_bias=model.density_bias, resample_padding=model.resample_padding,
-        t_rand=noise['t_rand'] if config.randomized else None, u_rand=noise['u_rand'] if config.randomized else None,
-        update=update, obj_fp32=obj_fp32, obj_x3=model.object_x3(), want_pos=pose_opt and not model.no_pose_opt, want_rot=pose_opt and not model.no_yaw_opt,
-        tv_loss_mult=config.tv_loss_mult if pose_opt else 0.0, seed=seed, comm=comm,
+        bkgd_mode=model.bkgd_mode(config.rand_bkgd, config.white_bkgd), density_bias=model.density_bias,
+        resample_padding=model.resample_padding, update=update, obj_fp32=obj_fp32, obj_x3=model.object_x3(), want_pos=pose_opt and not model.no_pose_opt, want_rot=pose_opt and not model.no_yaw_opt,
+        tv_loss_mult=config.tv_loss_mult if pose_opt else 0.0, comm=comm,
         world=dist.get_world_size() if dist is not None else 1, reduce_stats=dist is not None and reduce_stats,
-        density_noise=dn, density_rand=noise.get('density') if dn else None, weight_decay_mult=config.weight_decay_mult,
-        const_trunk=trunk_buf, const_trunk_valid=trunk_ok)
+        weight_decay_mult=config.weight_decay_mult, const_trunk=trunk_buf, const_trunk_valid=trunk_ok, **draws)
     if obj_fp32:        # (update=True: the buffer now holds the trunk of the updated parameters; update=False: of the unchanged ones)
         variables._c_trunk['key'] = (variables.flat._version, ops.param_generation(variables.flat))
     if pose_used is None:
