@@ -168,6 +168,21 @@ __device__ __forceinline__ void load_kernarg(T& dst, const __attribute__((addres
 #pragma unroll
     for (int i = 0; i < (int)(sizeof(T) / 4); i++) d[i] = s[i];
 }
+// Where that argument lies: type and byte offset of a kernel's LAST explicit parameter in the kernarg segment, from the
+// kernel's own function-pointer type (the parameters in order, each at its natural alignment) -- a parameter added to or
+// moved in the kernel moves the offset with it
+template <class T> struct kernarg_param { using type = T; };
+template <class F> struct kernarg_last;
+template <class... P>
+struct kernarg_last<void (*)(P...)> {
+    using type = typename decltype((kernarg_param<P>{}, ...))::type;
+    static constexpr size_t offset_of_last() {
+        size_t off = 0, end = 0;
+        ((off = (end + alignof(P) - 1) / alignof(P) * alignof(P), end = off + sizeof(P)), ...);
+        return off;
+    }
+    static constexpr size_t offset = offset_of_last();
+};
 
 // A device-memory pointer the compiler cannot trace to a kernel argument (read from the kernarg segment by hand, or a field of
 // a struct passed to a real call) is GENERIC to it, and flat loads / stores count on lgkmcnt as well as vmcnt: every ms_barrier

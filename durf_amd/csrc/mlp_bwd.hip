@@ -28,52 +28,7 @@ k_pack_bwd(int in_dim, const float* __restrict__ P, bf16x8* __restrict__ out, si
 // ---------------------------------------------------------------------------
 // fused backward data path
 // ---------------------------------------------------------------------------
-struct BPipe {        // same protocol as WPipe (mlp_fwd.hip): asm LDS-DMA, counted wait, raw barrier
-    i32x4 rsrc;          // the packed (transposed) weight stream
-    unsigned gnext;      // byte offset of the next tile group (the persistent loop wraps it to 0)
-    unsigned lds0;
-    char* lds;
-    int slot_bytes, par, wave, lane;
-    int nw;              // waves of the workgroup (8, or 4: launch_mlp_bwd)
-    int since;           // stores this wave issued after its last weight DMA (lower bound)
-    __device__ __forceinline__ void skip(int chunks) { gnext += chunks * 1024u; }
-    __device__ __forceinline__ void issue(int slot, int chunks) {
-        const unsigned dst = lds0 + (unsigned)(slot * slot_bytes);
-        for (int c = wave; c < chunks; c += nw)
-            lds_dma16_cached(rsrc, gnext + c * 1024u, lane * 16u, dst + c * 1024u);
-        gnext += chunks * 1024u;
-        since = 0;
-    }
-    __device__ __forceinline__ const char* begin(int next_chunks) {
-        wait_vmcnt_le(since);
-        __builtin_amdgcn_s_barrier();
-        issue(par ^ 1, next_chunks);
-        const char* cur = lds + par * slot_bytes;
-        par ^= 1;
-        return cur;
-    }
-};
-
-template <int NA, int NB>
-__device__ __forceinline__ f32x16 bmma_tile(const char* slot, int lane, const bf16x8* inA,
-                                            const bf16x8* inB) {
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; r++) acc[r] = 0.0f;
-    const char* ap = slot + lane * 16;
-#pragma unroll
-    for (int ks = 0; ks < NA; ks++) {
-        const bf16x8 a = *(const bf16x8*)(ap + ks * 1024);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, inA[ks], acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int ks = 0; ks < NB; ks++) {
-        const bf16x8 a = *(const bf16x8*)(ap + (NA + ks) * 1024);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, inB[ks], acc, 0, 0, 0);
-    }
-    return acc;
-}
-
+// (the weight stream L2 -> LDS: WPipe, mlp_spec.h)
 // two tiles with interleaved, independent accumulators, fragments through the register ring (mma_pair_ring, mlp_spec.h)
 template <int NA, int NB>
 __device__ __forceinline__ void bmma_tile2(const char* slot0, const char* slot1, int lane, const bf16x8* inA,
@@ -108,21 +63,16 @@ __device__ __forceinline__ void bpack_tile(const f32x16& acc, unsigned word, int
     }
 }
 
-__host__ __device__ constexpr int bgroup_tiles(int nmt, int ch, int slot) {
-    int g = nmt < slot / ch ? nmt : slot / ch;
-    return (g > 1) ? (g & ~1) : g;          // even, so tiles can be processed in pairs
-}
-
 // one backward stage: NMT tiles over the fwd stage's input features, buffered in tile groups
-// (one barrier + one prefetch burst per group, see mlp_fwd.hip)
+// (one barrier + one prefetch burst per group: group_tiles, mlp_spec.h)
 template <int SLOT, int NA, int NB, int NMT, bool MASK, int PREV_NMT, bool STORE_OUT = true>
-__device__ __forceinline__ void run_bstage(BPipe& p, const bf16x8* inA, const bf16x8* inB, bf16x8* out,
+__device__ __forceinline__ void run_bstage(WPipe& p, const bf16x8* inA, const bf16x8* inB, bf16x8* out,
                                            int next_stage_chunks, const char* mask_src,
                                            char* dz_dst, bool valid, const bf16x8* prev_out, char* prev_dst,
                                            int skip_chunks = 0, bool wrap = false) {
     // mask_src / dz_dst / prev_dst: wave-uniform byte pointers (+ lane*16 per lane), see mlp_fwd.hip
     constexpr int CH = NA + NB;
-    constexpr int G = bgroup_tiles(NMT, CH, SLOT);
+    constexpr int G = group_tiles(NMT, CH, SLOT);
     uint4 mk = make_uint4(0u, 0u, 0u, 0u);
     if (MASK && valid) mk = *(const uint4*)(mask_src + p.lane * 16);   // 128 ReLU bits of this lane's sample
     const unsigned mw[4] = {mk.x, mk.y, mk.z, mk.w};
@@ -160,7 +110,7 @@ __device__ __forceinline__ void run_bstage(BPipe& p, const bf16x8* inA, const bf
 
 // d(enc) stage (box-pose gradients): 2 output tiles = the 64 encoding features, fp32 accumulators
 template <int NA>
-__device__ __forceinline__ void run_enc_stage(BPipe& p, const bf16x8* in, f32x16* denc, bool add,
+__device__ __forceinline__ void run_enc_stage(WPipe& p, const bf16x8* in, f32x16* denc, bool add,
                                               int next_stage_chunks, bool wrap = false) {
     if (wrap) p.gnext = 0;
     const char* slot = p.begin(next_stage_chunks);           // both tiles arrive as one group
@@ -470,72 +420,6 @@ k_mlp_bwd_ms(MsBwd A) {
     }
 }
 
-// (the kernel's explicit arguments as the kernarg segment lays them out; see FwdKernArgs in mlp_fwd.hip)
-struct BwdKernArgs {
-    size_t rows; int N; const float* draw; const int32_t* ray_idx; const int32_t* count; const char* wpack; const uint4* relu_mask;
-    bf16x8* dz; bf16x8* dz_out; float* d_enc; BwdStrides bs; const int32_t* tail_idx; const int32_t* tail_count;
-    const float* draw_ray_sum; MsBwd ow;
-};
-// The object phase of a mixed backward workgroup (k_mlp_bwd<.., MIX>): two groups of four waves take (level, object, tile
-// pair) items off the ticket counter.  Inlined, arguments from the kernarg segment: see mix_object_items in mlp_fwd.hip.
-__device__ __forceinline__ void mix_object_items_bwd(char* smem, int wave, int nwg) {
-    typedef const __attribute__((address_space(4))) char* kptr_t;
-    kptr_t ka = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));          // (opaque: the loads below stay below the background loop)
-    const unsigned smem_lds = lds_addr_of(smem);
-    MsBwd ow;
-    load_kernarg(ow, ka + offsetof(BwdKernArgs, ow));
-    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    // (the ticket requests are wave 1's: wave 0 starts every item with the ray loads of the encoding / the head gradients, and
-    // a returning atomic ahead of them in its queue would be waited for with them)
-    const bool first = wave == MIX_TICKET_WAVE && lane == 0;
-    // (waves w and w + 4 share a SIMD: the second group's roles are rotated by two, so that the two groups' role-0 waves --
-    // the serial head of an item: the encoding / the head gradients -- run on different SIMDs)
-    const int half = wave >> 2, w4 = (wave + MIX_ROLE_ROT * half) & 3;
-    char* const lds = smem + half * msb::LDS_BYTES;
-    volatile __attribute__((address_space(3))) int* const tk =
-        (volatile __attribute__((address_space(3))) int*)(size_t)(__builtin_amdgcn_readfirstlane(smem_lds) + 2u * msb::LDS_BYTES);
-    volatile __attribute__((address_space(3))) int* const npl = tk + 4;         // the objects' pair counts, once per workgroup
-    if (wave == 0 && lane < ow.nobj) npl[lane] = (int)msb_pairs_of(ow, lane);
-    ms_barrier();
-    size_t total = 0;
-    for (int k = 0; k < ow.nobj; k++) total += (size_t)npl[k];
-    total = (size_t)__builtin_amdgcn_readfirstlane((unsigned)total);
-    const size_t items = total * (size_t)ow.lv.n;
-    const int last = 2 * (int)((items + 1) / 2 + nwg - 1);            // the value the LAST request of the launch returns
-    int t = 0;
-    // (a GLOBAL atomic: a flat one counts on lgkmcnt, and the first barrier of the item would wait for the request under way)
-    DURF_G(int)* const ticket = (DURF_G(int)*)ow.ticket;
-    if (first) { t = __hip_atomic_fetch_add(ticket, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); *tk = t; }
-    ms_barrier();
-    t = __builtin_amdgcn_readfirstlane(*tk);
-    while ((size_t)t < items) {
-        int tn = 0;
-        if (first) tn = __hip_atomic_fetch_add(ticket, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the next request is under way while this item runs
-        const size_t item = (size_t)t + (size_t)half;
-        const bool live = item < items;
-        const int level = __builtin_amdgcn_readfirstlane(live ? (int)(item / total) : 0);
-        size_t k = 0, pair = live ? item - (size_t)level * total : 0;
-        for (; live && k + 1 < (size_t)ow.nobj; k++) {
-            const size_t np = (size_t)npl[k];
-            if (pair < np) break;
-            pair -= np;
-        }
-        k = (size_t)__builtin_amdgcn_readfirstlane((unsigned)(live ? k : 0));
-        // (this level's operands straight from the kernarg segment: a dynamically indexed copy would live in scratch)
-        const __attribute__((address_space(4))) MsBwd* kp = (const __attribute__((address_space(4))) MsBwd*)(ka + offsetof(BwdKernArgs, ow));
-        const float* draw = kp->lv.draw[level];
-        const uint4* mk = kp->lv.relu_mask[level];
-        bf16x8* dzl = kp->lv.dz[level];
-        bf16x8* dzo = kp->lv.dz_out[level];
-        msb_bwd_pair(ow, draw, mk, dzl, dzo, lds, lane, w4, live, k, pair);
-        if (first) *tk = tn;
-        ms_barrier();
-        t = __builtin_amdgcn_readfirstlane(*tk);
-    }
-    if (first && t == last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // every other workgroup has made its last request
-}
-
 // MIX (W = 256, 8 waves; round 6): the background blocks, then the object MLPs' backward items on two 4-wave groups per
 // workgroup -- the counterpart of k_mlp_fwd<.., MIX> (mlp_fwd.hip), dz / dz_out of both classes bit-identical to the launches
 // of their own.
@@ -547,7 +431,7 @@ k_mlp_bwd(size_t rows, int N, const float* __restrict__ draw, const int32_t* __r
           float* __restrict__ d_enc, BwdStrides bs, const int32_t* __restrict__ tail_idx,
           const int32_t* __restrict__ tail_count, const float* __restrict__ draw_ray_sum, MsBwd ow_arg) {
     static_assert(!MIX || (W == 256 && NWV == 8 && !POSE), "the mixed launch: background blocks of 8 waves + object items on 2 x 4");
-    (void)ow_arg;      // (read from the kernarg segment behind the background loop: mix_object_items_bwd)
+    (void)ow_arg;      // (read from the kernarg segment behind the background loop: mix_object_items, mlp_spec.h)
     using S = MlpSpec<W>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (gridDim.y > 1) {                             // batched object MLPs: this workgroup's object slab
@@ -578,13 +462,13 @@ k_mlp_bwd(size_t rows, int N, const float* __restrict__ draw, const int32_t* __r
     const size_t ntile32 = rows >> 5;
     const size_t nblk = (nrows + 32 * NWV - 1) / (32 * NWV);
 
-    BPipe p;
+    WPipe p;
     constexpr int SLOT = 4 * (S::KW + 1);
     p.rsrc = make_rsrc(wpack);
     p.gnext = 0; p.lds = smem; p.slot_bytes = SLOT * 1024; p.par = 0;
     p.lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
     p.wave = wave; p.lane = lane; p.nw = NWV;
-    constexpr int GB0 = bgroup_tiles(S::CT, 1, SLOT) * 1;                 // all tiles of the rgb-head stage
+    constexpr int GB0 = group_tiles(S::CT, 1, SLOT) * 1;                 // all tiles of the rgb-head stage
     if (!MIX || has_block) p.issue(0, GB0);
 
   // persistent workgroup (see mlp_fwd.hip): loop over this CU's 256-sample blocks
@@ -625,9 +509,9 @@ k_mlp_bwd(size_t rows, int N, const float* __restrict__ draw, const int32_t* __r
     };
     bf16x8 a[S::KW], b[S::KW], c[S::KC];
     // bwd of stage 10 (rgb head): d rgb -> d A9, masked by A9
-    constexpr int GC = bgroup_tiles(S::WT, S::KC, SLOT) * S::KC;           // first group of bwd stage 9
-    constexpr int G8 = bgroup_tiles(S::WT, S::KW + 1, SLOT) * (S::KW + 1);
-    constexpr int GW = bgroup_tiles(S::WT, S::KW, SLOT) * S::KW;
+    constexpr int GC = group_tiles(S::WT, S::KC, SLOT) * S::KC;           // first group of bwd stage 9
+    constexpr int G8 = group_tiles(S::WT, S::KW + 1, SLOT) * (S::KW + 1);
+    constexpr int GW = group_tiles(S::WT, S::KW, SLOT) * S::KW;
     constexpr int GE = 2 * S::KW;                                             // d(enc) stage: 2 tiles, one group
     run_bstage<SLOT, 1, 0, S::CT, true, 0>(p, g10, nullptr, c, GC, stash_at(9), dz_at(9), tile_valid, nullptr, nullptr);
     // bwd of stage 9 (view layer): d Z9 -> d bottleneck (linear)
@@ -671,7 +555,13 @@ k_mlp_bwd(size_t rows, int N, const float* __restrict__ draw, const int32_t* __r
   if constexpr (MIX) {
     if (has_block) __builtin_amdgcn_s_setprio(0);
     ms_barrier();                  // every wave is past its last weight read; no DMA is in flight (the last block prefetches none)
-    mix_object_items_bwd(smem, wave, (int)gridDim.x);
+    mix_object_items<decltype(&k_mlp_bwd<W, POSE, NWV, MIX>), MsBwd, msb::LDS_BYTES, true>(
+        smem, wave, (int)gridDim.x, msb_pairs_of,
+        [](const MsBwd& ow, auto kp, int level, char* lds, int lane, int role, bool live, size_t k, size_t pair) {
+            // (this level's operands straight from the kernarg segment: a dynamically indexed copy would live in scratch)
+            msb_bwd_pair(ow, kp->lv.draw[level], kp->lv.relu_mask[level], kp->lv.dz[level], kp->lv.dz_out[level], lds, lane, role,
+                         live, k, pair);
+        });
   }
 }
 
@@ -1413,16 +1303,8 @@ int durf_mlp_bwd_obj(void* stream, size_t rows, int N, const float* draw, const 
     ow.bs.d_enc = rows * DURF_ENC_DIM * sizeof(float);
     ow.ticket = durf::next_ticket();
     DURF_REQUIRE(ow.ticket != nullptr, "no item counter for the mixed launch (device allocation failed)");
-    const unsigned nblk = durf_cdiv(rows, 256), nobj = durf_cdiv((size_t)nlevels * K * durf_cdiv(rows, 64), 2);
-    const unsigned g = nblk + nobj < 256u ? nblk + nobj : 256u;
-    constexpr int lds = 2 * 4 * (MlpSpec<256>::KW + 1) * 1024;
-    static_assert(2 * msb::LDS_BYTES + 96 <= lds, "two object groups fit the background block's LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)k_mlp_bwd<256, false, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((k_mlp_bwd<256, false, 8, true>), dim3(g), dim3(512), lds, (hipStream_t)stream, rows, N, draw, ray_idx, count,
+    const unsigned g = mix_launch_grid<k_mlp_bwd<256, false, 8, true>, msb::LDS_BYTES>(rows, (size_t)nlevels * K * durf_cdiv(rows, 64));
+    hipLaunchKernelGGL((k_mlp_bwd<256, false, 8, true>), dim3(g), dim3(512), MIX_LDS_BYTES, (hipStream_t)stream, rows, N, draw, ray_idx, count,
                        (const char*)wpack_bwd, (const uint4*)relu_mask, (bf16x8*)dz, (bf16x8*)dz_out, (float*)nullptr, BwdStrides{},
                        tail_idx, tail_count, draw_ray_sum, ow);
     DURF_CHECK_LAUNCH("durf_mlp_bwd_obj");

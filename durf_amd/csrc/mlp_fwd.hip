@@ -11,12 +11,6 @@
 #include "mlp_pack.h"
 #include "enc_lane.h"
 
-// 16 bytes per lane, global -> LDS (lane-linear destination), as a BUFFER load: descriptor in
-// SGPRs, one constant per-lane VGPR offset (lane*16), the chunk offset in an SGPR.  The
-// global_load_lds form needs a 64-bit per-lane VGPR address for every tile group; hipcc
-// precomputes those, they spill, and a scratch reload next to an in-flight LDS-DMA makes it
-// drain the whole weight prefetch (s_waitcnt vmcnt(0)).
-
 // ---------------------------------------------------------------------------
 // weight packer: fp32 flax params -> bf16 fragment stream (one thread per 16-byte vector)
 // ---------------------------------------------------------------------------
@@ -37,37 +31,7 @@ k_pack_all(PackAll a) {
 // ---------------------------------------------------------------------------
 // fused forward
 // ---------------------------------------------------------------------------
-struct WPipe {
-    i32x4 rsrc;          // the packed weight stream
-    unsigned gnext;      // byte offset of the next tile group to prefetch
-    unsigned lds0;       // LDS byte address of the two slots
-    char* lds;
-    int slot_bytes;
-    int par;             // slot that holds the tile about to be consumed
-    int wave, lane;
-    int nw;              // waves of the workgroup (8; 4 for launches that would leave half the chip idle, launch_mlp_fwd)
-    int since;           // vector-memory ops (stores) this wave issued after its last weight DMA (lower bound)
-    __device__ __forceinline__ void issue(int slot, int chunks) {
-        const unsigned dst = lds0 + (unsigned)(slot * slot_bytes);
-        for (int c = wave; c < chunks; c += nw)
-            lds_dma16_cached(rsrc, gnext + c * 1024u, lane * 16u, dst + c * 1024u);
-        gnext += chunks * 1024u;
-        since = 0;
-    }
-    // Make the prefetched tile group visible, start the prefetch of the following one
-    // (next_chunks KB, 0 = none) into the other slot, and return the slot to consume.
-    // The wait covers this wave's part of the DMA but leaves the stores issued after it in
-    // flight; the barrier then publishes every wave's part and frees the other slot.
-    __device__ __forceinline__ const char* begin(int next_chunks) {
-        wait_vmcnt_le(since);
-        __builtin_amdgcn_s_barrier();
-        issue(par ^ 1, next_chunks);
-        const char* cur = lds + par * slot_bytes;
-        par ^= 1;
-        return cur;
-    }
-};
-
+// (the weight stream L2 -> LDS: WPipe, mlp_spec.h)
 template <int NA, int NB>
 __device__ __forceinline__ f32x16 mma_tile(const char* slot, int lane, const bf16x8* inA,
                                            const bf16x8* inB) {
@@ -157,14 +121,7 @@ __device__ __forceinline__ unsigned pack_tile(const f32x16& acc, bf16x8& o0, bf1
     return bits;     // tile-local: flags of acc[2j] at bit j, of acc[2j+1] at bit 16+j (acc[8..15]: j = 4..7)
 }
 
-// Tiles are buffered in GROUPS: one barrier + one prefetch burst per group of up to
-// SLOT/CH output tiles (4 for a WxW layer), so the 8 waves run unsynchronised for ~64 MFMAs
-// each and the next group's weights have a whole group of compute time to arrive.
-__host__ __device__ constexpr int group_tiles(int nmt, int ch, int slot) {
-    int g = nmt < slot / ch ? nmt : slot / ch;
-    return (g > 1) ? (g & ~1) : g;          // even, so tiles can be processed in pairs
-}
-
+// (tiles are buffered in groups, one barrier + one prefetch burst each: group_tiles, mlp_spec.h)
 // One dense stage: NMT output tiles, inputs inA[NA] (C-perm) ++ inB[NB] (natural).
 // Training stores (activation stash + ReLU mask) always trail the compute by one tile pair,
 // also across stage boundaries (the previous stage's last pair is written after THIS stage's
@@ -313,8 +270,10 @@ extern "C" int durf_debug_ms_stamps(void* dst, int reset) {
 #define MS_STAMP_HO(j, i) do { } while (0)
 #endif
 
+// (the signature of an item of mix_object_items, mlp_spec.h: the arguments in the kernarg segment and the level are the backward's)
 template <bool TRAIN>
-__device__ __forceinline__ void ms_fwd_pair(const MsFwd& A, char* smem, int lane, int wave, bool live, size_t k, size_t pair) {
+__device__ __forceinline__ void ms_fwd_pair(const MsFwd& A, const __attribute__((address_space(4))) MsFwd*, int, char* smem, int lane,
+                                            int wave, bool live, size_t k, size_t pair) {
     using S = ms::S;
     constexpr int NT = ms::NT;
     const int n = lane & 31, hi = lane >> 5;
@@ -676,7 +635,7 @@ k_mlp_fwd_ms(MsFwd A) {
     for (size_t item = blockIdx.x; item < total; item += gridDim.x) {
         size_t k, pair;
         ms_item(A, item, k, pair);
-        ms_fwd_pair<TRAIN>(A, smem, lane, wave, true, k, pair);
+        ms_fwd_pair<TRAIN>(A, nullptr, 0, smem, lane, wave, true, k, pair);
     }
 }
 
@@ -694,75 +653,7 @@ k_mlp_fwd_ms(MsFwd A) {
 // the background's cost 22 us per level; on a second stream the early object workgroups delayed the persistent
 // background workgroups that wanted their CUs); at 1024 rays x K = 8 the workgroups with one block instead of two pick
 // them up.  `ow.ticket`: a zeroed int the launch leaves zeroed (the workgroup that draws the last ticket resets it).
-// (the kernel's explicit arguments as the kernarg segment lays them out -- in order, naturally aligned: the mixed launch reads
-// its object arguments from the segment itself, see below)
-struct FwdKernArgs {
-    size_t rows; int N; const bf16x8* enc; const bf16x8* view; const int32_t* ray_idx; const int32_t* count; const char* wpack;
-    float* raw; bf16x8* stash; uint4* relu_mask; FwdStrides bs; const int32_t* tail_idx; const int32_t* tail_count; EncIn ei;
-    MsFwd ow;
-};
-// The object phase of a mixed workgroup, inlined behind the background loop.  Two things keep it from costing that loop --
-// which sits at the 256-register cap -- anything: (i) nothing of it lives in a vector register across the loop (the lane number
-// is re-derived, everything else is wave-uniform), (ii) its ~70 dwords of arguments are fetched from the kernarg segment
-// HERE, behind an opaque pointer, instead of at kernel entry (as ordinary arguments hipcc keeps them in scalar registers
-// across the loop: 85 more SGPR spills, two more vector registers reserved for them).  What remains is one more vector
-// register of SGPR spill lanes than the plain kernel has: 28 B of scratch instead of 12, six reloads per 256-sample block.
-// (As a real CALL -- own register allocation, the loop untouched -- the phase needs a 360-byte frame for the callee-saved
-// registers, and a launch with that much scratch per lane took ~23 us longer whatever it did: profiles/r06_mix.txt.)
-template <bool TRAIN>
-__device__ __forceinline__ void mix_object_items(char* smem, int wave, int nwg) {
-    typedef const __attribute__((address_space(4))) char* kptr_t;
-    kptr_t ka = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));          // (opaque: the loads below stay below)
-    const unsigned smem_lds = lds_addr_of(smem);
-    MsFwd ow;
-    load_kernarg(ow, ka + offsetof(FwdKernArgs, ow));      // (scalar loads: a constant-address-space source)
-    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    // (the ticket requests are wave 1's: wave 0 starts every item with the ray loads of the encoding / the head gradients, and
-    // a returning atomic ahead of them in its queue would be waited for with them)
-    const bool first = wave == MIX_TICKET_WAVE && lane == 0;
-    // (waves w and w + 4 share a SIMD: the second group's roles are rotated by two, so that the two groups' role-0 waves --
-    // which carry an item's extra work: the density and rgb heads (and, until the encoding was dealt to all four waves, the
-    // whole input phase) -- run on different SIMDs)
-    const int half = wave >> 2, w4 = (wave + MIX_ROLE_ROT * half) & 3;
-    char* const lds = smem + half * ms::LDS_BYTES;
-    volatile __attribute__((address_space(3))) int* const tk =
-        (volatile __attribute__((address_space(3))) int*)(size_t)(__builtin_amdgcn_readfirstlane(smem_lds) + 2u * ms::LDS_BYTES);
-    // (the objects' pair counts once per workgroup, in LDS: re-read from memory for every item they were a chain of K
-    // dependent loads in front of it)
-    volatile __attribute__((address_space(3))) int* const npl = tk + 4;
-    if (wave == 0 && lane < ow.nobj) npl[lane] = (int)ms_pairs_of(ow, lane);
-    ms_barrier();
-    size_t total = 0;
-    for (int k = 0; k < ow.nobj; k++) total += (size_t)npl[k];
-    total = (size_t)__builtin_amdgcn_readfirstlane((unsigned)total);
-    const int last = 2 * (int)((total + 1) / 2 + nwg - 1);            // the value the LAST request of the launch returns
-    int t = 0;
-    // (a GLOBAL atomic: a flat one counts on lgkmcnt, and the first barrier of the item would wait for the request under way)
-    DURF_G(int)* const ticket = (DURF_G(int)*)ow.ticket;
-    if (first) { t = __hip_atomic_fetch_add(ticket, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); *tk = t; }
-    ms_barrier();
-    t = __builtin_amdgcn_readfirstlane(*tk);
-    while ((size_t)t < total) {
-        int tn = 0;
-        if (first) tn = __hip_atomic_fetch_add(ticket, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the next request is under way while this item runs
-        size_t k = 0, pair = (size_t)t + (size_t)half;
-        const bool live = pair < total;
-        for (; live && k + 1 < (size_t)ow.nobj; k++) {
-            const size_t np = (size_t)npl[k];
-            if (pair < np) break;
-            pair -= np;
-        }
-        k = (size_t)__builtin_amdgcn_readfirstlane((unsigned)(live ? k : 0));
-        pair = live ? pair : 0;
-        ms_fwd_pair<TRAIN>(ow, lds, lane, w4, live, k, pair);
-        if (first) *tk = tn;
-        ms_barrier();
-        t = __builtin_amdgcn_readfirstlane(*tk);
-    }
-    if (first && t == last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // every other workgroup has made its last request
-}
-
+// (the object phase: mix_object_items, mlp_spec.h)
 template <int W, bool TRAIN, int NWV = 8, bool ENC = false, bool MIX = false>
 __global__ void __launch_bounds__(512, 2)
 k_mlp_fwd(size_t rows, int N, const bf16x8* __restrict__ enc, const bf16x8* __restrict__ view,
@@ -771,7 +662,7 @@ k_mlp_fwd(size_t rows, int N, const bf16x8* __restrict__ enc, const bf16x8* __re
           uint4* __restrict__ relu_mask, FwdStrides bs, const int32_t* __restrict__ tail_idx,
           const int32_t* __restrict__ tail_count, EncIn ei, MsFwd ow_arg) {
     static_assert(!MIX || (W == 256 && NWV == 8 && ENC), "the mixed launch: background blocks of 8 waves + object items on 2 x 4");
-    (void)ow_arg;      // (read through the kernarg segment pointer behind the background loop, not held in SGPRs across it)
+    (void)ow_arg;      // (read through the kernarg segment pointer behind the background loop, not held in SGPRs across it: mix_object_items)
     using S = MlpSpec<W>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (gridDim.y > 1) {                             // batched object MLPs: this workgroup's object slab
@@ -1028,7 +919,8 @@ k_mlp_fwd(size_t rows, int N, const bf16x8* __restrict__ enc, const bf16x8* __re
     // still in flight do not touch the LDS; the barrier makes sure every wave is past its last weight read)
     if (has_block) __builtin_amdgcn_s_setprio(0);
     ms_barrier();
-    mix_object_items<TRAIN>(smem, wave, (int)gridDim.x);
+    mix_object_items<decltype(&k_mlp_fwd<W, TRAIN, NWV, ENC, MIX>), MsFwd, ms::LDS_BYTES, false>(smem, wave, (int)gridDim.x, ms_pairs_of,
+                                                                                                 ms_fwd_pair<TRAIN>);
   }
 }
 
@@ -1135,18 +1027,8 @@ int durf_mlp_fwd_enc_obj(void* stream, size_t rows, int N, const float* t_vals, 
         if (pr[0] == '1') ow.nobj = 0;
         if (pr[0] == '2') ei.flags |= 1 << 30;               // ... and without its background blocks
     }
-    hipStream_t s = (hipStream_t)stream;
-    // one workgroup per CU: the background blocks' (capacity: the counts live on the device), then room for the object items
-    const unsigned nblk = durf_cdiv(rows, 256), nobj = durf_cdiv((size_t)K * durf_cdiv(rows, 64), 2);
-    const unsigned g = nblk + nobj < 256u ? nblk + nobj : 256u;
-    constexpr int lds = 2 * 4 * (MlpSpec<256>::KW + 1) * 1024;
-    static_assert(2 * ms::LDS_BYTES + 96 <= lds, "two object groups fit the background block's LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)k_mlp_fwd<256, true, 8, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((k_mlp_fwd<256, true, 8, true, true>), dim3(g), dim3(512), lds, s, rows, N, (const bf16x8*)enc_tile,
+    const unsigned g = mix_launch_grid<k_mlp_fwd<256, true, 8, true, true>, ms::LDS_BYTES>(rows, (size_t)K * durf_cdiv(rows, 64));
+    hipLaunchKernelGGL((k_mlp_fwd<256, true, 8, true, true>), dim3(g), dim3(512), MIX_LDS_BYTES, (hipStream_t)stream, rows, N, (const bf16x8*)enc_tile,
                        (const bf16x8*)view_bf16, ray_idx, count, (const char*)wpack_fwd, raw, (bf16x8*)stash, (uint4*)relu_mask,
                        FwdStrides{}, tail_idx, tail_count, ei, ow);
     DURF_CHECK_LAUNCH("durf_mlp_fwd_enc_obj");

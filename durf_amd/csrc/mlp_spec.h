@@ -168,3 +168,150 @@ __device__ __forceinline__ void mma_pair_ring(const char* slot0, const char* slo
         if constexpr (i & 1) hook(std::integral_constant<int, ks>{});
     });
 }
+
+// ---------------------------------------------------------------------------
+// Weight stream L2 -> LDS of the fused kernels (k_mlp_fwd, k_mlp_bwd): two slots, one tile group each.
+// 16 bytes per lane, global -> LDS (lane-linear destination), as a BUFFER load: descriptor in
+// SGPRs, one constant per-lane VGPR offset (lane*16), the chunk offset in an SGPR.  The
+// global_load_lds form needs a 64-bit per-lane VGPR address for every tile group; hipcc
+// precomputes those, they spill, and a scratch reload next to an in-flight LDS-DMA makes it
+// drain the whole weight prefetch (s_waitcnt vmcnt(0)).
+// ---------------------------------------------------------------------------
+struct WPipe {
+    i32x4 rsrc;          // the packed weight stream (the backward's: transposed)
+    unsigned gnext;      // byte offset of the next tile group to prefetch (the backward's persistent loop wraps it to 0)
+    unsigned lds0;       // LDS byte address of the two slots
+    char* lds;
+    int slot_bytes;
+    int par;             // slot that holds the tile about to be consumed
+    int wave, lane;
+    int nw;              // waves of the workgroup (8; 4 for launches that would leave half the chip idle: launch_mlp_fwd / launch_mlp_bwd)
+    int since;           // vector-memory ops (stores) this wave issued after its last weight DMA (lower bound)
+    __device__ __forceinline__ void skip(int chunks) { gnext += chunks * 1024u; }      // stages a variant does not run
+    __device__ __forceinline__ void issue(int slot, int chunks) {
+        const unsigned dst = lds0 + (unsigned)(slot * slot_bytes);
+        for (int c = wave; c < chunks; c += nw)
+            lds_dma16_cached(rsrc, gnext + c * 1024u, lane * 16u, dst + c * 1024u);
+        gnext += chunks * 1024u;
+        since = 0;
+    }
+    // Make the prefetched tile group visible, start the prefetch of the following one
+    // (next_chunks KB, 0 = none) into the other slot, and return the slot to consume.
+    // The wait covers this wave's part of the DMA but leaves the stores issued after it in
+    // flight; the barrier then publishes every wave's part and frees the other slot.
+    __device__ __forceinline__ const char* begin(int next_chunks) {
+        wait_vmcnt_le(since);
+        __builtin_amdgcn_s_barrier();
+        issue(par ^ 1, next_chunks);
+        const char* cur = lds + par * slot_bytes;
+        par ^= 1;
+        return cur;
+    }
+};
+
+// Tiles are buffered in GROUPS: one barrier + one prefetch burst per group of up to
+// SLOT/CH output tiles (4 for a WxW layer), so the 8 waves run unsynchronised for ~64 MFMAs
+// each and the next group's weights have a whole group of compute time to arrive.
+__host__ __device__ constexpr int group_tiles(int nmt, int ch, int slot) {
+    int g = nmt < slot / ch ? nmt : slot / ch;
+    return (g > 1) ? (g & ~1) : g;          // even, so tiles can be processed in pairs
+}
+
+// ---------------------------------------------------------------------------
+// The object phase of a mixed workgroup (k_mlp_fwd<.., MIX>, k_mlp_bwd<.., MIX>), inlined behind the background loop: the
+// workgroup turns into TWO groups of four waves that take items of the K object MLPs -- (object, tile pair), times the levels
+// in the backward (LEVELS; level-major) -- off an atomic ticket counter until none is left.
+//   KERNEL  the function-pointer type of the very instantiation that runs the phase; its last parameter is the phase's
+//           argument struct ARGS (fields nobj and ticket; lv.n with LEVELS), read at the offset the kernel's own parameter
+//           list gives it (kernarg_last, durf_common.h)
+//   pairs_of(ow, k)  tile pairs of object k;  item(ow, kp, level, lds, lane, role, live, k, pair)  one item on four waves
+//           and ITEM_LDS bytes at `lds` (kp: the arguments in the kernarg segment itself -- the backward reads its level
+//           operands straight from there: a dynamically indexed copy would live in scratch).  The forward's item is
+//           ms_fwd_pair ITSELF: behind a wrapper, lambda or function, hipcc schedules the background loop differently.
+// Two things keep the phase from costing the background loop -- which sits at the 256-register cap -- anything: (i) nothing of
+// it lives in a vector register across the loop (the lane number is re-derived, everything else is wave-uniform), (ii) its ~70
+// dwords of arguments are fetched from the kernarg segment HERE, behind an opaque pointer, instead of at kernel entry (as
+// ordinary arguments hipcc keeps them in scalar registers across the loop: 85 more SGPR spills, two more vector registers
+// reserved for them).  What remains is one more vector register of SGPR spill lanes than the plain kernel has: 28 B of scratch
+// instead of 12, six reloads per 256-sample block.  (As a real CALL -- own register allocation, the loop untouched -- the
+// phase needs a 360-byte frame for the callee-saved registers, and a launch with that much scratch per lane took ~23 us
+// longer whatever it did: profiles/r06_mix.txt.)
+// The ticket: a zeroed int the launch leaves zeroed.  Every request adds 2 (one item per group); a workgroup asks for its next
+// pair of items while the current one runs and stops at the first ticket past the end, so the launch makes
+// ceil(items / 2) + nwg requests and the workgroup that draws the last of them -- every other one has made its last -- resets
+// the counter.
+// ---------------------------------------------------------------------------
+template <class KERNEL, class ARGS, int ITEM_LDS, bool LEVELS, class PairsOf, class Item>
+__device__ __forceinline__ void mix_object_items(char* smem, int wave, int nwg, PairsOf&& pairs_of, Item&& item) {
+    static_assert(std::is_same<typename kernarg_last<KERNEL>::type, ARGS>::value, "the object arguments are the kernel's LAST parameter");
+    typedef const __attribute__((address_space(4))) char* kptr_t;
+    kptr_t ka = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));          // (opaque: the loads below stay below the background loop)
+    const __attribute__((address_space(4))) ARGS* const kp = (const __attribute__((address_space(4))) ARGS*)(ka + kernarg_last<KERNEL>::offset);
+    const unsigned smem_lds = lds_addr_of(smem);
+    ARGS ow;
+    load_kernarg(ow, (kptr_t)kp);          // (scalar loads: a constant-address-space source)
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    // (the ticket requests are wave 1's: wave 0 starts every item with the ray loads of the encoding / the head gradients, and
+    // a returning atomic ahead of them in its queue would be waited for with them)
+    const bool first = wave == MIX_TICKET_WAVE && lane == 0;
+    // (waves w and w + 4 share a SIMD: the second group's roles are rotated by two, so that the two groups' role-0 waves --
+    // which carry an item's serial head: the encoding / the head gradients, the density and rgb heads -- run on different SIMDs)
+    const int half = wave >> 2, w4 = (wave + MIX_ROLE_ROT * half) & 3;
+    char* const lds = smem + half * ITEM_LDS;
+    volatile __attribute__((address_space(3))) int* const tk =
+        (volatile __attribute__((address_space(3))) int*)(size_t)(__builtin_amdgcn_readfirstlane(smem_lds) + 2u * ITEM_LDS);
+    // (the objects' pair counts once per workgroup, in LDS: re-read from memory for every item they were a chain of K
+    // dependent loads in front of it)
+    volatile __attribute__((address_space(3))) int* const npl = tk + 4;
+    if (wave == 0 && lane < ow.nobj) npl[lane] = (int)pairs_of(ow, lane);
+    ms_barrier();
+    size_t total = 0;
+    for (int k = 0; k < ow.nobj; k++) total += (size_t)npl[k];
+    total = (size_t)__builtin_amdgcn_readfirstlane((unsigned)total);
+    size_t items = total;
+    if constexpr (LEVELS) items = total * (size_t)ow.lv.n;
+    const int last = 2 * (int)((items + 1) / 2 + nwg - 1);            // the value the LAST request of the launch returns
+    int t = 0;
+    // (a GLOBAL atomic: a flat one counts on lgkmcnt, and the first barrier of the item would wait for the request under way)
+    DURF_G(int)* const ticket = (DURF_G(int)*)ow.ticket;
+    if (first) { t = __hip_atomic_fetch_add(ticket, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); *tk = t; }
+    ms_barrier();
+    t = __builtin_amdgcn_readfirstlane(*tk);
+    while ((size_t)t < items) {
+        int tn = 0;
+        if (first) tn = __hip_atomic_fetch_add(ticket, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the next request is under way while this item runs
+        const size_t it = (size_t)t + (size_t)half;
+        const bool live = it < items;
+        int level = 0;
+        if constexpr (LEVELS) level = __builtin_amdgcn_readfirstlane(live ? (int)(it / total) : 0);
+        size_t k = 0, pair = live ? it - (size_t)level * total : 0;
+        for (; live && k + 1 < (size_t)ow.nobj; k++) {
+            const size_t np = (size_t)npl[k];
+            if (pair < np) break;
+            pair -= np;
+        }
+        k = (size_t)__builtin_amdgcn_readfirstlane((unsigned)(live ? k : 0));
+        item(ow, kp, level, lds, lane, w4, live, k, pair);
+        if (first) *tk = tn;
+        ms_barrier();
+        t = __builtin_amdgcn_readfirstlane(*tk);
+    }
+    if (first && t == last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Host side of a mixed launch: the LDS of a background block (two weight slots), which the two object groups must fit, set
+// once per kernel, and the grid -- one workgroup per CU: the background blocks' (capacity: the counts live on the device),
+// then room for `obj_items` object items, two per workgroup.
+constexpr int MIX_LDS_BYTES = 2 * 4 * (MlpSpec<256>::KW + 1) * 1024;
+template <auto KERNEL, int ITEM_LDS>
+static inline unsigned mix_launch_grid(size_t rows, size_t obj_items) {
+    static_assert(2 * ITEM_LDS + 96 <= MIX_LDS_BYTES, "two object groups fit the background block's LDS");
+    static bool attr_set = false;      // once per kernel (the attribute sticks to the function)
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, MIX_LDS_BYTES);
+        attr_set = true;
+    }
+    const unsigned n = durf_cdiv(rows, 256) + durf_cdiv(obj_items, 2);
+    return n < 256u ? n : 256u;
+}
