@@ -1621,3 +1621,85 @@ def train_call(rays, pose, ext, params_flat, m, v, box_floats, mlp0_floats, obj_
         fn = L.durf_train_step if update else L.durf_loss_backward
         _lib.check(fn(_stream(), C.byref(a), _p(ws), ws.numel()), 'durf_train_step' if update else 'durf_loss_backward')
     return outs, dyn, zo, grad, stats, (gstats if update else None), pose_used, cls
+
+
+# ---- depth visualisations (csrc/vis.hip; include/durf_hip.h durf_vis_*) -----------------------------------------------------
+VIS_CURVES = dict(neglog=0, identity=1, inverse=2)       # DURF_VIS_CURVE_*
+VIS_STATS_FLOATS = 8                                     # DURF_VIS_STATS_FLOATS
+VIS_STATS_FIELDS = ('near_auto', 'far_auto', 'normal_scale', 'count', 'var_x', 'var_y', 'var_depth', 'mean_depth')
+VIS_NORMALS_RAW = 1
+
+
+def _vis_outputs(shape, dev, want_float, want_u8, rgb, rgb8):
+    if not (want_float or want_u8):
+        raise ValueError('at least one of the float and the 8-bit output')
+    if want_float and rgb is None:
+        rgb = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
+    if want_u8 and rgb8 is None:
+        rgb8 = torch.empty(shape + (3,), dtype=torch.uint8, device=dev)
+    for t, dt in ((rgb, torch.float32), (rgb8, torch.uint8)):
+        assert t is None or (t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape + (3,)), (t.dtype, t.shape)
+    return (rgb if want_float else None), (rgb8 if want_u8 else None)
+
+
+def vis_stats(depth):
+    """depth [F,H,W] -> [F, VIS_STATS_FLOATS] device record (VIS_STATS_FIELDS): durf_vis_stats, three launches, no read-back"""
+    F, H, W = depth.shape
+    L = _lib.lib()
+    stats = torch.empty(F, VIS_STATS_FLOATS, device=depth.device)
+    nbytes = int(L.durf_vis_scratch_bytes(F, H, W))
+    scratch = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=depth.device)
+    with _Timed('vis_stats'):
+        _lib.check(L.durf_vis_stats(_stream(), F, H, W, _p(_f32(depth)), _p(stats), _p(scratch), nbytes), 'durf_vis_stats')
+    return stats
+
+
+def vis_depth(depth, acc, rng, curve='neglog', modulus=0.0, lut=None, want_float=True, want_u8=False, rgb=None, rgb8=None):
+    """durf_vis_depth: depth [F,H,W], acc [F,H,W] or None, rng [F, >= 2] (near, far in its first two columns; None with
+    modulus > 0), lut None (turbo) or [256,3] -> (rgb [F,H,W,3] or None, rgb8 uint8 or None)"""
+    F, H, W = depth.shape
+    if curve not in VIS_CURVES:
+        raise ValueError('curve_fn %r: choose from %s' % (curve, sorted(VIS_CURVES)))
+    if lut is not None and (tuple(lut.shape) != (256, 3)):
+        raise ValueError('colormap: a [256,3] tensor, got %s' % (tuple(lut.shape),))
+    if acc is not None and acc.shape != depth.shape:
+        raise ValueError('acc %s against depth %s' % (tuple(acc.shape), tuple(depth.shape)))
+    if rng is not None:
+        assert rng.dim() == 2 and rng.shape[0] == F and rng.shape[1] >= 2 and rng.stride(1) == 1, (rng.shape, rng.stride())
+    rgb, rgb8 = _vis_outputs((F, H, W), depth.device, want_float, want_u8, rgb, rgb8)
+    with _Timed('vis_depth'):
+        _lib.check(_lib.lib().durf_vis_depth(_stream(), F, H, W, _p(_f32(depth)), _p(None if acc is None else _f32(acc)),
+                                             _p(rng), 0 if rng is None else rng.stride(0), VIS_CURVES[curve], float(modulus),
+                                             _p(None if lut is None else _f32(lut)), _p(rgb), _p(rgb8)), 'durf_vis_depth')
+    return rgb, rgb8
+
+
+def vis_normals(depth, acc, scale, raw=False, want_float=True, want_u8=False, rgb=None, rgb8=None):
+    """durf_vis_normals: scale a float32 device tensor read at stride scale.stride(0) (one value per frame; None: 1);
+    raw: the normals themselves (depth_to_normals)"""
+    F, H, W = depth.shape
+    if acc is not None and acc.shape != depth.shape:
+        raise ValueError('acc %s against depth %s' % (tuple(acc.shape), tuple(depth.shape)))
+    if scale is not None:
+        assert scale.dtype == torch.float32 and scale.is_cuda and scale.shape[0] == F, (scale.dtype, scale.shape)
+    rgb, rgb8 = _vis_outputs((F, H, W), depth.device, want_float, want_u8, rgb, rgb8)
+    stride = 1 if scale is None else max(int(scale.stride(0)), 1)
+    with _Timed('vis_normals'):
+        _lib.check(_lib.lib().durf_vis_normals(_stream(), F, H, W, _p(_f32(depth)), _p(None if acc is None else _f32(acc)),
+                                               _p(scale), stride, VIS_NORMALS_RAW if raw else 0, _p(rgb), _p(rgb8)),
+                   'durf_vis_normals')
+    return rgb, rgb8
+
+
+def vis_sinebow(h, want_float=True, want_u8=False):
+    rgb, rgb8 = _vis_outputs(tuple(h.shape), h.device, want_float, want_u8, None, None)
+    _lib.check(_lib.lib().durf_vis_sinebow(_stream(), h.numel(), _p(_f32(h)), _p(rgb), _p(rgb8)), 'durf_vis_sinebow')
+    return rgb, rgb8
+
+
+def vis_turbo_lut():
+    """the library's built-in colour map (matplotlib's turbo) -> [256,3] float32 numpy array; touches no device"""
+    import numpy as np
+    buf = (C.c_float * 768)()
+    _lib.check(_lib.lib().durf_vis_turbo_lut(C.cast(buf, C.c_void_p)), 'durf_vis_turbo_lut')
+    return np.ctypeslib.as_array(buf).reshape(256, 3).copy()

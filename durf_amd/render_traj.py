@@ -2,14 +2,18 @@
 internal/utils.py:155) and the loop of notebooks/durf_render_traj.ipynb as a command:
 
     python -m durf_amd.render_traj --gin_file configs/waymo.gin --data_dir DATA --train_dir CKPT --traj traj.npz --eval_dir OUT
-                                   [--cam 0] [--disable_box k ...] [--chunk 8192]
+                                   [--cam 0] [--disable_box k ...] [--chunk 8192] [--vis [--vis_near N] [--vis_far F]]
     python -m durf_amd.render_traj --synthetic --eval_dir OUT [--frames 8] [--traj traj.npz]
 
 The checkpoint in --train_dir is restored, the intrinsics (focal, principal point, image size) are those of image --cam of the
 dataset's test split, the half extents of the boxes are one timestep's for every frame, and the cameras and times come from
 --traj (durf_amd.trajectory.load_trajectory: the notebook's npz or a plain {c2w, times} one; fractional times render the
 boxes between two labelled timesteps).  The whole trajectory is ONE
-MipNerfModel.render_trajectory call; OUT/%04d.ppm (binary P6) and OUT/distance.npy [F,h,w] are written.  --synthetic renders
+MipNerfModel.render_trajectory call; OUT/%04d.ppm (binary P6) and OUT/distance.npy [F,h,w] are written.  --vis adds the
+depth pictures of the reference's evaluation block (vis.visualize_suite) for every frame: OUT/depth_%04d.ppm,
+OUT/depth_mod_%04d.ppm and OUT/normals_%04d.ppm, from ONE batched 8-bit durf_amd.vis.visualize_suite call over the
+trajectory's distance and acc planes (--vis_near / --vis_far: the planes of the depth picture; unset, every frame takes its
+own least and greatest depth).  --synthetic renders
 train_boxpose.SyntheticTimestepDataset's scene instead (no data directory; without --train_dir the freshly initialised
 model, without --traj a sweep between the scene's first and last camera), which exercises the command end to end."""
 import argparse
@@ -31,6 +35,9 @@ def build_parser():
     ap.add_argument('--synthetic', action='store_true', help='render the synthetic scene (no data directory needed)')
     ap.add_argument('--objects', type=int, default=3, help='dynamic boxes of the synthetic scene')
     ap.add_argument('--frames', type=int, default=8, help='--synthetic without --traj: frames of the generated sweep')
+    ap.add_argument('--vis', action='store_true', help='also write depth_%%04d.ppm, depth_mod_%%04d.ppm and normals_%%04d.ppm')
+    ap.add_argument('--vis_near', type=float, default=None, help='--vis: near plane of the depth picture (default: per frame, automatic)')
+    ap.add_argument('--vis_far', type=float, default=None, help='--vis: far plane of the depth picture (default: per frame, automatic)')
     return ap
 
 
@@ -81,12 +88,27 @@ def main(argv=None):
         enable = [0 if k in args.disable_box else 1 for k in range(K)]
     cams = trajectory.camera_rows(c2w, focal, (ppx, ppy), int(h), int(w))
     out = model.render_trajectory(variables, cams, times, ext, config.white_bkgd, alpha, near=config.near, far=config.far,
-                                  chunk=args.chunk, box_enable=enable, outputs=('rgb8', 'distance'))
+                                  chunk=args.chunk, box_enable=enable,
+                                  outputs=('rgb8', 'distance', 'acc') if args.vis else ('rgb8', 'distance'))
     os.makedirs(args.eval_dir, exist_ok=True)
     rgb8 = out['rgb8'].cpu().numpy()
     for f in range(rgb8.shape[0]):
         trajectory.write_ppm(os.path.join(args.eval_dir, '%04d.ppm' % f), rgb8[f])
     np.save(os.path.join(args.eval_dir, 'distance.npy'), out['distance'].cpu().numpy())
+    if args.vis:
+        from . import vis
+        shape = (rgb8.shape[0], int(h), int(w))
+        dist, acc = out['distance'].reshape(shape), out['acc'].reshape(shape)
+        if args.vis_near is None and args.vis_far is None:
+            pics = vis.visualize_suite(dist, acc, out8=True)
+        else:
+            pics = dict(depth=vis.visualize_depth(dist, acc, near=args.vis_near, far=args.vis_far, out8=True),
+                        depth_mod=vis.visualize_depth(dist, acc, modulus=0.1, out8=True),
+                        depth_normals=vis.visualize_normals(dist, acc, out8=True))
+        for name, key in (('depth', 'depth'), ('depth_mod', 'depth_mod'), ('normals', 'depth_normals')):
+            frames = pics[key].cpu().numpy()
+            for f in range(frames.shape[0]):
+                trajectory.write_ppm(os.path.join(args.eval_dir, '%s_%04d.ppm' % (name, f)), frames[f])
     print('render_traj: %d frames of %d x %d written to %s' % (rgb8.shape[0], int(h), int(w), args.eval_dir))
     return 0
 

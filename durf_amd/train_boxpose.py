@@ -771,10 +771,12 @@ def make_render_fn(model, config, variables, one_call=None):
     return render_fn
 
 
-def evaluate(model, config, variables, test_case, alpha, chunk=8192, rng=0, layers=False):
+def evaluate(model, config, variables, test_case, alpha, chunk=8192, rng=0, layers=False, vis=False):
     """One test image (train_boxpose.py:535-563): render, PSNR, SSIM.  -> dict(psnr, ssim, rgb, distance, acc, rays)
     layers=True (one device, supports_one_call): the image through MipNerfModel.render_layers, and the dict also carries
-    instance, bg_rgb / bg_distance / bg_acc and obj_rgba"""
+    instance, bg_rgb / bg_distance / bg_acc and obj_rgba
+    vis=True: the dict also carries vis = vis.visualize_suite(distance, acc) (:558): the pictures depth, depth_mod and
+    depth_normals, [h,w,3] on the device"""
     from . import metrics
     extra = {}
     if layers:
@@ -793,6 +795,9 @@ def evaluate(model, config, variables, test_case, alpha, chunk=8192, rng=0, laye
     gt = test_case['pixels'][..., :3]
     psnr = dmath.mse_to_psnr(((rgb - gt) ** 2).mean())                                   # :562
     ssim = metrics.compute_ssim(rgb, gt, 1.0) if rgb.is_cuda else None                   # :563
+    if vis:
+        from . import vis as dvis
+        extra['vis'] = dvis.visualize_suite(dist_, acc)                                  # :558
     return dict(psnr=psnr, ssim=ssim, rgb=rgb, distance=dist_, acc=acc, rays=rgb.shape[0] * rgb.shape[1], **extra)
 
 

@@ -328,4 +328,22 @@ def bind(path='durf_amd/libdurf_hip.so'):
     L.durf_ssim.restype = i32
     L.durf_ssim.argtypes = [vp, i32, i32, i32, vp, vp, f32, i32, vp, f32, f32, vp, vp, vp]
     #   (stream, H, W, C, img0, img1, max_val, filter_size, filt_dev, k1, k2, ssim_map, scratch, ssim_mean)
+    L.durf_vis_scratch_bytes.restype = u64
+    L.durf_vis_scratch_bytes.argtypes = [i32, i32, i32]
+    #   (F, H, W)
+    L.durf_vis_stats.restype = i32
+    L.durf_vis_stats.argtypes = [vp, i32, i32, i32, vp, vp, vp, u64]
+    #   (stream, F, H, W, depth, stats, scratch, scratch_bytes)
+    L.durf_vis_depth.restype = i32
+    L.durf_vis_depth.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, f32, vp, vp, vp]
+    #   (stream, F, H, W, depth, acc, range, range_stride, curve, modulus, lut, rgb, rgb8)
+    L.durf_vis_normals.restype = i32
+    L.durf_vis_normals.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp]
+    #   (stream, F, H, W, depth, acc, scale, scale_stride, flags, rgb, rgb8)
+    L.durf_vis_sinebow.restype = i32
+    L.durf_vis_sinebow.argtypes = [vp, u64, vp, vp, vp]
+    #   (stream, n, h, rgb, rgb8)
+    L.durf_vis_turbo_lut.restype = i32
+    L.durf_vis_turbo_lut.argtypes = [vp]
+    #   (lut_host)
     return L

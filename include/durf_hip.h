@@ -866,6 +866,47 @@ int durf_ssim(void* stream, int H, int W, int C, const float* img0, const float*
               int filter_size, const float* filt_dev, float k1, float k2, float* ssim_map, float* scratch,
               float* ssim_mean);
 
+/* ---- depth visualisations (internal/vis.py; train_boxpose.py:558 vis.visualize_suite) ------------
+ * F frames of H x W at once: depth [F,H,W] fp32 row-major, acc [F,H,W] nullable (= ones).  Outputs rgb [F,H,W,3]
+ * fp32 and / or rgb8 [F,H,W,3] uint8 = rintf(clamp(rgb, 0, 1) * 255) (NaN -> 0), either nullable (not both): an output
+ * that is not asked for is not written anywhere.  No call synchronises or copies to the host.
+ *
+ * durf_vis_stats: per frame DURF_VIS_STATS_FLOATS floats {near_auto, far_auto, normal_scale, count, var x, var y,
+ * var depth, mean depth} over the non-NaN pixels.  near_auto / far_auto are visualize_depth's automatic planes for
+ * ignore_frac = 0 (vis.py:77-91; acc plays no part there): first / last element of the plane sorted ascending with NaNs
+ * last, - / + FLT_EPSILON -- so far_auto is NaN as soon as one depth is NaN, as in the reference.  normal_scale =
+ * sqrt(((var x + var y) / 2) / var depth) (vis.py:116-122), every variance two-pass (mean, then mean squared deviation):
+ * a constant plane has var depth == 0 exactly.  fp64 sums in a fixed order (bit-reproducible); scratch:
+ * durf_vis_scratch_bytes bytes, 8-byte aligned.
+ *
+ * durf_vis_depth (vis.py:45-111): range = near, far (uncurved) at range[f * range_stride + {0, 1}] -- the stats record
+ * with range_stride = DURF_VIS_STATS_FLOATS, or planes the caller wrote.  curve applies to depth, near and far.
+ * modulus == 0: value = nan_to_num(clip((d - min(n, f)) / |f - n|, 0, 1)), colour = row min(int(value * 256), 255) of lut
+ * (256 x 3 device floats; NULL: matplotlib's turbo).  modulus > 0: value = mod(d, modulus) / modulus (floored), colour =
+ * sinebow(value) (lut given: its row; a NaN value is black), range is not read.  Then colour * a + (1 - a) with
+ * a = isnan(depth) ? 0 : acc.
+ *
+ * durf_vis_normals (vis.py:114-132, 34-42): s = scale[f * scale_stride] * depth (scale NULL: 1), dx / dy its 3 x 3 true
+ * convolutions with zero padding (blur (1, 2, 1) / 4 across, edge (-1, 0, 1) / 2 along; the zero taps are multiplied too, so a
+ * NaN or inf in the neighbourhood reaches the pixel), n = (dx, dy, 1) / sqrt(1 + dx^2 + dy^2), colour = isnan(n) +
+ * nan_to_num((n + 1) / 2), then colour * acc + (1 - acc) when acc is given (acc as it is, no NaN rule).
+ * DURF_VIS_NORMALS_RAW: the output is n itself (depth_to_normals), acc is not read.
+ *
+ * durf_vis_sinebow: vis.sinebow of n values.  durf_vis_turbo_lut: the built-in table, 256 x 3 floats, to a HOST buffer. */
+#define DURF_VIS_CURVE_NEGLOG 0    /* -log(x + eps): the reference's default */
+#define DURF_VIS_CURVE_IDENTITY 1
+#define DURF_VIS_CURVE_INVERSE 2   /* 1 / (x + eps) */
+#define DURF_VIS_STATS_FLOATS 8
+#define DURF_VIS_NORMALS_RAW 1
+size_t durf_vis_scratch_bytes(int F, int H, int W);
+int durf_vis_stats(void* stream, int F, int H, int W, const float* depth, float* stats, void* scratch, size_t scratch_bytes);
+int durf_vis_depth(void* stream, int F, int H, int W, const float* depth, const float* acc, const float* range, int range_stride,
+                   int curve, float modulus, const float* lut, float* rgb, uint8_t* rgb8);
+int durf_vis_normals(void* stream, int F, int H, int W, const float* depth, const float* acc, const float* scale, int scale_stride,
+                     int flags, float* rgb, uint8_t* rgb8);
+int durf_vis_sinebow(void* stream, size_t n, const float* h, float* rgb, uint8_t* rgb8);
+int durf_vis_turbo_lut(void* lut_host);
+
 #ifdef __cplusplus
 }
 #endif
