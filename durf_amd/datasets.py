@@ -251,6 +251,31 @@ class Waymo:
                     init=self._dev(tb['init']), ext=self._dev(tb['ext'][t - 1]), ts=t - 1,
                     target=self._dev(tb['target'][t - 1]), box=self._dev(tb['box'][t - 1]), can=self._dev(tb['can']))
 
+    def eval_set(self):
+        """The split as data, for train_boxpose.evaluate_set: every image in the order next() yields them from a fresh loader
+        -> dict(cams [F,17] host rows (raygen.camera_row), ts [F] host ints (what _next_test puts into test_case['ts']),
+        pixels / depth / sky: lists of [H,W,.] views of the resident timestep data, ext: list of the [K,3] half extents of each
+        frame's timestep, init [T,K,6]).  No rays are made and the iterator is not advanced."""
+        tb = self.tables()
+        cams, ts, pixels, depth, sky, ext = [], [], [], [], [], []
+        slot = {int(t): i for i, t in reversed(list(enumerate(self.ts_values)))}    # timestep -> its (first) ts_data entry
+        offs = {}                                         # timestep -> pixels of its images seen so far (_next_test's `off`)
+        for idx in range(self.n_examples):
+            t = int(self.timesteps[idx])
+            td = self.ts_data[slot[t]]
+            H, W = int(self.h[idx]), int(self.w[idx])
+            off = offs.get(t, 0)
+            offs[t] = off + H * W
+            img = lambda x, off=off, H=H, W=W: x[off:off + H * W].reshape(H, W, -1)
+            cams.append(raygen.camera_row(self.camtoworlds[idx], self.focal[idx], self.principal_point[idx], H, W))
+            ts.append(t - 1)
+            pixels.append(img(td.images))
+            depth.append(img(td.depth))
+            sky.append(img(td.sky))
+            ext.append(self._dev(tb['ext'][t - 1]))           # (uploaded once per timestep: _dev keeps the device copy)
+        return dict(cams=np.stack(cams), ts=np.asarray(ts, np.int64), pixels=pixels, depth=depth, sky=sky, ext=ext,
+                    init=self._dev(tb['init']))
+
     def peek(self):
         if self._peek is None:
             self._peek = self._next_train() if self.split == 'train' else self._next_test()

@@ -31,3 +31,23 @@ def compute_ssim(img0, img1, max_val, filter_size=11, filter_sigma=1.5, k1=0.01,
                            float(max_val), filter_size, _p(fd), float(k1), float(k2), _p(smap), _p(scratch), _p(out)),
                'durf_ssim')
     return smap if return_map else out
+
+
+def evaluate_frames(rgb, gt_rgb, distance=None, gt_depth=None, obj_mask=None):
+    """The evaluation loop's numbers for F frames at once (ops.eval_frames; include/durf_hip.h durf_eval_frames): rgb, gt_rgb
+    [F,H,W,3] or [H,W,3]; distance with gt_depth (the LIDAR plane, 0 = no return) and obj_mask [F,H,W] / [H,W] or None, any
+    float dtype or layout -> dict of [F] device tensors keyed by ops.EVAL_FIELDS.  Nothing is read back."""
+    single = rgb.dim() == 3
+
+    def frames(t, tail):
+        if t is None:
+            return None
+        if single:
+            t = t[None]
+        return t.reshape(t.shape[:3] + tail).to(torch.float32).contiguous()
+    # bound to locals for the call, as in compute_ssim: a temporary's block could be handed to the next conversion
+    a, b = frames(rgb, (3,)), frames(gt_rgb, (3,))
+    d, g, m = frames(distance, ()), frames(gt_depth, ()), frames(obj_mask, ())
+    from . import ops
+    rec, fields = ops.eval_frames(a, b, d, g, m)
+    return {name: rec[:, i] for i, name in enumerate(fields)}

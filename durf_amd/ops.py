@@ -1703,3 +1703,34 @@ def vis_turbo_lut():
     buf = (C.c_float * 768)()
     _lib.check(_lib.lib().durf_vis_turbo_lut(C.cast(buf, C.c_void_p)), 'durf_vis_turbo_lut')
     return np.ctypeslib.as_array(buf).reshape(256, 3).copy()
+
+
+# ---- evaluation metrics of F frames (csrc/metrics.hip; include/durf_hip.h durf_eval_frames) --------------------------------
+EVAL_FLOATS = 10                                         # DURF_EVAL_FLOATS
+EVAL_FIELDS = ('mse', 'psnr', 'ssim', 'obj_count', 'obj_mse', 'obj_psnr', 'depth_count', 'depth_abs', 'depth_rmse',
+               'nonfinite')                              # DURF_EVAL_* in index order
+EVAL_INDEX = {name: i for i, name in enumerate(EVAL_FIELDS)}
+
+
+def eval_frames(rgb, gt_rgb, distance=None, gt_depth=None, obj_mask=None):
+    """rgb, gt_rgb [F,H,W,3]; distance with gt_depth [F,H,W] or neither; obj_mask [F,H,W] or None -> ([F, EVAL_FLOATS] device
+    record, EVAL_FIELDS): durf_eval_frames, two launches for any F, no read-back (the fields of a plane that is None are NaN,
+    its count 0)"""
+    if rgb.dim() != 4 or rgb.shape[-1] != 3 or gt_rgb.shape != rgb.shape:
+        raise ValueError('rgb and gt_rgb: [F,H,W,3], got %s and %s' % (tuple(rgb.shape), tuple(gt_rgb.shape)))
+    F, H, W = rgb.shape[:3]
+    if (distance is None) != (gt_depth is None):
+        raise ValueError('distance and gt_depth are given together or not at all')
+    for name, t in (('distance', distance), ('gt_depth', gt_depth), ('obj_mask', obj_mask)):
+        if t is not None and tuple(t.shape) != (F, H, W):
+            raise ValueError('%s: %s against frames of %s' % (name, tuple(t.shape), (F, H, W)))
+    L = _lib.lib()
+    dev = rgb.device
+    out = torch.empty(F, EVAL_FLOATS, device=dev)
+    nbytes = int(L.durf_eval_scratch_bytes(F, H, W))
+    scratch = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+    opt = lambda t: None if t is None else _p(_f32(t))
+    with _Timed('eval_frames'):
+        _lib.check(L.durf_eval_frames(_stream(), F, H, W, _p(_f32(rgb)), _p(_f32(gt_rgb)), opt(distance), opt(gt_depth),
+                                      opt(obj_mask), _p(out), _p(scratch), nbytes), 'durf_eval_frames')
+    return out, EVAL_FIELDS

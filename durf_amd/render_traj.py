@@ -21,19 +21,25 @@ import os
 import sys
 
 
-def build_parser():
-    ap = argparse.ArgumentParser(prog='python -m durf_amd.render_traj', description=__doc__.split('\n\n')[0])
+def add_scene_arguments(ap):
+    """the arguments that name a trained scene and where to write: shared with python -m durf_amd.eval_set"""
     ap.add_argument('--gin_file', action='append', default=[])
     ap.add_argument('--gin_param', action='append', default=[])
     ap.add_argument('--train_dir', default=None, help='checkpoint directory (required unless --synthetic)')
     ap.add_argument('--data_dir', default=None, help='dataset directory (loaders: durf_amd.datasets)')
-    ap.add_argument('--traj', default=None, help='trajectory npz: the notebook\'s (c2w, ts) pairs or {c2w, times}')
     ap.add_argument('--eval_dir', required=True, help='where to render traj to')
-    ap.add_argument('--cam', type=int, default=0, help='index into the dataset\'s image list: the frames use that image\'s intrinsics')
-    ap.add_argument('--disable_box', type=int, action='append', default=[], help='box index to switch off (repeatable)')
     ap.add_argument('--chunk', type=int, default=8192)
     ap.add_argument('--synthetic', action='store_true', help='render the synthetic scene (no data directory needed)')
     ap.add_argument('--objects', type=int, default=3, help='dynamic boxes of the synthetic scene')
+    return ap
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(prog='python -m durf_amd.render_traj', description=__doc__.split('\n\n')[0])
+    add_scene_arguments(ap)
+    ap.add_argument('--traj', default=None, help='trajectory npz: the notebook\'s (c2w, ts) pairs or {c2w, times}')
+    ap.add_argument('--cam', type=int, default=0, help='index into the dataset\'s image list: the frames use that image\'s intrinsics')
+    ap.add_argument('--disable_box', type=int, action='append', default=[], help='box index to switch off (repeatable)')
     ap.add_argument('--frames', type=int, default=8, help='--synthetic without --traj: frames of the generated sweep')
     ap.add_argument('--vis', action='store_true', help='also write depth_%%04d.ppm, depth_mod_%%04d.ppm and normals_%%04d.ppm')
     ap.add_argument('--vis_near', type=float, default=None, help='--vis: near plane of the depth picture (default: per frame, automatic)')
@@ -41,26 +47,55 @@ def build_parser():
     return ap
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
-    import numpy as np
+def open_scene(args, split='test'):
+    """-> device, config and the `split` dataset the scene arguments name (the synthetic scene with --synthetic)"""
     import torch
-    from . import checkpoints, obbpose_model as om, train_boxpose, trajectory, utils
-    if not args.synthetic and (args.data_dir is None or args.train_dir is None or args.traj is None):
-        raise SystemExit('render_traj: --data_dir, --train_dir and --traj are required (or --synthetic)')
+    from . import train_boxpose, utils
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(dev)
     utils.clear_gin()
     config = utils.load_config(args.gin_file, args.gin_param)
     if args.synthetic:
-        dataset = train_boxpose.SyntheticTimestepDataset(config, K=args.objects, device=dev, split='test')
+        dataset = train_boxpose.SyntheticTimestepDataset(config, K=args.objects, device=dev, split=split)
+    else:
+        from . import datasets
+        dataset = datasets.get_dataset(split, args.data_dir, config, device=dev)
+    return dev, config, dataset
+
+
+def restore_model(args, config, dataset, dev):
+    """the scene's model with the checkpoint of --train_dir restored (none: freshly initialised) -> (model, variables, alpha:
+    the frequency schedule's value at the checkpoint's step)"""
+    from . import checkpoints, obbpose_model as om, train_boxpose
+    model, variables = om.construct_mipnerf(20200823, dataset.peek(), device=dev)
+    state = train_boxpose.create_train_state(variables)
+    if args.train_dir is not None:
+        state = checkpoints.restore_checkpoint(args.train_dir, state)
+    alpha = train_boxpose.make_schedules(config)[2](max(int(state.step), 1))
+    return model, state.variables, alpha
+
+
+def write_pictures(eval_dir, pics):
+    """pics {depth, depth_mod, depth_normals}: [F,h,w,3] uint8 host arrays -> depth_%04d.ppm, depth_mod_%04d.ppm, normals_%04d.ppm"""
+    from . import trajectory
+    for name, key in (('depth', 'depth'), ('depth_mod', 'depth_mod'), ('normals', 'depth_normals')):
+        for f in range(len(pics[key])):
+            trajectory.write_ppm(os.path.join(eval_dir, '%s_%04d.ppm' % (name, f)), pics[key][f])
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    import numpy as np
+    from . import trajectory
+    if not args.synthetic and (args.data_dir is None or args.train_dir is None or args.traj is None):
+        raise SystemExit('render_traj: --data_dir, --train_dir and --traj are required (or --synthetic)')
+    dev, config, dataset = open_scene(args)
+    if args.synthetic:
         cam_rows = dataset.ts_data[0].cams
         ext = dataset.ext
         key_c2w = [dataset.ts_data[0].cams[0, :12].reshape(3, 4), dataset.ts_data[-1].cams[-1, :12].reshape(3, 4)]
         key_t = [0.0, float(dataset.T - 1)]
     else:
-        from . import datasets
-        dataset = datasets.get_dataset('test', args.data_dir, config, device=dev)
         cam_rows = np.concatenate([np.asarray(dataset.camtoworlds, np.float32).reshape(-1, 12),
                                    np.stack([dataset.focal, dataset.principal_point[:, 0], dataset.principal_point[:, 1],
                                              dataset.h, dataset.w], -1).astype(np.float32)], -1)
@@ -69,12 +104,7 @@ def main(argv=None):
     if not 0 <= args.cam < len(cam_rows):
         raise SystemExit('render_traj: --cam %d of %d cameras' % (args.cam, len(cam_rows)))
     focal, ppx, ppy, h, w = [float(x) for x in cam_rows[args.cam][12:]]
-    model, variables = om.construct_mipnerf(20200823, dataset.peek(), device=dev)
-    state = train_boxpose.create_train_state(variables)
-    if args.train_dir is not None:
-        state = checkpoints.restore_checkpoint(args.train_dir, state)
-    variables = state.variables
-    alpha = train_boxpose.make_schedules(config)[2](max(int(state.step), 1))
+    model, variables, alpha = restore_model(args, config, dataset, dev)
     if args.traj is not None:
         c2w, times = trajectory.load_trajectory(args.traj)
     else:
@@ -105,10 +135,7 @@ def main(argv=None):
             pics = dict(depth=vis.visualize_depth(dist, acc, near=args.vis_near, far=args.vis_far, out8=True),
                         depth_mod=vis.visualize_depth(dist, acc, modulus=0.1, out8=True),
                         depth_normals=vis.visualize_normals(dist, acc, out8=True))
-        for name, key in (('depth', 'depth'), ('depth_mod', 'depth_mod'), ('normals', 'depth_normals')):
-            frames = pics[key].cpu().numpy()
-            for f in range(frames.shape[0]):
-                trajectory.write_ppm(os.path.join(args.eval_dir, '%s_%04d.ppm' % (name, f)), frames[f])
+        write_pictures(args.eval_dir, {k: v.cpu().numpy() for k, v in pics.items()})
     print('render_traj: %d frames of %d x %d written to %s' % (rgb8.shape[0], int(h), int(w), args.eval_dir))
     return 0
 

@@ -801,6 +801,94 @@ def evaluate(model, config, variables, test_case, alpha, chunk=8192, rng=0, laye
     return dict(psnr=psnr, ssim=ssim, rgb=rgb, distance=dist_, acc=acc, rays=rgb.shape[0] * rgb.shape[1], **extra)
 
 
+def _box_hit_masks(variables, config, cams, ts, ext):
+    """[F,h,w] float planes, 1 where the pixel's ray hits any box under box_centers[ts]: the training step's dyn_mask for a
+    full image (camera rays, then the box test of ops.ray_setup)"""
+    from . import raygen
+    dev = variables.flat.device
+    boxes = variables['params']['box_centers']
+    planes = []
+    for cam, t, e in zip(cams, ts, ext):
+        rays = raygen.camera_rays(cam, config.near, config.far, device=dev)
+        h, w = rays.origins.shape[:2]
+        hit = ops.ray_setup(rays.origins.reshape(-1, 3), rays.directions.reshape(-1, 3), boxes[int(t)].contiguous(),
+                            e.reshape(-1, 3).contiguous())[2]
+        planes.append((hit.sum(dim=-1) > 0).to(torch.float32).reshape(h, w))
+    return torch.stack(planes)
+
+
+def evaluate_set(model, config, variables, dataset, alpha, chunk=8192, obj_mask=None, vis=False, frames=False):
+    """A whole split in one pass (notebooks/render_eval_durf.ipynb; train_boxpose.py:535-575 over every image): the frames of
+    dataset.eval_set() grouped by (h, w, ts), per group ONE MipNerfModel.render_trajectory call at the integer time ts -- the
+    rays are made per chunk on the device, bit-identical to evaluate()'s render_image_one_call -- and ONE ops.eval_frames call
+    against the stacked ground truth.  One device, supports_one_call.
+    obj_mask: None, a list of [h,w] planes (one per frame), or 'boxes': every frame's any-box-hit mask (_box_hit_masks).
+    -> dict(per_frame [F, 10] device tensor in the dataset's order, fields = ops.EVAL_FIELDS, mean = {psnr, ssim: over the
+    frames, as the notebook's psnr.mean(); depth_abs, depth_rmse, obj_psnr: over the frames that have a count} of 0-d device
+    tensors, frames = F, rays = the rays rendered; frames=True: rgb8, a list of [h,w,3] uint8 frames; vis=True: vis, a list
+    of {depth, depth_mod, depth_normals} uint8 pictures (one batched vis.visualize_suite per group)).  Nothing is read back:
+    the caller decides when."""
+    if _dist() is not None or not model.supports_one_call(variables):
+        raise NotImplementedError('evaluate_set renders on one device through durf_render_trajectory (supports_one_call)')
+    es = dataset.eval_set()
+    cams, ts = es['cams'], [int(t) for t in es['ts']]
+    F = len(ts)
+    dev = variables.flat.device
+    if isinstance(obj_mask, str):
+        if obj_mask != 'boxes':
+            raise ValueError("obj_mask: None, a list of [h,w] planes or 'boxes', got %r" % obj_mask)
+    elif obj_mask is not None and len(obj_mask) != F:
+        raise ValueError('obj_mask: %d planes for %d frames' % (len(obj_mask), F))
+    groups = {}
+    for f in range(F):
+        groups.setdefault((int(cams[f][15]), int(cams[f][16]), ts[f]), []).append(f)
+    per_frame = torch.empty(F, ops.EVAL_FLOATS, device=dev)
+    rgb8, pics = [None] * F, [None] * F
+    rays = 0
+    for (h, w, t), members in groups.items():
+        ext = es['ext'][members[0]]
+        out = model.render_trajectory(variables, cams[members], [float(t)] * len(members), ext, config.white_bkgd, alpha,
+                                      near=config.near, far=config.far, chunk=chunk,
+                                      outputs=('rgb', 'distance', 'acc') + (('rgb8',) if frames else ()))
+        gt = torch.stack([es['pixels'][f][..., :3] for f in members]).to(torch.float32).contiguous()
+        gd = torch.stack([es['depth'][f].reshape(h, w) for f in members]).to(torch.float32).contiguous()
+        if obj_mask is None:
+            mask = None
+        elif isinstance(obj_mask, str):
+            mask = (_box_hit_masks(variables, config, cams[members], [t] * len(members), [ext] * len(members))
+                    if variables.layout.K else torch.zeros(len(members), h, w, device=dev))
+        else:
+            mask = torch.stack([obj_mask[f].reshape(h, w) for f in members]).to(device=dev, dtype=torch.float32).contiguous()
+        rec = ops.eval_frames(out['rgb'], gt, out['distance'], gd, mask)[0]
+        if members == list(range(members[0], members[0] + len(members))):
+            per_frame[members[0]:members[0] + len(members)] = rec
+        else:                                     # (device-to-device rows: an index tensor would be a host upload)
+            for i, f in enumerate(members):
+                per_frame[f] = rec[i]
+        rays += len(members) * h * w
+        if frames:
+            for i, f in enumerate(members):
+                rgb8[f] = out['rgb8'][i]
+        if vis:
+            from . import vis as dvis
+            suite = dvis.visualize_suite(out['distance'], out['acc'], out8=True)
+            for i, f in enumerate(members):
+                pics[f] = {k: v[i] for k, v in suite.items()}
+    col = lambda name: per_frame[:, ops.EVAL_INDEX[name]]
+
+    def mean_where(name, count):
+        have = (col(count) > 0).to(torch.float32)
+        return torch.where(have > 0, col(name), torch.zeros_like(have)).sum() / have.sum()           # no frame has a count: 0 / 0
+    mean = dict(psnr=col('psnr').mean(), ssim=col('ssim').mean(), depth_abs=mean_where('depth_abs', 'depth_count'),
+                depth_rmse=mean_where('depth_rmse', 'depth_count'), obj_psnr=mean_where('obj_psnr', 'obj_count'))
+    res = dict(per_frame=per_frame, fields=ops.EVAL_FIELDS, mean=mean, frames=F, rays=rays)
+    if frames:
+        res['rgb8'] = rgb8
+    if vis:
+        res['vis'] = pics
+    return res
+
+
 def train_loop(model, config, state, dataset, test_dataset=None, train_dir=None, render_every=0, chunk=8192,
                rng=20200823, step_fn=None, log=print, world=1, rank=0, keep=100):
     """The body of the reference's main() (train_boxpose.py:416-580) around `train_step`.
@@ -952,6 +1040,27 @@ class SyntheticTimestepDataset:
         img = lambda x: x[:n].reshape(self.H, self.W, -1)
         return dict(rays=utils.namedtuple_map(img, rays), pixels=img(px), depth=img(dp), sky=img(sk), init=self.init,
                     ext=self.ext, ts=ts)
+
+    def eval_set(self):
+        """The scene as an evaluation set (datasets.Waymo.eval_set's layout): every camera of every timestep, timestep-major
+        -- next() draws one timestep at random and yields its first camera, frame ts * n_cams of this set -> dict(cams [F,17],
+        ts [F] ints, pixels / depth / sky lists of [H,W,.] views of the resident data, ext per frame, init).  No rays are made
+        and the generator of next() is not advanced."""
+        import numpy as np
+        from . import raygen
+        n = self.H * self.W
+        cams, ts, pixels, depth, sky = [], [], [], [], []
+        for t, td in enumerate(self.ts_data):
+            for c in range(self.n_cams):
+                row = td.cams[c]
+                img = lambda x: x[c * n:(c + 1) * n].reshape(self.H, self.W, -1)
+                cams.append(raygen.camera_row(row[:12].reshape(3, 4), row[12], row[13:15], row[15], row[16]))
+                ts.append(t)
+                pixels.append(img(td.images))
+                depth.append(img(td.depth))
+                sky.append(img(td.sky))
+        return dict(cams=np.stack(cams), ts=np.asarray(ts, np.int64), pixels=pixels, depth=depth, sky=sky,
+                    ext=[self.ext] * len(ts), init=self.init)
 
     def peek(self):
         if self._peek is None:

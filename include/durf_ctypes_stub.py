@@ -328,6 +328,12 @@ def bind(path='durf_amd/libdurf_hip.so'):
     L.durf_ssim.restype = i32
     L.durf_ssim.argtypes = [vp, i32, i32, i32, vp, vp, f32, i32, vp, f32, f32, vp, vp, vp]
     #   (stream, H, W, C, img0, img1, max_val, filter_size, filt_dev, k1, k2, ssim_map, scratch, ssim_mean)
+    L.durf_eval_scratch_bytes.restype = u64
+    L.durf_eval_scratch_bytes.argtypes = [i32, i32, i32]
+    #   (F, H, W)
+    L.durf_eval_frames.restype = i32
+    L.durf_eval_frames.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, u64]
+    #   (stream, F, H, W, rgb, gt_rgb, distance, gt_depth, obj_mask, metrics, scratch, scratch_bytes)
     L.durf_vis_scratch_bytes.restype = u64
     L.durf_vis_scratch_bytes.argtypes = [i32, i32, i32]
     #   (F, H, W)

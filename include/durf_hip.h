@@ -865,6 +865,39 @@ size_t durf_ssim_scratch_floats(int H, int W, int C, int filter_size);
 int durf_ssim(void* stream, int H, int W, int C, const float* img0, const float* img1, float max_val,
               int filter_size, const float* filt_dev, float k1, float k2, float* ssim_map, float* scratch,
               float* ssim_mean);
+/* The evaluation loop's metrics for F frames at once (notebooks/render_eval_durf.ipynb; train_boxpose.py:535-575): per frame
+ * DURF_EVAL_FLOATS floats, metrics[f * DURF_EVAL_FLOATS + DURF_EVAL_*]:
+ *   MSE         mean of (rgb - gt_rgb)^2 over H * W * 3, nothing clipped (:562);  PSNR = -10 / ln 10 * ln(MSE) (math.py:49-51)
+ *   SSIM        math.compute_ssim(rgb, gt_rgb, max_val = 1) with its defaults (window 11, sigma 1.5, k1 0.01, k2 0.03, the
+ *               'valid' region, blur along W then along H, the clamps of math.py:126-129), mean over (H - 10)(W - 10) * 3
+ *   OBJ_COUNT   sum of obj_mask;  OBJ_MSE = sum(obj_mask * (rgb - gt_rgb)^2) / OBJ_COUNT, the sum over the three channels too
+ *               (the training step's obj_losses, :192; 0 / 0 = NaN as there);  OBJ_PSNR of OBJ_MSE
+ *   DEPTH_COUNT pixels with gt_depth > 0 (the LIDAR returns);  DEPTH_ABS = sum over them of |distance - gt_depth| /
+ *               max(DEPTH_COUNT, 1);  DEPTH_RMSE = sqrt(sum over them of (distance - gt_depth)^2 / max(DEPTH_COUNT, 1)) (:174-175)
+ *   NONFINITE   elements of rgb that are NaN or inf
+ * distance and gt_depth come together or not at all; the fields of a plane that is NULL are NaN and its count 0.  A NaN is not
+ * treated specially: it makes MSE, PSNR and SSIM of its own frame NaN (NONFINITE says why) and touches no other frame.
+ * Two launches for any F, nothing synchronises or reads back: workgroups of 32 x 32 pixels write fp64 partial sums to scratch
+ * (the differences and squares of the error sums are fp64, the SSIM blur fp32), one workgroup per frame adds them in tile
+ * order: every order is fixed, the record is bit-reproducible and does not depend on F.  scratch: durf_eval_scratch_bytes
+ * bytes, 8-byte aligned.  H, W >= 11. */
+#define DURF_EVAL_FLOATS 10
+#define DURF_EVAL_MSE 0
+#define DURF_EVAL_PSNR 1
+#define DURF_EVAL_SSIM 2
+#define DURF_EVAL_OBJ_COUNT 3
+#define DURF_EVAL_OBJ_MSE 4
+#define DURF_EVAL_OBJ_PSNR 5
+#define DURF_EVAL_DEPTH_COUNT 6
+#define DURF_EVAL_DEPTH_ABS 7
+#define DURF_EVAL_DEPTH_RMSE 8
+#define DURF_EVAL_NONFINITE 9
+size_t durf_eval_scratch_bytes(int F, int H, int W);
+int durf_eval_frames(void* stream, int F, int H, int W,
+                     const float* rgb      /* [F,H,W,3] */, const float* gt_rgb /* [F,H,W,3] */,
+                     const float* distance /* [F,H,W] nullable */, const float* gt_depth /* [F,H,W] nullable, with distance */,
+                     const float* obj_mask /* [F,H,W] nullable */,
+                     float* metrics /* [F, DURF_EVAL_FLOATS] */, void* scratch, size_t scratch_bytes);
 
 /* ---- depth visualisations (internal/vis.py; train_boxpose.py:558 vis.visualize_suite) ------------
  * F frames of H x W at once: depth [F,H,W] fp32 row-major, acc [F,H,W] nullable (= ones).  Outputs rgb [F,H,W,3]
