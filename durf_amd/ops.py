@@ -803,12 +803,18 @@ def stats_views(out, L):
 
 
 def mlp_bwd(width, rows, N, draw, wpack_bwd, relu_mask, ray_idx=None, count=None, want_d_enc=False,
-            tail_idx=None, tail_count=None, draw_ray_sum=None):
-    """-> dz (same layout as the stash), dz_out tile [rows,16][, d_enc [rows,64] fp32]"""
+            tail_idx=None, tail_count=None, draw_ray_sum=None, dz=None, dz_out=None, d_enc=None):
+    """-> dz (same layout as the stash), dz_out tile [rows,16][, d_enc [rows,64] fp32]
+    dz / dz_out / d_enc: the caller's buffers instead of fresh ones (as mlp_fwd's raw)"""
     dev = draw.device
-    dz = torch.empty(mlp_stash_bytes(width, rows), dtype=torch.uint8, device=dev)
-    dz_out = torch.empty(tile_rows(rows), 16, dtype=torch.bfloat16, device=dev)
-    d_enc = torch.zeros(rows, ENC_DIM, device=dev) if want_d_enc else None
+    if dz is None:
+        dz = torch.empty(mlp_stash_bytes(width, rows), dtype=torch.uint8, device=dev)
+    if dz_out is None:
+        dz_out = torch.empty(tile_rows(rows), 16, dtype=torch.bfloat16, device=dev)
+    if not want_d_enc:
+        d_enc = None
+    elif d_enc is None:
+        d_enc = torch.zeros(rows, ENC_DIM, device=dev)
     with _Timed('mlp_bwd_%d' % width):
         _lib.check(_lib.lib().durf_mlp_bwd(_stream(), width, rows, N, _p(_f32(draw)), _p(ray_idx), _p(count),
                                            _p(wpack_bwd), _p(relu_mask), _p(dz), _p(dz_out), _p(d_enc),
@@ -817,8 +823,9 @@ def mlp_bwd(width, rows, N, draw, wpack_bwd, relu_mask, ray_idx=None, count=None
     return (dz, dz_out, d_enc) if want_d_enc else (dz, dz_out)
 
 
-def expand_view(rows, N, view_bf16, ray_idx=None, count=None, tail_idx=None, tail_count=None):
-    out = torch.empty(tile_rows(rows), VIEW_DIM, dtype=torch.bfloat16, device=view_bf16.device)
+def expand_view(rows, N, view_bf16, ray_idx=None, count=None, tail_idx=None, tail_count=None, out=None):
+    if out is None:
+        out = torch.empty(tile_rows(rows), VIEW_DIM, dtype=torch.bfloat16, device=view_bf16.device)
     _lib.check(_lib.lib().durf_expand_view(_stream(), rows, N, _p(view_bf16), _p(ray_idx), _p(count),
                                            _p(out), _p(tail_idx), _p(tail_count)), 'durf_expand_view')
     return out
