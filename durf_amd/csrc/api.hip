@@ -47,6 +47,8 @@ int* durf::next_ticket() {
 extern "C" {
 int durf_dispatch_seen(void) { return (int)g_dispatch.load(std::memory_order_relaxed); }
 int durf_dispatch_reset(void) { g_dispatch.store(0u, std::memory_order_relaxed); return 0; }
+unsigned durf_step_policy(size_t rows) { return durf::step_policy(rows).bits(); }
+size_t durf_overlap_min_rows(void) { return DURF_OVERLAP_MIN_ROWS; }
 const char* durf_last_error(void) { return g_err; }
 int durf_version(void) { return 41; }      // bump with every kernel change: bench.py quotes PMC traffic per version
 }

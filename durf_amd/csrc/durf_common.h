@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <stdio.h>
 #include "../../include/durf_hip.h"
+#include "policy.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -235,8 +236,6 @@ int launch_pack(void* stream, int width, int in_dim, int K, const float* params,
 int launch_encode_obj(void* stream, int K, int max_rays, int N, const int32_t* idx, const int32_t* count,
                       const float* t_vals, const float* origins_s, const float* dirs_s, const float* radii,
                       const float* barf_w, int flags, void* out_tile, size_t out_stride, float* out_f32);
-bool obj_msplit(size_t rows);
-bool obj_mix(size_t rows);
 int launch_mlp_fwd(void* stream, int width, size_t rows, int N, const void* enc_tile, const void* view_bf16,
                    const int32_t* ray_idx, const int32_t* count, const void* wpack_fwd, float* raw, void* stash,
                    void* relu_mask, int K, const FwdStrides& st, const int32_t* tail_idx = nullptr,

@@ -124,7 +124,7 @@ static int forward_launches(void* stream, const durf_forward_args* a, const FwdW
     const float* raw_obj[DURF_MAX_OBJ > 0 ? DURF_MAX_OBJ : 1];
     for (int k = 0; k < K; k++) raw_obj[k] = w.obj_raw + (size_t)k * rows * 4;
     // (a large chunk's object MLPs on the library's side stream, issued before the persistent background launch: side_stream.h)
-    const durf::Overlap ov = durf::overlap_for(stream, rows, K);
+    const durf::Overlap ov = durf::overlap_for(stream, durf::step_policy(rows), K);
     const auto obj_fwd = [&](void* s, const float* t_vals) {          // the K object MLPs of one level, hit rays only
         return durf_obj_fwd_batch(s, K, B, N, w.idx_obj, w.count_obj, t_vals, w.o_s, w.d_s, a->radii, a->barf_w,
                                   a->enc_flags & (DURF_ENC_NO_INTEGRATION | DURF_ENC_CYLINDER), w.view, w.wf_obj, w.obj_enc, w.obj_raw,

@@ -1257,12 +1257,18 @@ size_t durf_wpack_bwd_bytes(int width) {
     return (size_t)(width == 256 ? BwdSpec<256>::TOTAL_CHUNKS : BwdSpec<128>::TOTAL_CHUNKS) * 1024;
 }
 
-int durf_mlp_bwd(void* stream, int width, size_t rows, int N, const float* draw, const int32_t* ray_idx,
-                 const int32_t* count, const void* wpack_bwd, const void* relu_mask, void* dz, void* dz_out,
-                 float* d_enc, const int32_t* tail_idx, const int32_t* tail_count, const float* draw_ray_sum) {
+// durf_mlp_bwd's checks of its tail arguments (the mixed launch's background half takes the same)
+static int bwd_tail_args(int N, const int32_t* count, const int32_t* tail_idx, const int32_t* tail_count, const float* draw_ray_sum) {
     DURF_REQUIRE((tail_idx == nullptr) == (tail_count == nullptr) && (tail_idx == nullptr) == (draw_ray_sum == nullptr),
                  "tail_idx, tail_count and draw_ray_sum go together");
     DURF_REQUIRE(tail_idx == nullptr || (count != nullptr && N % 32 == 0), "tail rows follow a compacted ray list");
+    return 0;
+}
+
+int durf_mlp_bwd(void* stream, int width, size_t rows, int N, const float* draw, const int32_t* ray_idx,
+                 const int32_t* count, const void* wpack_bwd, const void* relu_mask, void* dz, void* dz_out,
+                 float* d_enc, const int32_t* tail_idx, const int32_t* tail_count, const float* draw_ray_sum) {
+    if (int rc = bwd_tail_args(N, count, tail_idx, tail_count, draw_ray_sum)) return rc;
     return durf::launch_mlp_bwd(stream, width, rows, N, draw, ray_idx, count, wpack_bwd, relu_mask, dz, dz_out, d_enc,
                                 1, BwdStrides{}, tail_idx, tail_count, draw_ray_sum);
 }
@@ -1280,7 +1286,7 @@ int durf_mlp_bwd_obj(void* stream, size_t rows, int N, const float* draw, const 
     DURF_REQUIRE(K > 0 && B > 0 && (size_t)B * N == rows, "K object MLPs over rows = B * N sample rows");
     DURF_REQUIRE(nlevels >= 1 && nlevels <= DURF_MAX_LEVELS, "1 <= nlevels <= DURF_MAX_LEVELS");
     DURF_REQUIRE(obj_idx && obj_count && obj_draw && obj_wpack_bwd && obj_relu_mask && obj_dz && obj_dz_out, "the object launch's buffers");
-    const bool mix = durf::obj_mix(rows) && N % 32 == 0 && ray_idx != nullptr && count != nullptr;
+    const bool mix = durf::step_policy(rows).mix_enabled && N % 32 == 0 && ray_idx != nullptr && count != nullptr;
     if (!mix) {
         int rc = durf_mlp_bwd(stream, 256, rows, N, draw, ray_idx, count, wpack_bwd, relu_mask, dz, dz_out, nullptr, tail_idx, tail_count,
                               draw_ray_sum);
@@ -1288,8 +1294,7 @@ int durf_mlp_bwd_obj(void* stream, size_t rows, int N, const float* draw, const 
         return durf_obj_bwd_batch_levels(stream, K, B, N, nlevels, obj_idx, obj_count, obj_draw, obj_wpack_bwd, obj_relu_mask, obj_dz,
                                          obj_dz_out);
     }
-    DURF_REQUIRE((tail_idx == nullptr) == (tail_count == nullptr) && (tail_idx == nullptr) == (draw_ray_sum == nullptr),
-                 "tail_idx, tail_count and draw_ray_sum go together");
+    if (int rc = bwd_tail_args(N, count, tail_idx, tail_count, draw_ray_sum)) return rc;
     DURF_REQUIRE(rows % 32 == 0, "rows must be a multiple of 32");
     MsBwd ow{};
     ow.rows = rows; ow.N = N; ow.ray_idx = obj_idx; ow.count = obj_count; ow.wpack = (const char*)obj_wpack_bwd; ow.nobj = K;
@@ -1394,26 +1399,22 @@ int launch_mlp_bwd(void* stream, int width, size_t rows, int N, const float* dra
     if (rows == 0 || K <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     // the object MLPs (W = 128 on compacted ray lists, no d(enc)): the M-split kernel (k_mlp_bwd_ms; DURF_OBJ_MSPLIT=0: A/B switch)
-    {
-        if (width == 128 && ray_idx && count && !d_enc && !tail_idx && obj_msplit(rows)) {
-            const size_t items = (size_t)K * durf_cdiv(rows, 64);       // (small batches only; one round of workgroups: launch_mlp_fwd)
-            MsBwdLevels lv{};
-            lv.draw[0] = draw; lv.relu_mask[0] = (const uint4*)relu_mask; lv.dz[0] = (bf16x8*)dz; lv.dz_out[0] = (bf16x8*)dz_out; lv.n = 1;
-            const MsBwd A{rows, N, lv, ray_idx, count, (const char*)wpack_bwd, st, K, nullptr};
-            hipLaunchKernelGGL(k_mlp_bwd_ms, dim3((unsigned)(items < 256 ? items : 256)), dim3(256), msb::LDS_BYTES, s, A);
-            DURF_CHECK_LAUNCH("durf_mlp_bwd (M-split)");
-            note_dispatch(DURF_DISPATCH_BWD128_MSPLIT);
-            return 0;
-        }
+    if (width == 128 && ray_idx && count && !d_enc && !tail_idx && step_policy(rows).msplit) {      // (small batches only: launch_mlp_fwd)
+        MsBwdLevels lv{};
+        lv.draw[0] = draw; lv.relu_mask[0] = (const uint4*)relu_mask; lv.dz[0] = (bf16x8*)dz; lv.dz_out[0] = (bf16x8*)dz_out; lv.n = 1;
+        const MsBwd A{rows, N, lv, ray_idx, count, (const char*)wpack_bwd, st, K, nullptr};
+        hipLaunchKernelGGL(k_mlp_bwd_ms, dim3(ms_grid((size_t)K * durf_cdiv(rows, 64))), dim3(256), msb::LDS_BYTES, s, A);
+        DURF_CHECK_LAUNCH("durf_mlp_bwd (M-split)");
+        note_dispatch(DURF_DISPATCH_BWD128_MSPLIT);
+        return 0;
     }
-    // (as launch_mlp_fwd: 128-sample blocks of 4 waves when 256-sample blocks would leave half the chip idle)
-    const bool half = width == 256 && K == 1 && !d_enc && durf_cdiv(rows, 256) <= 128;
-    const unsigned nblk = durf_cdiv(rows, half ? 128u : 256u);
-    dim3 grid(nblk < 256u ? nblk : 256u, K), block(half ? 256 : 512);     // persistent: at most one workgroup per CU and object
+    const MlpBlockShape shape = mlp_block_shape(width, K, rows, d_enc != nullptr);
+    const bool half = shape.half;
+    dim3 grid(shape.grid_x, K), block(shape.block);
 #define LAUNCH_B(WW, PP, NWV)                                                                              \
     {                                                                                                      \
         constexpr int lds = 2 * 4 * (MlpSpec<WW>::KW + 1) * 1024;                                          \
-        (void)hipFuncSetAttribute((const void*)k_mlp_bwd<WW, PP, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
+        dynamic_lds_once<k_mlp_bwd<WW, PP, NWV>>(lds);                                                       \
         hipLaunchKernelGGL((k_mlp_bwd<WW, PP, NWV>), grid, block, lds, s, rows, N, draw, ray_idx, count,    \
                            (const char*)wpack_bwd, (const uint4*)relu_mask, (bf16x8*)dz, (bf16x8*)dz_out,  \
                            d_enc, st, tail_idx, tail_count, draw_ray_sum, MsBwd{});                        \
@@ -1429,7 +1430,7 @@ int launch_mlp_bwd(void* stream, int width, size_t rows, int N, const float* dra
 }
 
 // the M-split object backward of SEVERAL levels as one launch (levels x objects x pairs dealt to one 1-D grid); the caller
-// checked obj_msplit(rows)
+// checked the policy's msplit bit
 int launch_mlp_bwd_ms_levels(void* stream, size_t rows, int N, int nlevels, const float* const* draw, const int32_t* ray_idx,
                              const int32_t* count, const void* wpack_bwd, const void* const* relu_mask, void* const* dz,
                              void* const* dz_out, int K, const BwdStrides& st) {
@@ -1440,9 +1441,8 @@ int launch_mlp_bwd_ms_levels(void* stream, size_t rows, int N, int nlevels, cons
     for (int l = 0; l < nlevels; l++) {
         lv.draw[l] = draw[l]; lv.relu_mask[l] = (const uint4*)relu_mask[l]; lv.dz[l] = (bf16x8*)dz[l]; lv.dz_out[l] = (bf16x8*)dz_out[l];
     }
-    const size_t items = (size_t)nlevels * K * durf_cdiv(rows, 64);
     const MsBwd A{rows, N, lv, ray_idx, count, (const char*)wpack_bwd, st, K, nullptr};
-    hipLaunchKernelGGL(k_mlp_bwd_ms, dim3((unsigned)(items < 256 ? items : 256)), dim3(256), msb::LDS_BYTES, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(k_mlp_bwd_ms, dim3(ms_grid((size_t)nlevels * K * durf_cdiv(rows, 64))), dim3(256), msb::LDS_BYTES, (hipStream_t)stream, A);
     DURF_CHECK_LAUNCH("durf_obj_bwd_batch_levels (M-split)");
     note_dispatch(DURF_DISPATCH_BWD128_MSPLIT);
     return 0;

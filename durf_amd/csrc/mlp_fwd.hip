@@ -692,7 +692,9 @@ k_mlp_fwd(size_t rows, int N, const bf16x8* __restrict__ enc, const bf16x8* __re
         nrows = t < rows ? t : rows;
     }
     bool has_block = (size_t)blockIdx.x * (32 * NWV) < nrows;
+#ifdef DURF_MIX_PROBES
     if (MIX && (ei.flags & (1 << 30))) { has_block = false; nrows = 0; }      // (DURF_MIX_PROBE=2: timing probe, object items only)
+#endif
     if (!MIX && !has_block) return;                          // whole workgroup idle
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -963,10 +965,10 @@ int durf_pack_weights(void* stream, int width, int in_dim, const float* mlp_para
     return durf::launch_pack(stream, width, in_dim, 1, mlp_params, 0, wpack_fwd, wpack_bwd);
 }
 
-int durf_mlp_fwd_enc(void* stream, size_t rows, int N, const float* t_vals, const float* origins_s, const float* dirs_s,
-                     const float* radii, const int32_t* hit, int K, int enc_flags, void* enc_tile, const void* view_bf16,
-                     const int32_t* ray_idx, const int32_t* count, const void* wpack_fwd, float* raw, void* stash,
-                     void* relu_mask, const int32_t* tail_idx, const int32_t* tail_count, void* view_tile) {
+// durf_mlp_fwd_enc's argument checks and its EncIn (the mixed launch's background half takes the same arguments)
+static int fwd_enc_args(size_t rows, int N, const float* t_vals, const float* origins_s, const float* dirs_s, const float* radii,
+                        const int32_t* hit, int K, int enc_flags, const void* enc_tile, const int32_t* ray_idx, const int32_t* count,
+                        const void* stash, const int32_t* tail_idx, const int32_t* tail_count, void* view_tile, EncIn* ei) {
     DURF_REQUIRE((tail_idx == nullptr) == (tail_count == nullptr), "tail_idx and tail_count go together");
     DURF_REQUIRE(tail_idx == nullptr || (count != nullptr && N % 32 == 0), "tail rows follow a compacted ray list");
     DURF_REQUIRE((ray_idx == nullptr) == (count == nullptr), "ray_idx and count go together");
@@ -975,9 +977,19 @@ int durf_mlp_fwd_enc(void* stream, size_t rows, int N, const float* t_vals, cons
     DURF_REQUIRE(K >= 0 && K <= DURF_MAX_OBJ && (K == 0 || hit != nullptr), "0 <= K <= DURF_MAX_OBJ, hit [B,K]");
     DURF_REQUIRE(N > 0 && (count != nullptr ? N % 32 == 0 : rows % 32 == 0), "whole 32-sample tiles");
     DURF_REQUIRE(!(enc_flags & DURF_FWD_RAW_FULL) || rows < ((size_t)1 << 32), "DURF_FWD_RAW_FULL: 32-bit row numbers");
-    EncIn ei{};
-    ei.t_vals = t_vals; ei.origins_s = origins_s; ei.dirs_s = dirs_s; ei.radii = radii; ei.hit = hit; ei.K = K; ei.flags = enc_flags;
-    ei.view_tile = view_tile;
+    *ei = EncIn{};
+    ei->t_vals = t_vals; ei->origins_s = origins_s; ei->dirs_s = dirs_s; ei->radii = radii; ei->hit = hit; ei->K = K; ei->flags = enc_flags;
+    ei->view_tile = view_tile;
+    return 0;
+}
+
+int durf_mlp_fwd_enc(void* stream, size_t rows, int N, const float* t_vals, const float* origins_s, const float* dirs_s,
+                     const float* radii, const int32_t* hit, int K, int enc_flags, void* enc_tile, const void* view_bf16,
+                     const int32_t* ray_idx, const int32_t* count, const void* wpack_fwd, float* raw, void* stash,
+                     void* relu_mask, const int32_t* tail_idx, const int32_t* tail_count, void* view_tile) {
+    EncIn ei;
+    if (int rc = fwd_enc_args(rows, N, t_vals, origins_s, dirs_s, radii, hit, K, enc_flags, enc_tile, ray_idx, count, stash, tail_idx,
+                              tail_count, view_tile, &ei)) return rc;
     return durf::launch_mlp_fwd(stream, 256, rows, N, enc_tile, view_bf16, ray_idx, count, wpack_fwd, raw, stash,
                                 relu_mask, 1, FwdStrides{}, tail_idx, tail_count, &ei);
 }
@@ -993,7 +1005,7 @@ int durf_mlp_fwd_enc_obj(void* stream, size_t rows, int N, const float* t_vals, 
     DURF_REQUIRE(K > 0 && B > 0 && (size_t)B * N == rows, "K object MLPs over rows = B * N sample rows");
     DURF_REQUIRE(obj_idx && obj_count && barf_w && obj_wpack_fwd && obj_enc && obj_raw, "the object launch's buffers");
     DURF_REQUIRE((stash == nullptr) == (obj_stash == nullptr), "training or inference: both MLP classes alike");
-    const bool mix = durf::obj_mix(rows) && stash != nullptr && obj_relu_mask != nullptr && N % 32 == 0 && ray_idx != nullptr;
+    const bool mix = durf::step_policy(rows).mix_enabled && stash != nullptr && obj_relu_mask != nullptr && N % 32 == 0 && ray_idx != nullptr;
     if (!mix) {
         int rc = durf_mlp_fwd_enc(stream, rows, N, t_vals, origins_s, dirs_s, radii, hit, K, enc_flags, enc_tile, view_bf16, ray_idx,
                                   count, wpack_fwd, raw, stash, relu_mask, tail_idx, tail_count, view_tile);
@@ -1001,14 +1013,9 @@ int durf_mlp_fwd_enc_obj(void* stream, size_t rows, int N, const float* t_vals, 
         return durf_obj_fwd_batch(stream, K, B, N, obj_idx, obj_count, t_vals, origins_s, dirs_s, radii, barf_w, obj_flags, view_bf16,
                                   obj_wpack_fwd, obj_enc, obj_raw, obj_stash, obj_relu_mask, obj_view_tile);
     }
-    DURF_REQUIRE((tail_idx == nullptr) == (tail_count == nullptr), "tail_idx and tail_count go together");
-    DURF_REQUIRE(tail_idx == nullptr || count != nullptr, "tail rows follow a compacted ray list");
-    DURF_REQUIRE(t_vals && origins_s && dirs_s && radii && enc_tile && hit, "ray data, hit masks and the encoding tile buffer");
-    DURF_REQUIRE(K <= DURF_MAX_OBJ, "K <= DURF_MAX_OBJ");
-    DURF_REQUIRE(!(enc_flags & DURF_FWD_RAW_FULL) || rows < ((size_t)1 << 32), "DURF_FWD_RAW_FULL: 32-bit row numbers");
-    EncIn ei{};
-    ei.t_vals = t_vals; ei.origins_s = origins_s; ei.dirs_s = dirs_s; ei.radii = radii; ei.hit = hit; ei.K = K; ei.flags = enc_flags;
-    ei.view_tile = view_tile;
+    EncIn ei;
+    if (int rc = fwd_enc_args(rows, N, t_vals, origins_s, dirs_s, radii, hit, K, enc_flags, enc_tile, ray_idx, count, stash, tail_idx,
+                              tail_count, view_tile, &ei)) return rc;
     // the object items: durf_obj_fwd_batch's arguments as the M-split kernel takes them
     MsFwd ow{};
     ow.rows = rows; ow.N = N; ow.enc = (const bf16x8*)obj_enc; ow.view = (const bf16x8*)view_bf16; ow.ray_idx = obj_idx;
@@ -1022,11 +1029,12 @@ int durf_mlp_fwd_enc_obj(void* stream, size_t rows, int N, const float* t_vals, 
     ow.ei.view_tile = obj_view_tile; ow.ei.view_stride = durf_obj_view_stride(B, N);
     ow.ticket = durf::next_ticket();
     DURF_REQUIRE(ow.ticket != nullptr, "no item counter for the mixed launch (device allocation failed)");
-    if (const char* pr = getenv("DURF_MIX_PROBE"))        // timing probe (the results are WRONG): the launch without its object items
-    {
-        if (pr[0] == '1') ow.nobj = 0;
+#ifdef DURF_MIX_PROBES      // variant build only (tools/README.md): timing probes, the results are WRONG
+    if (const char* pr = getenv("DURF_MIX_PROBE")) {
+        if (pr[0] == '1') ow.nobj = 0;                       // the launch without its object items
         if (pr[0] == '2') ei.flags |= 1 << 30;               // ... and without its background blocks
     }
+#endif
     const unsigned g = mix_launch_grid<k_mlp_fwd<256, true, 8, true, true>, ms::LDS_BYTES>(rows, (size_t)K * durf_cdiv(rows, 64));
     hipLaunchKernelGGL((k_mlp_fwd<256, true, 8, true, true>), dim3(g), dim3(512), MIX_LDS_BYTES, (hipStream_t)stream, rows, N, (const bf16x8*)enc_tile,
                        (const bf16x8*)view_bf16, ray_idx, count, (const char*)wpack_fwd, raw, (bf16x8*)stash, (uint4*)relu_mask,
@@ -1050,19 +1058,6 @@ int durf_mlp_fwd(void* stream, int width, size_t rows, int N, const void* enc_ti
 }  // extern "C"
 
 namespace durf {
-
-static bool msplit_enabled() {           // read per call: tests toggle it
-    const char* e = getenv("DURF_OBJ_MSPLIT");
-    return !(e && e[0] == '0');
-}
-// whether launch_mlp_fwd / launch_mlp_bwd take the M-split kernels for a W = 128 launch on compacted ray lists of `rows` rows
-bool obj_msplit(size_t rows) { return rows < (size_t)2048 * 128 && msplit_enabled(); }
-// whether a training step of `rows` sample rows per level issues its bf16 object MLPs as items of the background MLP's launches
-// (durf_mlp_fwd_enc_obj / durf_mlp_bwd_obj; DURF_OBJ_MIX=0: A/B switch, bit-identical results)
-bool obj_mix(size_t rows) {
-    const char* e = getenv("DURF_OBJ_MIX");
-    return !(e && e[0] == '0') && obj_msplit(rows);
-}
 
 int pack_bwd_launch(void* stream, int width, int in_dim, int K, const float* params, size_t param_stride, void* wpack_bwd);
 
@@ -1092,30 +1087,26 @@ int launch_mlp_fwd(void* stream, int width, size_t rows, int N, const void* enc_
                    void* relu_mask, int K, const FwdStrides& st, const int32_t* tail_idx, const int32_t* tail_count,
                    const EncIn* enc_in) {
     DURF_REQUIRE(width == 256 || width == 128, "width must be 256 or 128");
-    DURF_REQUIRE(enc_in == nullptr || (width == 256 && K == 1 && !enc_in->obj) || (width == 128 && ray_idx && count && (enc_in->obj || obj_msplit(rows))),
+    const bool msplit = width == 128 && ray_idx && count && step_policy(rows).msplit;
+    DURF_REQUIRE(enc_in == nullptr || (width == 256 && K == 1 && !enc_in->obj) || (width == 128 && ray_idx && count && (enc_in->obj || msplit)),
                  "the self-encoding forward: the background MLP, or the object MLPs on their compacted ray lists");
     DURF_REQUIRE(rows % 32 == 0, "rows must be a multiple of 32");
     DURF_REQUIRE(K == 1 || (ray_idx && count), "batched launches are for compacted object rays");
     if (rows == 0 || K <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    // A launch that fills at most half the chip with 256-sample blocks (8 waves) runs as 128-sample blocks (4 waves): twice the
-    // workgroups, each with half the dependent work, one per CU as before (cfg1: 128 -> 256 workgroups).
-    const bool half = width == 256 && K == 1 && durf_cdiv(rows, 256) <= 128;
-    const unsigned per = half ? 128u : 256u;
-    const unsigned nblk = durf_cdiv(rows, per);
-    // persistent: at most one workgroup per CU and object
-    dim3 grid(nblk < 256u ? nblk : 256u, K), block(half ? 256 : 512);
+    const MlpBlockShape shape = mlp_block_shape(width, K, rows, false);
+    const bool half = shape.half;
+    dim3 grid(shape.grid_x, K), block(shape.block);
     const EncIn ei = enc_in ? *enc_in : EncIn{};
     // The object MLPs (W = 128 on compacted ray lists): the M-split kernel -- 4 waves x 64 samples, one output tile per wave --
     // whose launch is a few microseconds of latency instead of one 11-stage round of 256-sample blocks.  DURF_OBJ_MSPLIT=0
     // keeps k_mlp_fwd<128> (A/B switch; bit-identical results).
-    // Small batches only (below ops.OVERLAP_MIN_ROWS = 2048 x 128 sample rows): there the object launches sit on the critical
+    // Small batches only (below DURF_OVERLAP_MIN_ROWS sample rows): there the object launches sit on the critical
     // path; above, they run on a side stream in the shadow of the persistent background kernels, where a launch that spreads
     // over every CU only delays those (measured at cfg3: 4.26 -> 4.42 ms per step).  At most 128 workgroups per object walk the
     // 64-sample pairs: the hit count lives on the device and an early-exit workgroup still costs its dispatch.
-    if (width == 128 && ray_idx && count && obj_msplit(rows)) {
-        const size_t items = (size_t)K * durf_cdiv(rows, 64);           // capacity; the counts decide (see the kernel)
-        dim3 g((unsigned)(items < 256 ? items : 256)), b(256);         // one workgroup per CU at most: one round
+    if (msplit) {
+        dim3 g(ms_grid((size_t)K * durf_cdiv(rows, 64))), b(256);
         const MsFwd A{rows, N, (const bf16x8*)enc_tile, (const bf16x8*)view_bf16, ray_idx, count, (const char*)wpack_fwd, raw,
                       (bf16x8*)stash, (uint4*)relu_mask, st, ei, K, nullptr};
         if (stash)
@@ -1129,11 +1120,7 @@ int launch_mlp_fwd(void* stream, int width, size_t rows, int N, const void* enc_
 #define LAUNCH_F(WW, TR, NWV, EN)                                                                 \
     {                                                                                             \
         constexpr int lds = 2 * 4 * (MlpSpec<WW>::KW + 1) * 1024;                                 \
-        static bool attr_set = false;      /* once per instantiation (the attribute sticks to the function) */ \
-        if (!attr_set) {                                                                          \
-            (void)hipFuncSetAttribute((const void*)k_mlp_fwd<WW, TR, NWV, EN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-            attr_set = true;                                                                      \
-        }                                                                                         \
+        dynamic_lds_once<k_mlp_fwd<WW, TR, NWV, EN>>(lds);                                        \
         hipLaunchKernelGGL((k_mlp_fwd<WW, TR, NWV, EN>), grid, block, lds, s, rows, N, (const bf16x8*)enc_tile, \
                            (const bf16x8*)view_bf16, ray_idx, count, (const char*)wpack_fwd, raw,  \
                            (bf16x8*)stash, (uint4*)relu_mask, st, tail_idx, tail_count, ei, MsFwd{}); \

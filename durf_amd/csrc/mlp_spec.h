@@ -304,14 +304,32 @@ __device__ __forceinline__ void mix_object_items(char* smem, int wave, int nwg, 
 // once per kernel, and the grid -- one workgroup per CU: the background blocks' (capacity: the counts live on the device),
 // then room for `obj_items` object items, two per workgroup.
 constexpr int MIX_LDS_BYTES = 2 * 4 * (MlpSpec<256>::KW + 1) * 1024;
+template <auto KERNEL>
+static inline void dynamic_lds_once(int bytes) {      // once per kernel (the attribute sticks to the function)
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        attr_set = true;
+    }
+}
 template <auto KERNEL, int ITEM_LDS>
 static inline unsigned mix_launch_grid(size_t rows, size_t obj_items) {
     static_assert(2 * ITEM_LDS + 96 <= MIX_LDS_BYTES, "two object groups fit the background block's LDS");
-    static bool attr_set = false;      // once per kernel (the attribute sticks to the function)
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, MIX_LDS_BYTES);
-        attr_set = true;
-    }
+    dynamic_lds_once<KERNEL>(MIX_LDS_BYTES);
     const unsigned n = durf_cdiv(rows, 256) + durf_cdiv(obj_items, 2);
     return n < 256u ? n : 256u;
 }
+
+// Block shape of the persistent launches (k_mlp_fwd / k_mlp_bwd): a launch that fills at most half the chip with 256-sample
+// blocks (8 waves) runs as 128-sample blocks (4 waves) -- twice the workgroups, each with half the dependent work, one per CU
+// as before (cfg1: 128 -> 256 workgroups).  The background MLP only (W = 256, K = 1), and not the backward that also returns
+// d(enc) (`pose`).  grid_x: persistent, at most one workgroup per CU and object.
+struct MlpBlockShape { bool half; unsigned per, grid_x, block; };
+static inline MlpBlockShape mlp_block_shape(int width, int K, size_t rows, bool pose) {
+    const bool half = width == 256 && K == 1 && !pose && durf_cdiv(rows, 256) <= 128;
+    const unsigned per = half ? 128u : 256u, nblk = durf_cdiv(rows, per);
+    return {half, per, nblk < 256u ? nblk : 256u, half ? 256u : 512u};
+}
+// Grid of the M-split kernels (workgroups of 256 threads) over `items` 64-sample pairs -- capacity; the counts live on the
+// device and decide (see the kernels) -- : one workgroup per CU at most, one round
+static inline unsigned ms_grid(size_t items) { return (unsigned)(items < 256 ? items : 256); }

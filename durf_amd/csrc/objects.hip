@@ -63,7 +63,7 @@ int durf_obj_bwd_batch_levels(void* stream, int K, int B, int N, int nlevels, co
                               void* const* dz_out) {
     DURF_REQUIRE(nlevels >= 1 && nlevels <= DURF_MAX_LEVELS, "1 <= nlevels <= DURF_MAX_LEVELS");
     const size_t rows = (size_t)B * N;
-    if (!durf::obj_msplit(rows)) {          // large batches: the sample-split kernel, level by level (as durf_obj_bwd_batch)
+    if (!durf::step_policy(rows).msplit) {          // large batches: the sample-split kernel, level by level (as durf_obj_bwd_batch)
         for (int l = 0; l < nlevels; l++) {
             const int rc = durf_obj_bwd_batch(stream, K, B, N, idx, count, draw[l], wpack_bwd, relu_mask[l], dz[l], dz_out[l], nullptr);
             if (rc) return rc;

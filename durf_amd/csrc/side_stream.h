@@ -1,18 +1,16 @@
 // The object side stream of the one-call entry points (csrc/train.hip, csrc/forward.hip).
 #pragma once
-#include <cstdlib>
-#include <cstring>
 #include <mutex>
 #include <hip/hip_runtime.h>
+#include "policy.h"
 
 namespace durf {
 
 // The K object MLPs of a LARGE step run beside the background MLP's kernels on a second stream, as durf_amd/obbpose_model.py
-// and train_boxpose.py place them (ops.overlap_mode: from 2048 x 128 sample rows per level; below that every kernel is one
-// latency-bound round and a fork / join is one more dependency in the chain): the forward's object launches are issued
+// and train_boxpose.py place them (durf_step_policy, include/durf_hip.h): the forward's object launches are issued
 // BEFORE the persistent background launch takes every CU, the object backward runs in its shadow, the objects' weight
 // gradients (their own split-K launch + finalize) beside the background's.  One side stream + two events per device,
-// created on first use; DURF_OVERLAP_OBJECTS=0 keeps everything on the caller's stream.  No result depends on it (no atomics).
+// created on first use.  No result depends on it (no atomics).
 // pending_trunk: the buffer an outstanding cross-step prefetch (durf_train_step: prefetch_const_trunk) is writing on this stream
 // -- it also READS the parameters -- or nullptr; whoever uses, recomputes or is asked about that buffer joins first (join_prefetch).
 struct SideStream { hipStream_t s; hipEvent_t forked, joined; bool ok; void* pending_trunk; };
@@ -69,15 +67,12 @@ inline void note_prefetch(SideStream* sd, void* dst) {
     sd->pending_trunk = dst;
 }
 
-// DURF_OVERLAP_OBJECTS as the one-call entry points read it: unset / "auto" = by size, "0" = one stream, anything else = "2"
-// (forward, backward and weight gradients of the objects on the side stream).  The Python-issued path's experiment modes "1"
-// (forward only) and "3" (forward + backward) exist there only (ops.overlap_mode): an A/B of those through the C call measures
-// mode 2.  Read per call (the tests toggle it); the host must not call setenv concurrently with a step.
-inline Overlap overlap_for(void* stream, size_t rows, int Kb) {
+// The one-call entry points know ONE side mode -- forward, backward and weight gradients of the objects on the side stream --
+// and take it for any side bit of the policy: the Python-issued path's experiment modes "1" (forward only) and "3" (forward +
+// backward) exist there only, and an A/B of those through the C call measures mode "2".
+inline Overlap overlap_for(void* stream, const StepPolicy& policy, int Kb) {
     Overlap o{(hipStream_t)stream, nullptr};
-    const char* e = getenv("DURF_OVERLAP_OBJECTS");
-    const bool want = (e == nullptr || !strcmp(e, "auto")) ? rows >= (size_t)2048 * 128 : strcmp(e, "0") != 0;
-    if (Kb > 0 && want) o.sd = side_stream_of_device();
+    if (Kb > 0 && policy.side()) o.sd = side_stream_of_device();
     return o;
 }
 

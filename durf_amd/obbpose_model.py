@@ -327,7 +327,7 @@ class MipNerfModel:
         cyl = self.ray_shape == 'cylinder'
         view_tiles_obj = ops.obj_view_tiles(Kb, B, N, dev) if (train and Kb and not f32) else None
         ctx = dict(o_s=o_s, d_s=d_s, hit=hit, zo=zo, idx=idx, count=count, slot=slot, view=view,
-                   packs=packs, levels=[], B=B, N=N, K=Kd, ts=ts, bkgd_mode=bk, view_tiles_obj=view_tiles_obj,
+                   packs=packs, levels=[], B=B, N=N, K=Kd, ts=ts, policy=ops.step_policy(rows), bkgd_mode=bk, view_tiles_obj=view_tiles_obj,
                    obj_f32=obj_f32 or (f32 and bool(Kd)), obj_x3=obj_f32 and self.object_x3())
         obj_flat = None
         if ctx['obj_f32']:                           # BoxMLP_0 .. BoxMLP_{K-1} sit back to back in the flat buffer
@@ -389,7 +389,7 @@ class MipNerfModel:
                 lvd = None
                 stash_b = torch.empty(ops.mlp_stash_bytes(W_BKGD, rows), dtype=torch.uint8, device=dev) if train else None
                 mask_b = torch.empty(ops.mlp_mask_bytes(rows), dtype=torch.uint8, device=dev) if train else None
-                side = ops.on_side(dev, bool(Kb) and ops.overlap_forward(rows))          # the object MLPs run in the shadow of the background MLP
+                side = ops.on_side(dev, bool(Kb) and ctx['policy'].side_fwd)          # the object MLPs run in the shadow of the background MLP
                 enc_kw = dict(contraction=self.contraction, disable_integration=self.disable_integration, cylinder=cyl)
                 slabs = None
                 # side-stream forward: the object launches are issued BEFORE the persistent background forward, which takes
@@ -414,7 +414,7 @@ class MipNerfModel:
                 # a small training step (one stream): the K object MLPs' forward rides in the background MLP's persistent
                 # launch as (object, tile pair) items (durf_mlp_fwd_enc_obj, round 6) -- bit-identical to the two launches
                 mixed = (train and bool(Kb) and dd is not None and ops.FUSED_ENCODE and ops.FWD_SCATTER_RAW and
-                         not side.enabled and ops.obj_mix(rows))
+                         not side.enabled and ctx['policy'].mix)
                 if mixed:
                     scatter = True
                     raw_c, enc_b = ops.mlp_fwd_enc_obj(rows, N, t_vals, o_s, d_s, radii, hit, view, packs['MLP_0'][0], slabs, idx,

@@ -1,6 +1,7 @@
 """Stage-level operators: torch tensors in, torch tensors out, every one a call through the
 C ABI of libdurf_hip.so on the current HIP stream.  PyTorch is used for device memory and
 streams only.  Reference lines each op replaces are cited in include/durf_hip.h."""
+import collections
 import ctypes as C
 import math
 import os
@@ -425,36 +426,52 @@ def mlp_fwd_enc(rows, N, t_vals, origins_s, dirs_s, radii, hit, view_bf16, wpack
 # together with the background ones, is destructive (background launch 1725-1777 us, 898-910 k rays/s): measured, dropped.
 # The same switch costs at small batches, where every kernel is one latency-bound round and a fork / join is one more
 # dependency in the chain (cfg3 shape, k rays/s, 0 vs 2: 512 rays 595 -> 545-559, 1024 rays 750-756 -> 745, 2048 rays 883
-# -> 902-908, 4096 rays above): 'auto' (default) = 2 from 2048 x 128 sample rows per step (4 rounds of background blocks), else 0.
-_MODE = os.environ.get('DURF_OVERLAP_OBJECTS', 'auto')
-OVERLAP_MIN_ROWS = 2048 * 128
+# -> 902-908, 4096 rays above): 'auto' (default) = 2 from OVERLAP_MIN_ROWS sample rows per step (4 rounds of background blocks), else 0.
+# The rule itself -- this switch, DURF_OBJ_MSPLIT and DURF_OBJ_MIX, read from the environment on every call -- is the library's
+# (durf_step_policy, include/durf_hip.h DURF_POLICY_*); everything below reads it from there.
+class StepPolicy(collections.namedtuple('StepPolicy', 'side_fwd side_bwd side_dw msplit mix_enabled')):      # (in bit order)
+    @property
+    def mix(self):
+        """the bf16 object MLPs ride in the background MLP's persistent launches: enabled, and the step runs on one stream"""
+        return self.mix_enabled and not (self.side_fwd or self.side_bwd or self.side_dw)
+
+
+def step_policy(rows):
+    """the launch policy of a step (or a render chunk) of `rows` sample rows per level"""
+    m = int(_lib.lib().durf_step_policy(rows))
+    return StepPolicy(*(bool(m & (1 << i)) for i in range(5)))
+
+
+def __getattr__(name):
+    if name == 'OVERLAP_MIN_ROWS':          # include/durf_hip.h DURF_OVERLAP_MIN_ROWS
+        return int(_lib.lib().durf_overlap_min_rows())
+    if name == '_MODE':                     # what set_overlap_mode() takes to restore the present setting
+        small, large = overlap_mode(0), overlap_mode(1 << 62)
+        return small if small == large else 'auto'
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))
 
 
 def set_overlap_mode(mode):
-    """'auto' / '0' .. '3' for the Python-issued launches; the one-call C step reads DURF_OVERLAP_OBJECTS per call and knows
-    'auto', '0' and '2' only -- it runs '1' and '3' (experiment modes of this file) as '2' (csrc/side_stream.h)"""
-    global _MODE
-    _MODE = mode
+    """'auto' / '0' .. '3'; the one-call C step runs '1' and '3' (experiment modes of this file) as '2' (csrc/side_stream.h)"""
     os.environ['DURF_OVERLAP_OBJECTS'] = mode
 
 
 def overlap_mode(rows):
     """'0' .. '3' for a step (or a render chunk) of `rows` sample rows per level"""
-    if _MODE == 'auto':
-        return '2' if rows >= OVERLAP_MIN_ROWS else '0'
-    return _MODE
+    p = step_policy(rows)
+    return '2' if p.side_dw else '3' if p.side_bwd else '1' if p.side_fwd else '0'
 
 
 def overlap_forward(rows):
-    return overlap_mode(rows) in ('1', '2', '3')
+    return step_policy(rows).side_fwd
 
 
 def overlap_backward(rows):
-    return overlap_mode(rows) in ('2', '3')
+    return step_policy(rows).side_bwd
 
 
 def overlap_dw(rows):
-    return overlap_mode(rows) == '2'
+    return step_policy(rows).side_dw
 
 
 _SIDE = {}
@@ -929,8 +946,7 @@ def obj_fwd_batch(slabs, idx, count, t_vals, origins_s, dirs_s, radii, alpha, vi
 def obj_mix(rows):
     """whether a training step of `rows` sample rows per level issues its bf16 object MLPs as items of the background MLP's
     persistent launches (durf_mlp_fwd_enc_obj / durf_mlp_bwd_obj: one stream, the M-split regime; DURF_OBJ_MIX=0: A/B switch)"""
-    return (os.environ.get('DURF_OBJ_MIX', '1') != '0' and os.environ.get('DURF_OBJ_MSPLIT', '1') != '0' and
-            rows < OVERLAP_MIN_ROWS and overlap_mode(rows) == '0')
+    return step_policy(rows).mix
 
 
 def mlp_fwd_enc_obj(rows, N, t_vals, origins_s, dirs_s, radii, hit, view_bf16, wpack_fwd, slabs, obj_idx, obj_count, alpha, obj_wf,

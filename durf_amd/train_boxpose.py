@@ -245,11 +245,12 @@ def loss_and_grad(model, config, rng, variables, batch, eps, alpha, prev, noise=
     bufs = None if f32 else ops.dw_buffers(om.W_BKGD, dev)
     dzs = [None] * L                            # per-level (dz, dz_out) of the bkgd MLP, consumed by ONE dW launch
     dd = ctx.get('dedup')                        # de-duplicated background evaluation (obbpose_model._forward)
-    # Side stream (ops.overlap_mode; large batches only -- a fork / join is one more dependency in a latency-bound step): the
+    policy = ctx['policy']                       # ops.step_policy(rows), as the forward took it
+    # Side stream (large batches only -- a fork / join is one more dependency in a latency-bound step): the
     # object backward / weight gradients and, when the forward did not write it, the view-direction tile (read by the
     # weight-gradient launch only).  (Until round 5 also the loss launches of the levels below the last: one launch for every
     # level on this stream measured better -- two cross-stream hops fewer.)
-    side = ops.on_side(dev, not f32 and ops.overlap_backward(rows))
+    side = ops.on_side(dev, not f32 and policy.side_bwd)
     main = torch.cuda.current_stream() if side.enabled else None
     obj_side = side if Kb else ops.on_side(dev, False)
 
@@ -323,7 +324,7 @@ def loss_and_grad(model, config, rng, variables, batch, eps, alpha, prev, noise=
     obj_bwd_done = bool(Kb) and not pose_opt and not f32 and all(d is not None for d in draws)
     # ... or, at a small step on one stream, level by level as items of the background backward's persistent launch
     # (durf_mlp_bwd_obj, round 6: bit-identical to the launches of their own)
-    obj_bwd_mixed = obj_bwd_done and dd is not None and not obj_side.enabled and ops.obj_mix(rows)
+    obj_bwd_mixed = obj_bwd_done and dd is not None and not obj_side.enabled and policy.mix
     if obj_bwd_done and not obj_bwd_mixed:
         obj_side.fork()
         with obj_side:
@@ -444,7 +445,7 @@ def loss_and_grad(model, config, rng, variables, batch, eps, alpha, prev, noise=
         else:
             geo = ([rows] * L, [N] * L, [None] * L)
         o0, sz = (lay.mlp_off['BoxMLP_0'], lay.mlp_size[om.W_OBJ]) if Kb else (0, 0)
-        merged = Kb and not ops.overlap_dw(rows) and objects_ready is None
+        merged = Kb and not policy.side_dw and objects_ready is None
         if Kb and objects_ready is not None:           # bucketed all-reduce: the objects' gradients first, finalized on their own
             obj_side.join()                            # (the object backward may still be writing dz on the side stream)
             ops.obj_dw_batch([lv['slabs'] for lv in levels], ctx['view_tiles_obj'], ctx['count'],

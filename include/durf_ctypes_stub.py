@@ -17,6 +17,11 @@ def bind(path='durf_amd/libdurf_hip.so'):
     L.durf_dispatch_seen.argtypes = []
     L.durf_dispatch_reset.restype = i32
     L.durf_dispatch_reset.argtypes = []
+    L.durf_step_policy.restype = C.c_uint
+    L.durf_step_policy.argtypes = [u64]
+    #   (rows)
+    L.durf_overlap_min_rows.restype = u64
+    L.durf_overlap_min_rows.argtypes = []
     L.durf_mlp_param_count.restype = u64
     L.durf_mlp_param_count.argtypes = [i32, i32]
     #   (width, in_dim)

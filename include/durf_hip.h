@@ -49,7 +49,7 @@ int durf_version(void);
 #define DURF_DISPATCH_FWD256_8W 0x1        /* k_mlp_fwd<256>: 256-sample blocks of 8 waves */
 #define DURF_DISPATCH_FWD256_4W 0x2        /* k_mlp_fwd<256>: 128-sample blocks of 4 waves (launches of <= 128 blocks) */
 #define DURF_DISPATCH_FWD128_SAMPLE 0x4    /* k_mlp_fwd<128>: the object MLPs, one wave per 32 samples */
-#define DURF_DISPATCH_FWD128_MSPLIT 0x8    /* k_mlp_fwd_ms: the object MLPs, one wave per output tile (< 2048 x 128 rows) */
+#define DURF_DISPATCH_FWD128_MSPLIT 0x8    /* k_mlp_fwd_ms: the object MLPs, one wave per output tile (< DURF_OVERLAP_MIN_ROWS) */
 #define DURF_DISPATCH_BWD256_8W 0x10
 #define DURF_DISPATCH_BWD256_4W 0x20
 #define DURF_DISPATCH_BWD128_SAMPLE 0x40
@@ -76,6 +76,30 @@ int durf_version(void);
 #define DURF_LAYERLOG_TRAJ_PACK 0x2000000   /* k_frame_pack: the 8-bit epilogue (absent when rgb8 is NULL) */
 int durf_dispatch_seen(void);
 int durf_dispatch_reset(void);
+/* The launch policy of a step's bf16 object work, for `rows` sample rows per level: a bit mask of DURF_POLICY_*.  Three
+ * environment variables steer it, read on every call, and none of them changes a result:
+ *   DURF_OVERLAP_OBJECTS  unset / "auto": "2" from DURF_OVERLAP_MIN_ROWS sample rows per level, else "0".  "0" one stream;
+ *                         "1" the object forward on a side stream; "3" forward + backward; "2" forward + backward + weight
+ *                         gradients.  (Below the threshold every kernel is one latency-bound round and a fork / join is one
+ *                         more dependency in the chain.)  The one-call entry points know one side mode: any side bit is "2".
+ *   DURF_OBJ_MSPLIT=0     W = 128 launches on compacted ray lists keep the sample-split kernels below the threshold too.
+ *   DURF_OBJ_MIX=0        no object items in the background MLP's persistent launches (durf_mlp_fwd_enc_obj / durf_mlp_bwd_obj).
+ * A step mixes where DURF_POLICY_MIX is set AND it runs on one stream (no side bit).  Every launcher and both orchestrations
+ * (durf_amd/ops.py, csrc/train.hip / forward.hip) take their decision from this function (csrc/policy.h); it needs no device. */
+#define DURF_OVERLAP_MIN_ROWS ((size_t)2048 * 128)      /* 4 rounds of background blocks */
+#define DURF_POLICY_SIDE_FWD 0x1
+#define DURF_POLICY_SIDE_BWD 0x2
+#define DURF_POLICY_SIDE_DW 0x4
+#define DURF_POLICY_MSPLIT 0x8         /* rows < DURF_OVERLAP_MIN_ROWS and DURF_OBJ_MSPLIT is not 0 */
+#define DURF_POLICY_MIX 0x10           /* DURF_POLICY_MSPLIT and DURF_OBJ_MIX is not 0 */
+unsigned durf_step_policy(size_t rows);
+size_t durf_overlap_min_rows(void);    /* DURF_OVERLAP_MIN_ROWS, for hosts that cannot read this header */
+/* The item counters of the mixed launches (DURF_DISPATCH_FWD_MIX / BWD_MIX) are the library's own state: a ring of zeroed
+ * ints per device, allocated and zero filled on a device's first mixed launch.  That first use allocates and synchronizes, so
+ * it is illegal under stream capture: run one mixed step before capturing.  The device is the calling thread's current one
+ * (hipGetDevice), not the stream's -- as for every call here, they must agree.  A launch takes one slot and leaves it zeroed
+ * (the workgroup that draws the last ticket resets it); a launch that FAULTS leaves its slot nonzero, and the launch that
+ * meets that slot 16 384 mixed launches later would skip object items -- after a device fault, restart the process. */
 
 /* ---- parameter layout -------------------------------------------------------
  * One contiguous fp32 buffer (so the data-parallel gradient exchange is a single
@@ -249,7 +273,7 @@ int durf_mlp_fwd_enc(void* stream, size_t rows, int N, const float* t_vals, cons
  * the de-duplication leaves without a block (512 rays) or with one block fewer (1024 rays, K = 8) absorb the object MLPs
  * inside the background launch's own duration, where a second launch cost 22 us per level and a second stream delayed the
  * persistent workgroups.  Every output (raw, encoding tiles, stashes, masks, view tiles of both classes) is bit-identical
- * to the two separate calls'.  Applies in training below 2048 x 128 sample rows (the M-split regime of the object
+ * to the two separate calls'.  Applies in training below DURF_OVERLAP_MIN_ROWS sample rows (the M-split regime of the object
  * kernels); otherwise, with inference buffers (stash == NULL) or under DURF_OBJ_MIX=0, the call issues the two launches. */
 int durf_mlp_fwd_enc_obj(void* stream, size_t rows, int N, const float* t_vals, const float* origins_s, const float* dirs_s,
                          const float* radii, const int32_t* hit, int K, int enc_flags, void* enc_tile, const void* view_bf16,
@@ -551,7 +575,7 @@ int durf_render_trajectory(void* stream, const durf_forward_args* args, const in
  * workspace: durf_train_workspace_bytes_flags(B, N, K, num_levels, n_params, flags) bytes, 256-byte aligned
  * (durf_train_workspace_bytes = flags 0).
  * Streams: everything is ordered on `stream`, whose device must be the calling thread's current device.  The bf16 object
- * MLPs of a large step (>= 2048 x 128 sample rows per level) run on a second, non-blocking stream the library creates per
+ * MLPs of a large step (>= DURF_OVERLAP_MIN_ROWS sample rows per level) run on a second, non-blocking stream the library creates per
  * device on first use, forked from / joined to `stream` with events inside the call (DURF_OVERLAP_OBJECTS=0: one stream);
  * when the call returns, all of its work is ordered before whatever the caller issues to `stream` next -- with ONE exception,
  * prefetch_const_trunk (below): that launch is left running on the side stream, reading `params` and writing const_trunk.  The
@@ -735,7 +759,7 @@ int durf_obj_bwd_batch(void* stream, int K, int B, int N, const int32_t* idx, co
                        const float* draw, const void* wpack_bwd, const void* relu_mask, void* dz, void* dz_out,
                        float* d_enc /* nullable */);
 /* The same for EVERY level of a step at once (no d(enc)): stop_level_grad makes each level's d(raw) a function of the forward
- * alone, so all of them exist before the first backward launch; at small batches (the M-split kernel, < 2048 x 128 sample rows)
+ * alone, so all of them exist before the first backward launch; at small batches (the M-split kernel, < DURF_OVERLAP_MIN_ROWS sample rows)
  * the step's object backward is then ONE latency-bound launch instead of one per level.  draw / relu_mask / dz / dz_out: host
  * arrays [nlevels] of the per-level device buffers durf_obj_bwd_batch takes.  Bit-identical to the per-level calls. */
 int durf_obj_bwd_batch_levels(void* stream, int K, int B, int N, int nlevels, const int32_t* idx, const int32_t* count,
@@ -745,7 +769,7 @@ int durf_obj_bwd_batch_levels(void* stream, int K, int B, int N, int nlevels, co
  * durf_obj_bwd_batch_levels of the K object MLPs over `nlevels` levels (host arrays of per-level device buffers) as ONE
  * heterogeneous persistent launch -- background blocks, then (level, object, tile pair) items off a ticket counter on two
  * 4-wave groups per workgroup.  dz / dz_out of both classes bit-identical to the two calls, which it falls back to above
- * 2048 x 128 sample rows or under DURF_OBJ_MIX=0. */
+ * DURF_OVERLAP_MIN_ROWS sample rows or under DURF_OBJ_MIX=0 (durf_step_policy). */
 int durf_mlp_bwd_obj(void* stream, size_t rows, int N, const float* draw, const int32_t* ray_idx, const int32_t* count,
                      const void* wpack_bwd, const void* relu_mask, void* dz, void* dz_out, const int32_t* tail_idx /* nullable */,
                      const int32_t* tail_count /* nullable */, const float* draw_ray_sum /* nullable */, int K, int B, int nlevels,

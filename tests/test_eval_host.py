@@ -73,7 +73,7 @@ def test_symbols_are_declared_bound_and_exported():
         assert re.search(r'\b%s\s*\(' % name, hdr), name + ' is not in include/durf_hip.h'
         assert name in _lib._SIGS, name + ' is not in durf_amd/_sigs.py'
         assert hasattr(L, name)
-    assert len(_lib._SIGS) == 116
+    assert len(_lib._SIGS) == 118
     assert L.durf_version() == 41
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'gen_integration_stub.py'), '--check'], cwd=ROOT)
     assert p.returncode == 0, 'the header, durf_amd/_sigs.py, the stub and INTEGRATION.md have drifted apart'

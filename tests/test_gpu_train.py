@@ -652,7 +652,7 @@ def test_side_stream_modes_give_the_same_parameters(cuda, monkeypatch, pose_opt)
     db = H.device_batch(synthetic.make_batch(B, K, seed=77), cuda)
     results = {}
     for mode in ('0', '2', '3', '1'):
-        monkeypatch.setattr(ops, '_MODE', mode)
+        monkeypatch.setenv('DURF_OVERLAP_OBJECTS', mode)
         assert ops.overlap_mode(B * N) == mode
         model, variables = obbpose_model.construct_mipnerf(5, db, device=cuda)
         state = train_boxpose.create_train_state(variables)
@@ -664,7 +664,7 @@ def test_side_stream_modes_give_the_same_parameters(cuda, monkeypatch, pose_opt)
     for mode in ('2', '3', '1'):
         for a, b in zip(results['0'], results[mode]):
             assert torch.equal(a, b), 'mode %s differs from the single-stream step' % mode
-    monkeypatch.setattr(ops, '_MODE', 'auto')
+    monkeypatch.setenv('DURF_OVERLAP_OBJECTS', 'auto')
     assert ops.overlap_mode(2048 * 128) == '2' and ops.overlap_mode(2048 * 128 - 1) == '0'
 
 

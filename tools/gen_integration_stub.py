@@ -43,10 +43,10 @@ def parse_header(text=None):
     text = open(HDR).read() if text is None else text
     body = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
     out = []
-    for m in re.finditer(r'(?:^|\n)\s*(const char\*|int|size_t)\s+(durf_\w+)\s*\(([^;{]*?)\)\s*;', body):
+    for m in re.finditer(r'(?:^|\n)\s*(const char\*|int|unsigned|size_t)\s+(durf_\w+)\s*\(([^;{]*?)\)\s*;', body):
         ret, name, args = m.group(1), m.group(2), ' '.join(m.group(3).split())
         params = [] if args in ('', 'void') else [ctype_of(a) for a in args.split(',')]
-        out.append((name, {'const char*': 'C.c_char_p', 'int': 'i32', 'size_t': 'u64'}[ret], params))
+        out.append((name, {'const char*': 'C.c_char_p', 'int': 'i32', 'unsigned': 'C.c_uint', 'size_t': 'u64'}[ret], params))
     return out
 
 
