@@ -1193,15 +1193,22 @@ def mlp_f32_pack(width, in_dim, mlp_params, K=1, param_stride=0, x3=False):
 
 
 def mlp_fwd_f32(width, in_dim, rows, N, enc_f32, view27, mlp_params, ray_idx=None, count=None, want_act=False,
-                wstream=None):
+                wstream=None, raw=None, act=None):
     """-> raw [rows,4][, act (opaque record buffer for mlp_bwd_f32 / mlp_dw_f32)].  enc_f32 [rows,in_dim] row-major, or
-    None: every row is the background MLP's constant encoding of a box-hit ray (width 256); view27 [B,27]"""
+    None: every row is the background MLP's constant encoding of a box-hit ray (width 256); view27 [B,27]
+    raw / act: caller-owned output buffers (at least [rows,4] / tile_rows(rows) records; act implies want_act)"""
     dev = view27.device
     L = _lib.lib()
     if wstream is None:
         wstream = mlp_f32_pack(width, in_dim, mlp_params)
-    raw = torch.zeros(rows, 4, device=dev)
-    act = torch.empty(tile_rows(rows) * int(L.durf_mlp_f32_act_floats(width, in_dim)), device=dev) if want_act else None
+    want_act = want_act or act is not None
+    nact = tile_rows(rows) * int(L.durf_mlp_f32_act_floats(width, in_dim))
+    if raw is None:
+        raw = torch.zeros(rows, 4, device=dev)
+    assert _f32(raw).numel() >= rows * 4
+    if want_act and act is None:
+        act = torch.empty(nact, device=dev)
+    assert act is None or _f32(act).numel() >= nact
     with _Timed('mlp_fwd_f32_%d' % width):
         _lib.check(L.durf_mlp_fwd_f32(_stream(), width, in_dim, rows, N, _p(None if enc_f32 is None else _f32(enc_f32)),
                                       _p(_f32(view27)), _p(ray_idx), _p(count), _p(_f32(mlp_params)), _p(wstream), _p(raw),
@@ -1209,14 +1216,22 @@ def mlp_fwd_f32(width, in_dim, rows, N, enc_f32, view27, mlp_params, ray_idx=Non
     return (raw, act) if want_act else raw
 
 
-def mlp_bwd_f32(width, in_dim, rows, N, draw, mlp_params, act, ray_idx=None, count=None, want_d_enc=False, wstream=None):
-    """-> dz (opaque record buffer)[, d_enc [rows,64]]"""
+def mlp_bwd_f32(width, in_dim, rows, N, draw, mlp_params, act, ray_idx=None, count=None, want_d_enc=False, wstream=None,
+                dz=None, d_enc=None):
+    """-> dz (opaque record buffer)[, d_enc [rows,64]]
+    dz / d_enc: caller-owned output buffers (at least tile_rows(rows) records / [rows,64]; d_enc implies want_d_enc)"""
     dev = draw.device
     L = _lib.lib()
     if wstream is None:
         wstream = mlp_f32_pack(width, in_dim, mlp_params)
-    dz = torch.empty(tile_rows(rows) * int(L.durf_mlp_f32_dz_floats(width, in_dim)), device=dev)
-    d_enc = torch.zeros(rows, ENC_DIM, device=dev) if want_d_enc else None
+    want_d_enc = want_d_enc or d_enc is not None
+    ndz = tile_rows(rows) * int(L.durf_mlp_f32_dz_floats(width, in_dim))
+    if dz is None:
+        dz = torch.empty(ndz, device=dev)
+    assert _f32(dz).numel() >= ndz
+    if want_d_enc and d_enc is None:
+        d_enc = torch.zeros(rows, ENC_DIM, device=dev)
+    assert d_enc is None or _f32(d_enc).numel() >= rows * ENC_DIM
     with _Timed('mlp_bwd_f32_%d' % width):
         _lib.check(L.durf_mlp_bwd_f32(_stream(), width, in_dim, rows, N, _p(_f32(draw)), _p(ray_idx), _p(count),
                                       _p(_f32(mlp_params)), _p(wstream), _p(_f32(act)), _p(dz), _p(d_enc)),
@@ -1244,13 +1259,16 @@ def bkgd_const_trunk_f32(bkgd_params):
     return trunk
 
 
-def bkgd_hit_rays_f32(B, view27, bkgd_params, idx1, count1, trunk=None):
+def bkgd_hit_rays_f32(B, view27, bkgd_params, idx1, count1, trunk=None, raw_tail=None):
     """the background MLP's one evaluation of every box-hit ray (ray class 1: idx1 / count1), in fp32 -> raw_tail [B,4]
-    (row j = ray idx1[j]): the view layer and the rgb head per ray on top of bkgd_const_trunk_f32's output"""
+    (row j = ray idx1[j]): the view layer and the rgb head per ray on top of bkgd_const_trunk_f32's output
+    raw_tail: a caller-owned [B,4] buffer; rows from count1 on are not written"""
     dev = view27.device
     if trunk is None:
         trunk = bkgd_const_trunk_f32(bkgd_params)
-    raw_tail = torch.empty(B, 4, device=dev)
+    if raw_tail is None:
+        raw_tail = torch.empty(B, 4, device=dev)
+    assert _f32(raw_tail).numel() >= B * 4
     with _Timed('bkgd_hit_rays_f32'):
         _lib.check(_lib.lib().durf_bkgd_hit_rays_f32(_stream(), B, _p(_f32(view27)), _p(_f32(bkgd_params)), _p(idx1),
                                                      _p(count1), _p(trunk), _p(raw_tail)), 'durf_bkgd_hit_rays_f32')
@@ -1260,12 +1278,17 @@ def bkgd_hit_rays_f32(B, view27, bkgd_params, idx1, count1, trunk=None):
 class ObjSlabsF32:
     """[K, ...] slabs of one level for the batched fp32 object calls (durf_objf32_*; strides fixed by the library)"""
 
-    def __init__(self, K, B, N, device, train):
+    def __init__(self, K, B, N, device, train, raw=None, act=None):
+        """raw [K, B * N, 4] / act (K * durf_objf32_act_stride floats): caller-owned slabs instead of fresh ones (act may
+        be longer)"""
         L = _lib.lib()
         self.K, self.B, self.N = K, B, N
         self.enc = None                       # only filled by objf32_fwd_batch(fused_encode=False)
-        self.raw = torch.empty(K, B * N, 4, device=device)
-        self.act = torch.empty(K * int(L.durf_objf32_act_stride(B, N)), device=device) if train else None
+        nact = K * int(L.durf_objf32_act_stride(B, N))
+        self.raw = torch.empty(K, B * N, 4, device=device) if raw is None else raw
+        assert _f32(self.raw).shape == (K, B * N, 4)
+        self.act = act if act is not None else (torch.empty(nact, device=device) if train else None)
+        assert self.act is None or _f32(self.act).numel() >= nact
         self.dz = self.d_enc = None
 
     def raws(self):
@@ -1297,12 +1320,21 @@ def objf32_fwd_batch(slabs, idx, count, t_vals, origins_s, dirs_s, radii, alpha,
                    'durf_objf32_fwd_batch')
 
 
-def objf32_bwd_batch(slabs, idx, count, draw, obj_params, param_stride, wstream, want_d_enc=False, x3=False):
+def objf32_bwd_batch(slabs, idx, count, draw, obj_params, param_stride, wstream, want_d_enc=False, x3=False, dz=None,
+                     d_enc=None):
+    """dz (K * durf_objf32_dz_stride floats) / d_enc [K, B * N, 64]: caller-owned slabs instead of fresh ones (d_enc implies
+    want_d_enc)"""
     L = _lib.lib()
     dev = draw.device
     K, B, N = slabs.K, slabs.B, slabs.N
-    slabs.dz = torch.empty(K * int(L.durf_objf32_dz_stride(B, N)), device=dev)
-    slabs.d_enc = torch.empty(K, B * N, ENC_DIM, device=dev) if want_d_enc else None     # every valid row is written
+    ndz = K * int(L.durf_objf32_dz_stride(B, N))
+    slabs.dz = torch.empty(ndz, device=dev) if dz is None else dz
+    assert _f32(slabs.dz).numel() >= ndz
+    if d_enc is not None:
+        assert _f32(d_enc).shape == (K, B * N, ENC_DIM)
+        slabs.d_enc = d_enc
+    else:
+        slabs.d_enc = torch.empty(K, B * N, ENC_DIM, device=dev) if want_d_enc else None     # every valid row is written
     with _Timed('objf32_bwd_batch'):
         fn = L.durf_objf32_bwd_batch_x3 if x3 else L.durf_objf32_bwd_batch
         _lib.check(fn(_stream(), K, B, N, _p(idx), _p(count), _p(_f32(draw)), _p(_f32(obj_params)), int(param_stride), _p(wstream),

@@ -36,7 +36,8 @@ def _params(width, in_dim, seed, requires_grad=False):
 @pytest.mark.parametrize('width,in_dim', [(256, 60), (128, 63)])
 def test_mlp_f32_forward_backward(cuda, width, in_dim):
     """fwd / bwd / dW kernels against fp64 autograd of the oracle MLP: outputs 2e-6 rel, gradients 1e-5 norm-wise
-    (fp32 round-off only); ragged row count (not a multiple of 32) and the object calling convention (ray_idx, count)."""
+    (fp32 round-off only); the object calling convention (ray_idx, count) with a count below the capacity.  N = 32, so every
+    row count here is a whole number of 32-row tiles (19 valid of 21): the partial tiles are tests/test_gpu_f32_edges.py's."""
     N, Bn = 32, 21
     rows = N * Bn
     cfg, params, flat, g = _params(width, in_dim, 5, requires_grad=True)
@@ -275,7 +276,9 @@ def test_background_mlp_on_the_box_hit_rays(cuda):
     count = torch.tensor([cnt], dtype=torch.int32, device=cuda)
     d = lambda t: t.to(cuda).contiguous()
     a = ops.mlp_fwd_f32(256, 60, B, 1, None, d(view_all), d(flat), ray_idx=d(ridx), count=count)
-    got = ops.bkgd_hit_rays_f32(B, d(view_all), d(flat), d(ridx), count)
+    tail = torch.full((B, 4), -1, dtype=torch.int32, device=cuda).view(torch.float32)          # 0xFF bytes: NaN
+    got = ops.bkgd_hit_rays_f32(B, d(view_all), d(flat), d(ridx), count, raw_tail=tail)
+    assert got.data_ptr() == tail.data_ptr() and bool((got[cnt:].view(torch.int32) == -1).all()), 'rows past count untouched'
     torch.testing.assert_close(got[:cnt], a[:cnt], rtol=2e-6, atol=2e-6)
     const = torch.cat([torch.zeros(cnt, 30), torch.ones(cnt, 30)], 1)
     p64 = [[k.double(), b_.double()] for k, b_ in params]
