@@ -1139,10 +1139,12 @@ def encode_obj_bwd(k_obj, idx_k, count_k, d_enc, t_vals, origins_s, dirs_s, radi
 
 
 def encode_obj_bwd_batch(K, idx, count, d_enc, t_vals, origins_s, dirs_s, radii, origins, dirs, pose, alpha, sums,
-                         precise=False, enc_flags=0):
-    """all K objects of one level in one launch pair: idx [K,B], count [K], d_enc [K, B*N, 64] (obj_bwd_batch's slab)"""
+                         precise=False, enc_flags=0, scratch=None):
+    """all K objects of one level in one launch pair: idx [K,B], count [K], d_enc [K, B*N, 64] (obj_bwd_batch's slab);
+    scratch: caller-owned K*21*B floats (the per-ray rows [K][21][B], column j = compact ray index), or None"""
     B, N = t_vals.shape[0], t_vals.shape[1] - 1
-    scratch = torch.empty(K * 21 * B, device=t_vals.device)
+    if scratch is None:
+        scratch = torch.empty(K * 21 * B, device=t_vals.device)
     w = barf_weights(alpha)
     wa = (C.c_float * 10)(*[float(x) for x in w])
     _lib.check(_lib.lib().durf_encode_obj_bwd_batch(_stream(), int(K), B, N, _p(idx), _p(count), _p(_f32(d_enc)),
@@ -1152,13 +1154,38 @@ def encode_obj_bwd_batch(K, idx, count, d_enc, t_vals, origins_s, dirs_s, radii,
                'durf_encode_obj_bwd_batch')
 
 
+def encode_obj_bwd_levels(K, idx, count, d_enc_list, t_vals_list, origins_s, dirs_s, radii, origins, dirs, pose, alpha, sums,
+                          scratch=None, precise=False, enc_flags=0):
+    """all K objects of every level in one launch pair (durf_encode_obj_bwd_levels: the one-call step's form): one d_enc slab
+    [K, B*N, 64] and one t_vals [B, N+1] per level, the same N; the levels' row sums are added into sums [K,21] in the order
+    given.  scratch: caller-owned nlev*K*21*B floats (level l's rows [K][21][B] at l*K*21*B), or None"""
+    nlev = len(d_enc_list)
+    if nlev != len(t_vals_list) or nlev < 1:
+        raise ValueError('encode_obj_bwd_levels: %d d_enc slabs for %d t_vals' % (nlev, len(t_vals_list)))
+    B, N = t_vals_list[0].shape[0], t_vals_list[0].shape[1] - 1
+    if any(tuple(t.shape) != (B, N + 1) for t in t_vals_list):
+        raise ValueError('encode_obj_bwd_levels: every level takes the same [B, N+1] t_vals')
+    if scratch is None:
+        scratch = torch.empty(nlev * K * 21 * B, device=t_vals_list[0].device)
+    w = barf_weights(alpha)
+    wa = (C.c_float * 10)(*[float(x) for x in w])
+    de = (C.c_void_p * nlev)(*[_p(_f32(t)) for t in d_enc_list])
+    tv = (C.c_void_p * nlev)(*[_p(_f32(t)) for t in t_vals_list])
+    _lib.check(_lib.lib().durf_encode_obj_bwd_levels(_stream(), int(K), B, N, nlev, _p(idx), _p(count), de, tv,
+                                                     _p(_f32(origins_s)), _p(_f32(dirs_s)), _p(_f32(radii)), _p(_f32(origins)),
+                                                     _p(_f32(dirs)), _p(_f32(pose)), wa, _p(scratch), _p(_f32(sums)),
+                                                     int(precise), int(enc_flags)), 'durf_encode_obj_bwd_levels')
+
+
 def encode_bkgd_bwd_batch(K, idx, count, d_enc, t_vals, origins_s, dirs_s, radii, origins, dirs, pose, sums, raw=None, draw=None,
-                          density_bias=-1.0, denc_slot=None, enc_flags=ENC_CONTRACT):
+                          density_bias=-1.0, denc_slot=None, enc_flags=ENC_CONTRACT, scratch=None):
     """dynamics=False: the box-pose rows of all K boxes of one level through the BACKGROUND encoding (durf_encode_bkgd_bwd_batch):
     idx [K,B], count [K] (compact_hits); d_enc [rows,64]: row b*N + n, or denc_slot[b]*N + n (the fp32 evaluation of the box-hit
-    rays); raw / draw [B*N,4] add the rendering's |d_s| term.  Accumulates into sums [K,21]."""
+    rays); raw / draw [B*N,4] add the rendering's |d_s| term.  Accumulates into sums [K,21].  scratch: caller-owned K*21*B
+    floats (the per-ray rows), or None."""
     B, N = t_vals.shape[0], t_vals.shape[1] - 1
-    scratch = torch.empty(K * 21 * B, device=t_vals.device)
+    if scratch is None:
+        scratch = torch.empty(K * 21 * B, device=t_vals.device)
     _lib.check(_lib.lib().durf_encode_bkgd_bwd_batch(_stream(), int(K), B, N, _p(idx), _p(count), _p(_f32(d_enc)), _p(denc_slot),
                                                      _p(_f32(t_vals)), _p(_f32(origins_s)), _p(_f32(dirs_s)), _p(_f32(radii)),
                                                      _p(_f32(origins)), _p(_f32(dirs)), _p(_f32(pose)),
