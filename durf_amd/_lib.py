@@ -11,9 +11,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DURF_LIB_PATH: kernel-tuning A/B builds (tools/build_variant.sh); the default is the in-tree build
 LIB_PATH = os.environ.get('DURF_LIB_PATH') or os.path.join(_HERE, 'libdurf_hip.so')
 
+OVERLAY_LIB_PATH = os.path.join(_HERE, 'libdurf_overlay.so')        # the box overlay (include/durf_overlay.h), built beside it
+
 _lib = None
+_overlay = None
 
 from ._sigs import SIGS as _SIGS       # generated from include/durf_hip.h (tools/gen_integration_stub.py)
+from ._overlay_sigs import SIGS as _OVERLAY_SIGS       # generated from include/durf_overlay.h
 
 
 def symbols():
@@ -39,6 +43,27 @@ def lib():
             fn.argtypes = args
         _lib = L
     return _lib
+
+
+def overlay_symbols():
+    """Every symbol include/durf_overlay.h declares."""
+    return sorted(_OVERLAY_SIGS)
+
+
+def overlay_lib():
+    """libdurf_overlay.so, after libdurf_hip.so (it reports errors through that library's durf_last_error): no fallback either"""
+    global _overlay
+    if _overlay is None:
+        lib()
+        if not os.path.exists(OVERLAY_LIB_PATH):
+            raise RuntimeError('libdurf_overlay.so not built (%s).  Run __graft_entry__.build().' % OVERLAY_LIB_PATH)
+        L = C.CDLL(OVERLAY_LIB_PATH)
+        for name, (res, args) in _OVERLAY_SIGS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _overlay = L
+    return _overlay
 
 
 class DurfError(RuntimeError):

@@ -1816,3 +1816,46 @@ def eval_frames(rgb, gt_rgb, distance=None, gt_depth=None, obj_mask=None):
         _lib.check(L.durf_eval_frames(_stream(), F, H, W, _p(_f32(rgb)), _p(_f32(gt_rgb)), opt(distance), opt(gt_depth),
                                       opt(obj_mask), _p(out), _p(scratch), nbytes), 'durf_eval_frames')
     return out, EVAL_FIELDS
+
+
+# ---- the scene's boxes on rendered frames (csrc/overlay.hip, libdurf_overlay.so; include/durf_overlay.h) -------
+BOX_EDGES = 12                                           # DURF_BOX_EDGES
+BOX_RECT_FLOATS = 6                                      # DURF_BOX_RECT_FLOATS
+BOX_RECT_FIELDS = ('xmin', 'ymin', 'xmax', 'ymax', 'zc', 'visible')
+MAX_OBJ = 16                                             # DURF_MAX_OBJ
+
+
+def project_boxes(cams, poses, ext, box_enable=None, znear=1e-2):
+    """cams [F,17] device rows, poses [F,K,6], ext [K,3] -> (segments [F,K,12,4], rect [F,K,BOX_RECT_FLOATS]): one launch of
+    durf_project_boxes, no read-back.  box_enable: None or K values 0 / 1 (a box with 0 is culled whole)."""
+    F, K = int(poses.shape[0]), int(poses.shape[1])
+    dev = poses.device
+    assert tuple(cams.shape) == (F, 17) and tuple(poses.shape) == (F, K, 6) and tuple(ext.shape) == (K, 3), \
+        (tuple(cams.shape), tuple(poses.shape), tuple(ext.shape))
+    segments = torch.empty(F, K, BOX_EDGES, 4, device=dev)
+    rect = torch.empty(F, K, BOX_RECT_FLOATS, device=dev)
+    en = _enable(box_enable, K, dev)
+    with _Timed('project_boxes'):
+        _lib.check(_lib.overlay_lib().durf_project_boxes(_stream(), F, K, _p(_f32(cams)), _p(_f32(poses)), _p(_f32(ext)), _p(en),
+                                                 float(znear), _p(segments), _p(rect)), 'durf_project_boxes')
+    return segments, rect
+
+
+def draw_boxes(segments, colors, half_width, opacity=1.0, frames8=None, framesf=None, label=None):
+    """durf_draw_boxes, one launch: segments [F,K,12,4], colors [K,3] uint8 on the device; frames8 [F,h,w,3] uint8 (any byte
+    offset into its storage) and / or framesf [F,h,w,3] float are decorated IN PLACE, label [F,h,w] int32 is written whole
+    (the owning box, -1: none).  At least one target."""
+    targets = [t for t in (frames8, framesf, label) if t is not None]
+    if not targets:
+        raise ValueError('at least one of frames8, framesf and label')
+    F, h, w = (int(n) for n in targets[0].shape[:3])
+    K = int(segments.shape[1])
+    for t, dt, shape in ((frames8, torch.uint8, (F, h, w, 3)), (framesf, torch.float32, (F, h, w, 3)), (label, torch.int32, (F, h, w))):
+        assert t is None or (t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape), (t.dtype, tuple(t.shape))
+    assert tuple(segments.shape) == (F, K, BOX_EDGES, 4), (tuple(segments.shape), F)
+    assert colors.dtype == torch.uint8 and colors.is_cuda and colors.is_contiguous() and tuple(colors.shape) == (K, 3), \
+        (colors.dtype, tuple(colors.shape))
+    with _Timed('draw_boxes'):
+        _lib.check(_lib.overlay_lib().durf_draw_boxes(_stream(), F, h, w, K, _p(_f32(segments)), _p(colors), float(half_width), float(opacity),
+                                              _p(frames8), _p(framesf), _p(label)), 'durf_draw_boxes')
+    return frames8, framesf, label

@@ -3,6 +3,7 @@ internal/utils.py:155) and the loop of notebooks/durf_render_traj.ipynb as a com
 
     python -m durf_amd.render_traj --gin_file configs/waymo.gin --data_dir DATA --train_dir CKPT --traj traj.npz --eval_dir OUT
                                    [--cam 0] [--disable_box k ...] [--chunk 8192] [--vis [--vis_near N] [--vis_far F]]
+                                   [--boxes [--box_width W] [--box_opacity A]]
     python -m durf_amd.render_traj --synthetic --eval_dir OUT [--frames 8] [--traj traj.npz]
 
 The checkpoint in --train_dir is restored, the intrinsics (focal, principal point, image size) are those of image --cam of the
@@ -13,7 +14,10 @@ MipNerfModel.render_trajectory call; OUT/%04d.ppm (binary P6) and OUT/distance.n
 depth pictures of the reference's evaluation block (vis.visualize_suite) for every frame: OUT/depth_%04d.ppm,
 OUT/depth_mod_%04d.ppm and OUT/normals_%04d.ppm, from ONE batched 8-bit durf_amd.vis.visualize_suite call over the
 trajectory's distance and acc planes (--vis_near / --vis_far: the planes of the depth picture; unset, every frame takes its
-own least and greatest depth).  --synthetic renders
+own least and greatest depth).  --boxes adds the frames with the scene's boxes drawn on them, OUT/boxes_%04d.ppm, and the
+boxes' 2D rectangles OUT/boxes2d.npy [F,K,6] (xmin, ymin, xmax, ymax, depth of the centre, visible), from
+durf_amd.overlay.overlay_trajectory on the call's own poses (a box switched off with --disable_box is not drawn; --box_width:
+the lines' width in pixels, --box_opacity: how much of the picture they cover).  --synthetic renders
 train_boxpose.SyntheticTimestepDataset's scene instead (no data directory; without --train_dir the freshly initialised
 model, without --traj a sweep between the scene's first and last camera), which exercises the command end to end."""
 import argparse
@@ -44,6 +48,9 @@ def build_parser():
     ap.add_argument('--vis', action='store_true', help='also write depth_%%04d.ppm, depth_mod_%%04d.ppm and normals_%%04d.ppm')
     ap.add_argument('--vis_near', type=float, default=None, help='--vis: near plane of the depth picture (default: per frame, automatic)')
     ap.add_argument('--vis_far', type=float, default=None, help='--vis: far plane of the depth picture (default: per frame, automatic)')
+    ap.add_argument('--boxes', action='store_true', help='also write boxes_%%04d.ppm (the frames with the boxes drawn on) and boxes2d.npy')
+    ap.add_argument('--box_width', type=float, default=1.5, help='--boxes: width of the lines in pixels')
+    ap.add_argument('--box_opacity', type=float, default=1.0, help='--boxes: opacity of the lines, 0..1')
     return ap
 
 
@@ -136,6 +143,14 @@ def main(argv=None):
                         depth_mod=vis.visualize_depth(dist, acc, modulus=0.1, out8=True),
                         depth_normals=vis.visualize_normals(dist, acc, out8=True))
         write_pictures(args.eval_dir, {k: v.cpu().numpy() for k, v in pics.items()})
+    if args.boxes:
+        from . import overlay
+        drawn = overlay.overlay_trajectory(dict(rgb8=out['rgb8'], poses=out['poses']), cams, ext, box_enable=enable,
+                                           width=args.box_width, opacity=args.box_opacity)
+        boxes8 = drawn['rgb8'].reshape(rgb8.shape[0], int(h), int(w), 3).cpu().numpy()
+        for f in range(boxes8.shape[0]):
+            trajectory.write_ppm(os.path.join(args.eval_dir, 'boxes_%04d.ppm' % f), boxes8[f])
+        np.save(os.path.join(args.eval_dir, 'boxes2d.npy'), drawn['rect'].cpu().numpy())
     print('render_traj: %d frames of %d x %d written to %s' % (rgb8.shape[0], int(h), int(w), args.eval_dir))
     return 0
 

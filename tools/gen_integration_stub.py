@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """include/durf_hip.h -> the reference-side ctypes binding (include/durf_ctypes_stub.py) and the copy of it
-embedded in INTEGRATION.md, and the product's own table durf_amd/_sigs.py, so that no copy can drift from the header:
+embedded in INTEGRATION.md, and the product's own table durf_amd/_sigs.py, so that no copy can drift from the header;
+include/durf_overlay.h (libdurf_overlay.so, a library of its own) -> durf_amd/_overlay_sigs.py likewise:
     python tools/gen_integration_stub.py            # rewrite both
     python tools/gen_integration_stub.py --check    # exit 1 if either is stale (tests/test_host_logic.py)
 The parser handles exactly the C subset the header uses (scalar / pointer parameters, /* */ comments)."""
@@ -13,6 +14,8 @@ HDR = os.path.join(ROOT, 'include', 'durf_hip.h')
 STUB = os.path.join(ROOT, 'include', 'durf_ctypes_stub.py')
 SIGS = os.path.join(ROOT, 'durf_amd', '_sigs.py')          # the product's own binding table (durf_amd/_lib.py)
 DOC = os.path.join(ROOT, 'INTEGRATION.md')
+OVERLAY_HDR = os.path.join(ROOT, 'include', 'durf_overlay.h')
+OVERLAY_SIGS = os.path.join(ROOT, 'durf_amd', '_overlay_sigs.py')  # the binding table of libdurf_overlay.so
 BEGIN, END = '<!-- BEGIN GENERATED: tools/gen_integration_stub.py -->', '<!-- END GENERATED -->'
 
 SCALARS = {'int': 'i32', 'float': 'f32', 'size_t': 'u64', 'int32_t': 'i32', 'uint32_t': 'C.c_uint32'}
@@ -70,11 +73,13 @@ def render():
     return '\n'.join(L)
 
 
-def render_sigs():
-    L = ['"""Argument types of every entry point of libdurf_hip.so -- GENERATED from include/durf_hip.h by',
+def render_sigs(hdr=None, lib='libdurf_hip.so'):
+    """the binding table of `lib` from header `hdr` (default: include/durf_hip.h)"""
+    text = None if hdr is None else open(hdr).read()
+    L = ['"""Argument types of every entry point of %s -- GENERATED from include/%s by' % (lib, os.path.basename(hdr or HDR)),
          'tools/gen_integration_stub.py (do not edit; `--check` runs in the CPU test-suite)."""', 'import ctypes as C', '',
          'vp, i32, f32, u64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t', '', 'SIGS = {']
-    for name, ret, params in parse_header():
+    for name, ret, params in parse_header(text):
         L.append('    %r: (%s, [%s]),' % (name, ret, ', '.join(t for t, _ in params)))
     L += ['}', '']
     return '\n'.join(L)
@@ -88,16 +93,19 @@ def doc_with_stub(doc, stub):
 def main():
     stub = render()
     sigs = render_sigs()
+    overlay_sigs = render_sigs(OVERLAY_HDR, 'libdurf_overlay.so')
     doc = open(DOC).read()
     new_doc = doc_with_stub(doc, stub)
     if '--check' in sys.argv:
         ok = (os.path.exists(STUB) and open(STUB).read() == stub and new_doc == doc and
-              os.path.exists(SIGS) and open(SIGS).read() == sigs)
+              os.path.exists(SIGS) and open(SIGS).read() == sigs and
+              os.path.exists(OVERLAY_SIGS) and open(OVERLAY_SIGS).read() == overlay_sigs)
         if not ok:
             print('stale: run python tools/gen_integration_stub.py')
         sys.exit(0 if ok else 1)
     open(STUB, 'w').write(stub)
     open(SIGS, 'w').write(sigs)
+    open(OVERLAY_SIGS, 'w').write(overlay_sigs)
     open(DOC, 'w').write(new_doc)
     print('wrote %s (%d functions) and the block in INTEGRATION.md' % (os.path.relpath(STUB, ROOT), len(parse_header())))
 
