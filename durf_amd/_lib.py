@@ -12,12 +12,15 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DURF_LIB_PATH') or os.path.join(_HERE, 'libdurf_hip.so')
 
 OVERLAY_LIB_PATH = os.path.join(_HERE, 'libdurf_overlay.so')        # the box overlay (include/durf_overlay.h), built beside it
+LIDAR_LIB_PATH = os.path.join(_HERE, 'libdurf_lidar.so')            # LIDAR sweeps (include/durf_lidar.h), likewise
 
 _lib = None
 _overlay = None
+_lidar = None
 
 from ._sigs import SIGS as _SIGS       # generated from include/durf_hip.h (tools/gen_integration_stub.py)
 from ._overlay_sigs import SIGS as _OVERLAY_SIGS       # generated from include/durf_overlay.h
+from ._lidar_sigs import SIGS as _LIDAR_SIGS       # generated from include/durf_lidar.h
 
 
 def symbols():
@@ -64,6 +67,27 @@ def overlay_lib():
             fn.argtypes = args
         _overlay = L
     return _overlay
+
+
+def lidar_symbols():
+    """Every symbol include/durf_lidar.h declares."""
+    return sorted(_LIDAR_SIGS)
+
+
+def lidar_lib():
+    """libdurf_lidar.so, after libdurf_hip.so (it calls that library and reports errors through its durf_last_error): no fallback either"""
+    global _lidar
+    if _lidar is None:
+        lib()
+        if not os.path.exists(LIDAR_LIB_PATH):
+            raise RuntimeError('libdurf_lidar.so not built (%s).  Run __graft_entry__.build().' % LIDAR_LIB_PATH)
+        L = C.CDLL(LIDAR_LIB_PATH)
+        for name, (res, args) in _LIDAR_SIGS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _lidar = L
+    return _lidar
 
 
 class DurfError(RuntimeError):

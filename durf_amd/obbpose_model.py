@@ -684,6 +684,12 @@ class MipNerfModel:
             return variables['params']['box_centers'].new_empty(0, 6)
         return self._trajectory_call(variables, None, [float(t)], None, False, 0.0, 0.0, 1.0, 1, None, ())['poses'][0]
 
+    def render_lidar(self, variables, sensor, poses, times, ext, white_bkgd, alpha, **kw):
+        """F sweeps of a spinning LIDAR (durf_amd.lidar.LidarSensor) through the scene, ONE library call (durf_render_lidar,
+        libdurf_lidar.so): durf_amd.lidar.render_lidar(self, ...) -- see there.  Same scope as render_image_one_call."""
+        from . import lidar
+        return lidar.render_lidar(self, variables, sensor, poses, times, ext, white_bkgd, alpha, **kw)
+
     def apply(self, variables, rng, rays, init, ext, ts, randomized, rand_bkgd, white_bkgd, alpha,
               noise=None, *, box_enable=None, pose=None):
         """model.apply(variables, key, rays, init, ext, ts, randomized=, rand_bkgd=, white_bkgd=,

@@ -1859,3 +1859,126 @@ def draw_boxes(segments, colors, half_width, opacity=1.0, frames8=None, framesf=
         _lib.check(_lib.overlay_lib().durf_draw_boxes(_stream(), F, h, w, K, _p(_f32(segments)), _p(colors), float(half_width), float(opacity),
                                               _p(frames8), _p(framesf), _p(label)), 'durf_draw_boxes')
     return frames8, framesf, label
+
+
+# ---- LIDAR sweeps (csrc/lidar.hip, libdurf_lidar.so; include/durf_lidar.h) -------------------------------------
+LIDAR_SENSOR_FLOATS = 6                                  # DURF_LIDAR_SENSOR_FLOATS: H, W, az0, az_span, radius_scale, max_range
+LIDAR_SWEEP_FLOATS = 18                                  # DURF_LIDAR_SWEEP_FLOATS: pose_start [3,4], omega [3], dp [3]
+LIDAR_COMPACT_BLOCK = 256                                # DURF_LIDAR_COMPACT_BLOCK
+LIDAR_POINT_FLOATS = 8                                   # DURF_LIDAR_POINT_FLOATS
+LIDAR_POINT_FIELDS = ('x', 'y', 'z', 'range', 'r', 'g', 'b', 'dynamic')
+LIDAR_OUTPUTS = ('range', 'range_mean', 'distance', 'acc', 'rgb', 'spread', 'dynamic', 'valid', 'xyz')      # in argument order
+
+
+def _host_floats(values, n, what):
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(values, np.float32).reshape(-1))
+    if a.size != n:
+        raise ValueError('%s: %d floats, expected %d' % (what, a.size, n))
+    return (C.c_float * n)(*a.tolist())
+
+
+def lidar_compact_scratch(n):
+    """DURF_LIDAR_COMPACT_SCRATCH(n): int32 elements of durf_lidar_compact's scratch"""
+    return (n + LIDAR_COMPACT_BLOCK - 1) // LIDAR_COMPACT_BLOCK + 1
+
+
+def lidar_rays(sensor_row, inclinations, sweep_row, near, far, first=0, count=None):
+    """rays [first, first + count) of one sweep (durf_lidar_rays, one launch): sensor_row 6 host floats, inclinations [H] on the
+    device, sweep_row 18 host floats -> (origins, directions, viewdirs [count,3], radii, near, far [count])"""
+    H, Wd = int(sensor_row[0]), int(sensor_row[1])
+    count = H * Wd - first if count is None else count
+    dev = inclinations.device
+    f = lambda *sh: torch.empty(*sh, device=dev)
+    out = (f(count, 3), f(count, 3), f(count, 3), f(count), f(count), f(count))
+    with _Timed('lidar_rays'):
+        _lib.check(_lib.lidar_lib().durf_lidar_rays(_stream(), _host_floats(sensor_row, LIDAR_SENSOR_FLOATS, 'sensor_row'),
+                                                    _p(_f32(inclinations)), _host_floats(sweep_row, LIDAR_SWEEP_FLOATS, 'sweep_row'),
+                                                    int(first), int(count), float(near), float(far), *[_p(t) for t in out]),
+                   'durf_lidar_rays')
+    return out
+
+
+def lidar_returns(weights, t_vals, acc, origins=None, directions=None, q=0.5, q_lo=0.16, q_hi=0.84, min_acc=0.5,
+                  max_range=float('inf'), to_sensor=None):
+    """the return model on weights [n,N], t_vals [n,N+1], acc [n] (durf_lidar_returns, one launch) -> dict: range, range_mean,
+    spread [n], valid [n] int32 and, with origins / directions [n,3], xyz [n,3] (world; with to_sensor, a [3,4] host
+    world-to-sensor row, in that frame)"""
+    n, N = int(weights.shape[0]), int(weights.shape[1])
+    assert tuple(t_vals.shape) == (n, N + 1) and acc.numel() == n, (tuple(weights.shape), tuple(t_vals.shape), tuple(acc.shape))
+    dev = weights.device
+    f = lambda *sh: torch.empty(*sh, device=dev)
+    out = dict(range=f(n), range_mean=f(n), valid=torch.empty(n, dtype=torch.int32, device=dev), spread=f(n))
+    if origins is not None:
+        assert tuple(origins.shape) == (n, 3) == tuple(directions.shape), (tuple(origins.shape), tuple(directions.shape))
+        out['xyz'] = f(n, 3)
+    M = None if to_sensor is None else _host_floats(to_sensor, 12, 'to_sensor')
+    with _Timed('lidar_returns'):
+        _lib.check(_lib.lidar_lib().durf_lidar_returns(
+            _stream(), n, N, _p(_f32(weights)), _p(_f32(t_vals)), _p(_f32(acc)), _p(None if origins is None else _f32(origins)),
+            _p(None if origins is None else _f32(directions)), M, float(q), float(q_lo), float(q_hi), float(min_acc), float(max_range),
+            _p(out['range']), _p(out['range_mean']), _p(out['valid']), _p(out.get('xyz')), _p(out['spread'])), 'durf_lidar_returns')
+    return out
+
+
+def lidar_compact(valid, xyz, range_, rgb=None, dyn_mask=None, points=None, source=None):
+    """the valid returns of n rays, in ray order (durf_lidar_compact: three launches, no read-back) -> points [n,8] (x, y, z, range,
+    r, g, b, dynamic; rows from count on are untouched), source [n] int32, count [1] int32 ON THE DEVICE"""
+    n = int(valid.numel())
+    dev = valid.device
+    assert valid.dtype == torch.int32 and valid.is_contiguous() and xyz.numel() == 3 * n and range_.numel() == n
+    points = torch.empty(n, LIDAR_POINT_FLOATS, device=dev) if points is None else points
+    source = torch.empty(n, dtype=torch.int32, device=dev) if source is None else source
+    assert tuple(points.shape) == (n, LIDAR_POINT_FLOATS) and source.dtype == torch.int32 and source.numel() == n
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(lidar_compact_scratch(n), dtype=torch.int32, device=dev)
+    if dyn_mask is not None:
+        assert dyn_mask.dtype == torch.int32 and dyn_mask.is_contiguous() and dyn_mask.numel() == n
+    with _Timed('lidar_compact'):
+        _lib.check(_lib.lidar_lib().durf_lidar_compact(_stream(), n, _p(valid), _p(_f32(xyz)), _p(_f32(range_)),
+                                                       _p(None if rgb is None else _f32(rgb)), _p(dyn_mask), _p(_f32(points)), _p(source),
+                                                       _p(count), _p(scratch)), 'durf_lidar_compact')
+    return points, source, count
+
+
+def render_lidar(sensor_row, inclinations, sweep_rows, poses, ext, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha,
+                 enc_flags, chunk, near, far, lindisp=False, bkgd_mode=BKGD_GREY, density_bias=-1.0, resample_padding=0.01,
+                 box_enable=None, q=0.5, q_lo=0.16, q_hi=0.84, min_acc=0.5, outputs=LIDAR_OUTPUTS, out=None):
+    """F sweeps as ONE library call (durf_render_lidar): sensor_row 6 host floats, inclinations [H] on the device, sweep_rows
+    [F,18] host floats, poses [F,K,6] on the device (the boxes of every sweep) -> dict of the requested `outputs`, [F,n,.]
+    with n = H * W.  out: dict of preallocated contiguous tensors to write into.  The call only enqueues work."""
+    import numpy as np
+    outputs = tuple(outputs)
+    unknown = [o for o in outputs if o not in LIDAR_OUTPUTS]
+    if unknown:
+        raise ValueError('unknown outputs %s: choose from %s' % (unknown, list(LIDAR_OUTPUTS)))
+    sweep_rows = np.ascontiguousarray(np.asarray(sweep_rows, np.float32).reshape(-1, LIDAR_SWEEP_FLOATS))
+    F, K = int(sweep_rows.shape[0]), int(poses.shape[1])
+    if int(poses.shape[0]) != F:
+        raise ValueError('%d box-pose rows for %d sweeps' % (poses.shape[0], F))
+    H, Wd = int(sensor_row[0]), int(sensor_row[1])
+    n = max(H, 0) * max(Wd, 0)
+    dev = inclinations.device
+    L = _lib.lidar_lib()
+    res = {}
+    for name in outputs:
+        shape = (F, n, 3) if name in ('rgb', 'xyz') else (F, n)
+        dtype = torch.int32 if name in ('dynamic', 'valid') else torch.float32
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        assert tuple(t.shape) == shape and t.dtype == dtype and t.is_cuda and t.is_contiguous(), (name, tuple(t.shape), t.dtype)
+        res[name] = t
+    a = ForwardArgs()
+    _fill_model_args(a, K, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags, lindisp, bkgd_mode,
+                     density_bias, resample_padding)
+    a.B = ck = max(min(chunk, max(n, 1)), 1)
+    a.ext = _p(_f32(ext)) if K else None
+    ws = _workspace(dev, int(L.durf_render_lidar_workspace_bytes(ck, N, K, num_levels)))
+    with _Timed('render_lidar'):
+        _lib.check(L.durf_render_lidar(_stream(), C.byref(a), _p(box_enable), F, _host_floats(sensor_row, LIDAR_SENSOR_FLOATS, 'sensor_row'),
+                                       _p(_f32(inclinations)), (C.c_float * max(sweep_rows.size, 1))(*sweep_rows.reshape(-1).tolist()),
+                                       _p(_f32(poses)) if K else None, float(near), float(far), ck, float(q), float(q_lo), float(q_hi),
+                                       float(min_acc), *[_p(res.get(name)) for name in LIDAR_OUTPUTS], _p(ws), ws.numel()),
+                   'durf_render_lidar')
+    return res
