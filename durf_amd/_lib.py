@@ -13,14 +13,17 @@ LIB_PATH = os.environ.get('DURF_LIB_PATH') or os.path.join(_HERE, 'libdurf_hip.s
 
 OVERLAY_LIB_PATH = os.path.join(_HERE, 'libdurf_overlay.so')        # the box overlay (include/durf_overlay.h), built beside it
 LIDAR_LIB_PATH = os.path.join(_HERE, 'libdurf_lidar.so')            # LIDAR sweeps (include/durf_lidar.h), likewise
+FLOW_LIB_PATH = os.path.join(_HERE, 'libdurf_flow.so')              # motion between frames (include/durf_flow.h), likewise
 
 _lib = None
 _overlay = None
 _lidar = None
+_flow = None
 
 from ._sigs import SIGS as _SIGS       # generated from include/durf_hip.h (tools/gen_integration_stub.py)
 from ._overlay_sigs import SIGS as _OVERLAY_SIGS       # generated from include/durf_overlay.h
 from ._lidar_sigs import SIGS as _LIDAR_SIGS       # generated from include/durf_lidar.h
+from ._flow_sigs import SIGS as _FLOW_SIGS       # generated from include/durf_flow.h
 
 
 def symbols():
@@ -88,6 +91,27 @@ def lidar_lib():
             fn.argtypes = args
         _lidar = L
     return _lidar
+
+
+def flow_symbols():
+    """Every symbol include/durf_flow.h declares."""
+    return sorted(_FLOW_SIGS)
+
+
+def flow_lib():
+    """libdurf_flow.so, after libdurf_hip.so (it calls that library and reports errors through its durf_last_error): no fallback either"""
+    global _flow
+    if _flow is None:
+        lib()
+        if not os.path.exists(FLOW_LIB_PATH):
+            raise RuntimeError('libdurf_flow.so not built (%s).  Run __graft_entry__.build().' % FLOW_LIB_PATH)
+        L = C.CDLL(FLOW_LIB_PATH)
+        for name, (res, args) in _FLOW_SIGS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _flow = L
+    return _flow
 
 
 class DurfError(RuntimeError):

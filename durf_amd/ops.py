@@ -1982,3 +1982,131 @@ def render_lidar(sensor_row, inclinations, sweep_rows, poses, ext, bkgd_params, 
                                        float(min_acc), *[_p(res.get(name)) for name in LIDAR_OUTPUTS], _p(ws), ws.numel()),
                    'durf_render_lidar')
     return res
+
+
+# ---- motion between frames (csrc/flow.hip, libdurf_flow.so; include/durf_flow.h) -------------------------------
+FLOW_CONS_FLOATS = 4                                     # DURF_FLOW_CONS_FLOATS
+FLOW_CONS_FIELDS = ('count', 'sse', 'sae', 'psnr')
+FLOW_CONS_SPAN = 4096                                    # DURF_FLOW_CONS_SPAN
+FLOW_WHEEL = 55                                          # DURF_FLOW_WHEEL
+FLOW_OUTPUTS = ('flow', 'scene_flow', 'xyz', 'target', 'zcam', 'moving', 'valid')      # in argument order
+_FLOW_COLS = dict(flow=2, scene_flow=3, xyz=3, target=3, zcam=None, moving=None, valid=None)
+
+
+def flow_pose_floats(K):
+    """DURF_FLOW_POSE_FLOATS(K): floats of durf_flow_points' pose scratch"""
+    return 2 * K * 12
+
+
+def flow_cons_scratch(P, m):
+    """DURF_FLOW_CONS_SCRATCH(P, m): floats of durf_flow_consistency's scratch"""
+    return P * ((m + FLOW_CONS_SPAN - 1) // FLOW_CONS_SPAN) * 3
+
+
+def _flow_outputs(outputs, lead, dev, out=None):
+    outputs = tuple(outputs)
+    unknown = [o for o in outputs if o not in FLOW_OUTPUTS]
+    if unknown:
+        raise ValueError('unknown outputs %s: choose from %s' % (unknown, list(FLOW_OUTPUTS)))
+    res = {}
+    for name in outputs:
+        cols = _FLOW_COLS[name]
+        shape = tuple(lead) + ((cols,) if cols else ())
+        dtype = torch.int32 if name in ('moving', 'valid') else torch.float32
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        assert tuple(t.shape) == shape and t.dtype == dtype and t.is_cuda and t.is_contiguous(), (name, tuple(t.shape), t.dtype)
+        res[name] = t
+    return res
+
+
+def flow_points(origins_s, dirs_s, hit, t, acc, cam_a, cam_b, pose_a, pose_b, ext, *, first=0, normalise=True, min_acc=0.5,
+                znear=1e-2, inside_tol=1e-3, outputs=FLOW_OUTPUTS, out=None):
+    """where n pixels [first, first + n) of frame a go (durf_flow_points: a one-wave pose launch and one per-pixel launch):
+    origins_s, dirs_s [n,3], hit [n,K] int32 (ray_setup's outputs at pose_a), t, acc [n], cam_a / cam_b 17 host floats, pose_a /
+    pose_b [K,6], ext [K,3] -> dict of the requested `outputs` (FLOW_OUTPUTS), [n,.]"""
+    n, K = int(origins_s.shape[0]), int(pose_a.shape[0])
+    dev = origins_s.device
+    assert tuple(dirs_s.shape) == (n, 3) and t.numel() == n and acc.numel() == n, (tuple(dirs_s.shape), tuple(t.shape), tuple(acc.shape))
+    if K:
+        assert hit.dtype == torch.int32 and hit.is_contiguous() and tuple(hit.shape) == (n, K), (hit.dtype, tuple(hit.shape))
+        assert tuple(pose_b.shape) == (K, 6) and tuple(ext.shape) == (K, 3), (tuple(pose_b.shape), tuple(ext.shape))
+    res = _flow_outputs(outputs, (n,), dev, out)
+    scratch = torch.empty(max(flow_pose_floats(K), 1), device=dev)
+    with _Timed('flow_points'):
+        _lib.check(_lib.flow_lib().durf_flow_points(
+            _stream(), n, int(first), K, _p(_f32(origins_s)), _p(_f32(dirs_s)), _p(hit) if K else None, _p(_f32(t)), _p(_f32(acc)),
+            _host_floats(cam_a, 17, 'cam_a'), _host_floats(cam_b, 17, 'cam_b'), _p(_f32(pose_a)) if K else None,
+            _p(_f32(pose_b)) if K else None, _p(_f32(ext)) if K else None, int(bool(normalise)), float(min_acc), float(znear),
+            float(inside_tol), _p(scratch), *[_p(res.get(name)) for name in FLOW_OUTPUTS]), 'durf_flow_points')
+    return res
+
+
+def flow_warp(target, valid, img_b, zcam_b, occ_rel=0.02, occ_abs=0.0, want_warped=True, want_mask=True):
+    """frame b sampled where frame a's pixels land (durf_flow_warp, one launch): target [n,3], valid [n] int32, img_b [h,w,C]
+    (C 1 or 3), zcam_b [h,w] -> (warped [n,C], NaN where not visible, or None; mask [n] int32 or None)"""
+    n = int(valid.numel())
+    h, w, Cc = (int(x) for x in img_b.shape)
+    dev = img_b.device
+    assert target.numel() == 3 * n and valid.dtype == torch.int32 and valid.is_contiguous() and zcam_b.numel() == h * w, \
+        (tuple(target.shape), valid.dtype, tuple(zcam_b.shape))
+    warped = torch.empty(n, Cc, device=dev) if want_warped else None
+    mask = torch.empty(n, dtype=torch.int32, device=dev) if want_mask else None
+    with _Timed('flow_warp'):
+        _lib.check(_lib.flow_lib().durf_flow_warp(_stream(), n, h, w, Cc, _p(_f32(target)), _p(valid), _p(_f32(img_b)), _p(_f32(zcam_b)),
+                                                  float(occ_rel), float(occ_abs), _p(warped), _p(mask)), 'durf_flow_warp')
+    return warped, mask
+
+
+def flow_consistency(warped, img_a, mask):
+    """warped, img_a [P,m,C], mask [P,m] int32 -> [P,FLOW_CONS_FLOATS] (count, sse, sae, psnr) on the device
+    (durf_flow_consistency: two launches, no atomics, the same bits on every run)"""
+    P, m, Cc = (int(x) for x in warped.shape)
+    assert tuple(img_a.shape) == (P, m, Cc) and tuple(mask.shape) == (P, m) and mask.dtype == torch.int32 and mask.is_contiguous(), \
+        (tuple(img_a.shape), tuple(mask.shape), mask.dtype)
+    dev = warped.device
+    out = torch.empty(P, FLOW_CONS_FLOATS, device=dev)
+    scratch = torch.empty(max(flow_cons_scratch(P, m), 1), device=dev)
+    with _Timed('flow_consistency'):
+        _lib.check(_lib.flow_lib().durf_flow_consistency(_stream(), P, m, Cc, _p(_f32(warped)), _p(_f32(img_a)), _p(mask), _p(out),
+                                                         _p(scratch)), 'durf_flow_consistency')
+    return out
+
+
+def flow_color(flow, max_mag, want_float=True, want_u8=False):
+    """the Middlebury flow picture of flow [n,2] (durf_flow_color, one launch) -> (rgb [n,3] float or None, rgb8 [n,3] uint8 or None)"""
+    n = int(flow.numel()) // 2
+    dev = flow.device
+    rgb = torch.empty(n, 3, device=dev) if want_float else None
+    rgb8 = torch.empty(n, 3, dtype=torch.uint8, device=dev) if want_u8 else None
+    with _Timed('flow_color'):
+        _lib.check(_lib.flow_lib().durf_flow_color(_stream(), n, _p(_f32(flow)), float(max_mag), _p(rgb), _p(rgb8)), 'durf_flow_color')
+    return rgb, rgb8
+
+
+def render_flow(cams, poses, ext, distance, acc, pairs, near, far, chunk, *, box_enable=None, normalise=True, min_acc=0.5, znear=1e-2,
+                inside_tol=1e-3, outputs=('flow', 'valid', 'moving'), out=None):
+    """P pairs of frames as ONE library call (durf_render_flow): cams [F,17] host rows, poses [F,K,6] on the device, ext [K,3],
+    distance / acc [F,n] (render_trajectory's planes), pairs [P,2] host ints (source, target) -> dict of the requested `outputs`
+    (FLOW_OUTPUTS), [P,n,.].  out: dict of preallocated contiguous tensors to write into.  The call only enqueues work."""
+    import numpy as np
+    cams = np.ascontiguousarray(np.asarray(cams, np.float32).reshape(-1, 17))
+    pairs = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    F, P, K = int(cams.shape[0]), int(pairs.shape[0]), int(poses.shape[1])
+    n = int(cams[0, 15]) * int(cams[0, 16]) if F else 0
+    dev = distance.device
+    if int(poses.shape[0]) != F or tuple(distance.shape) != (F, n) or tuple(acc.shape) != (F, n):
+        raise ValueError('%d camera rows of %d pixels for poses %s, distance %s, acc %s' %
+                         (F, n, tuple(poses.shape), tuple(distance.shape), tuple(acc.shape)))
+    L = _lib.flow_lib()
+    res = _flow_outputs(outputs, (P, n), dev, out)
+    ck = max(min(int(chunk), max(n, 1)), 1) if chunk > 0 else int(chunk)
+    ws = _workspace(dev, int(L.durf_render_flow_workspace_bytes(ck, K)))
+    with _Timed('render_flow'):
+        _lib.check(L.durf_render_flow(_stream(), F, K, (C.c_float * max(cams.size, 1))(*cams.reshape(-1).tolist()),
+                                      _p(_f32(poses)) if K else None, _p(_f32(ext)) if K else None, _p(box_enable), _p(_f32(distance)),
+                                      _p(_f32(acc)), P, (C.c_int * max(pairs.size, 1))(*pairs.reshape(-1).tolist()), float(near),
+                                      float(far), ck, int(bool(normalise)), float(min_acc), float(znear), float(inside_tol),
+                                      *[_p(res.get(name)) for name in FLOW_OUTPUTS], _p(ws), ws.numel()), 'durf_render_flow')
+    return res

@@ -3,8 +3,8 @@ internal/utils.py:155) and the loop of notebooks/durf_render_traj.ipynb as a com
 
     python -m durf_amd.render_traj --gin_file configs/waymo.gin --data_dir DATA --train_dir CKPT --traj traj.npz --eval_dir OUT
                                    [--cam 0] [--disable_box k ...] [--chunk 8192] [--vis [--vis_near N] [--vis_far F]]
-                                   [--boxes [--box_width W] [--box_opacity A]]
-    python -m durf_amd.render_traj --synthetic --eval_dir OUT [--frames 8] [--traj traj.npz]
+                                   [--boxes [--box_width W] [--box_opacity A]] [--flow]
+    python -m durf_amd.render_traj --synthetic --eval_dir OUT [--frames 8] [--traj traj.npz] [--synthetic_size H W]
 
 The checkpoint in --train_dir is restored, the intrinsics (focal, principal point, image size) are those of image --cam of the
 dataset's test split, the half extents of the boxes are one timestep's for every frame, and the cameras and times come from
@@ -17,7 +17,11 @@ trajectory's distance and acc planes (--vis_near / --vis_far: the planes of the 
 own least and greatest depth).  --boxes adds the frames with the scene's boxes drawn on them, OUT/boxes_%04d.ppm, and the
 boxes' 2D rectangles OUT/boxes2d.npy [F,K,6] (xmin, ymin, xmax, ymax, depth of the centre, visible), from
 durf_amd.overlay.overlay_trajectory on the call's own poses (a box switched off with --disable_box is not drawn; --box_width:
-the lines' width in pixels, --box_opacity: how much of the picture they cover).  --synthetic renders
+the lines' width in pixels, --box_opacity: how much of the picture they cover).  --flow adds how the scene moves from every
+frame to the next (durf_amd.flow, from the call's own distance, acc and poses: no second render): OUT/flow_%04d.flo (Middlebury
+format, unknown where invalid), OUT/flow_%04d.ppm (the Middlebury colour wheel, one scale for the trajectory) and
+OUT/consistency.json -- per pair the count, MSE and PSNR of frame f + 1 warped back onto frame f under the occlusion mask, and
+their means.  --synthetic renders
 train_boxpose.SyntheticTimestepDataset's scene instead (no data directory; without --train_dir the freshly initialised
 model, without --traj a sweep between the scene's first and last camera), which exercises the command end to end."""
 import argparse
@@ -35,6 +39,8 @@ def add_scene_arguments(ap):
     ap.add_argument('--chunk', type=int, default=8192)
     ap.add_argument('--synthetic', action='store_true', help='render the synthetic scene (no data directory needed)')
     ap.add_argument('--objects', type=int, default=3, help='dynamic boxes of the synthetic scene')
+    ap.add_argument('--synthetic_size', type=int, nargs=2, default=None, metavar=('H', 'W'),
+                    help='image size of the synthetic scene (default: the dataset\'s own, 64 x 96)')
     return ap
 
 
@@ -51,6 +57,7 @@ def build_parser():
     ap.add_argument('--boxes', action='store_true', help='also write boxes_%%04d.ppm (the frames with the boxes drawn on) and boxes2d.npy')
     ap.add_argument('--box_width', type=float, default=1.5, help='--boxes: width of the lines in pixels')
     ap.add_argument('--box_opacity', type=float, default=1.0, help='--boxes: opacity of the lines, 0..1')
+    ap.add_argument('--flow', action='store_true', help='also write flow_%%04d.flo, flow_%%04d.ppm (frame f to f + 1) and consistency.json')
     return ap
 
 
@@ -63,7 +70,8 @@ def open_scene(args, split='test'):
     utils.clear_gin()
     config = utils.load_config(args.gin_file, args.gin_param)
     if args.synthetic:
-        dataset = train_boxpose.SyntheticTimestepDataset(config, K=args.objects, device=dev, split=split)
+        size = dict(hw=tuple(args.synthetic_size)) if getattr(args, 'synthetic_size', None) else {}
+        dataset = train_boxpose.SyntheticTimestepDataset(config, K=args.objects, device=dev, split=split, **size)
     else:
         from . import datasets
         dataset = datasets.get_dataset(split, args.data_dir, config, device=dev)
@@ -88,6 +96,35 @@ def write_pictures(eval_dir, pics):
     for name, key in (('depth', 'depth'), ('depth_mod', 'depth_mod'), ('normals', 'depth_normals')):
         for f in range(len(pics[key])):
             trajectory.write_ppm(os.path.join(eval_dir, '%s_%04d.ppm' % (name, f)), pics[key][f])
+
+
+def write_flow(eval_dir, out, cams, ext, near, far, enable, chunk):
+    """--flow: the motion from every frame to the next (durf_amd.flow) -> flow_%04d.flo, flow_%04d.ppm (one colour scale for
+    the whole trajectory) and consistency.json: per pair the count, MSE and PSNR of frame f + 1 warped onto frame f under the
+    occlusion mask, and their means over the pairs that have any visible pixel"""
+    import json
+    import math
+    from . import flow, trajectory
+    kw = dict(near=near, far=far, box_enable=enable, chunk=chunk)
+    fl = flow.render_flow(out, cams, ext, outputs=('flow', 'valid', 'moving', 'target'), **kw)
+    P = len(fl['pairs'])
+    if P == 0:
+        return
+    cons = flow.consistency(flow.warp(fl, out['rgb'], flow.frame_depth(out, cams, ext, **kw)), out['rgb'], fl['pairs'])
+    pics = flow.flow_to_color(fl['flow'], out8=True).cpu().numpy()
+    flows, valid = fl['flow'].cpu().numpy(), fl['valid'].cpu().numpy()
+    for p in range(P):
+        flow.write_flo(os.path.join(eval_dir, 'flow_%04d.flo' % p), flows[p], valid[p])
+        trajectory.write_ppm(os.path.join(eval_dir, 'flow_%04d.ppm' % p), pics[p])
+    cols = {k: [float(x) for x in cons[k].cpu().numpy()] for k in ('count', 'mse', 'psnr')}
+    rows = [dict(source=int(fl['pairs'][p][0]), target=int(fl['pairs'][p][1]), count=cols['count'][p], mse=cols['mse'][p],
+                 psnr=cols['psnr'][p]) for p in range(P)]
+    seen = [r for r in rows if r['count'] > 0]
+    finite = [r['psnr'] for r in seen if math.isfinite(r['psnr'])]
+    mean = dict(count=sum(r['count'] for r in rows) / P, mse=sum(r['mse'] for r in seen) / len(seen) if seen else float('nan'),
+                psnr=sum(finite) / len(finite) if finite else float('nan'))
+    with open(os.path.join(eval_dir, 'consistency.json'), 'w') as f:
+        json.dump(dict(pairs=rows, mean=mean), f, indent=1)
 
 
 def main(argv=None):
@@ -124,9 +161,11 @@ def main(argv=None):
             raise SystemExit('render_traj: --disable_box %s of K = %d boxes' % (bad, K))
         enable = [0 if k in args.disable_box else 1 for k in range(K)]
     cams = trajectory.camera_rows(c2w, focal, (ppx, ppy), int(h), int(w))
+    outputs = ('rgb8', 'distance', 'acc') if args.vis else ('rgb8', 'distance')
+    if args.flow:
+        outputs = ('rgb8', 'rgb', 'distance', 'acc')
     out = model.render_trajectory(variables, cams, times, ext, config.white_bkgd, alpha, near=config.near, far=config.far,
-                                  chunk=args.chunk, box_enable=enable,
-                                  outputs=('rgb8', 'distance', 'acc') if args.vis else ('rgb8', 'distance'))
+                                  chunk=args.chunk, box_enable=enable, outputs=outputs)
     os.makedirs(args.eval_dir, exist_ok=True)
     rgb8 = out['rgb8'].cpu().numpy()
     for f in range(rgb8.shape[0]):
@@ -151,6 +190,8 @@ def main(argv=None):
         for f in range(boxes8.shape[0]):
             trajectory.write_ppm(os.path.join(args.eval_dir, 'boxes_%04d.ppm' % f), boxes8[f])
         np.save(os.path.join(args.eval_dir, 'boxes2d.npy'), drawn['rect'].cpu().numpy())
+    if args.flow:
+        write_flow(args.eval_dir, out, cams, ext, config.near, config.far, enable, args.chunk)
     print('render_traj: %d frames of %d x %d written to %s' % (rgb8.shape[0], int(h), int(w), args.eval_dir))
     return 0
 
