@@ -14,16 +14,19 @@ LIB_PATH = os.environ.get('DURF_LIB_PATH') or os.path.join(_HERE, 'libdurf_hip.s
 OVERLAY_LIB_PATH = os.path.join(_HERE, 'libdurf_overlay.so')        # the box overlay (include/durf_overlay.h), built beside it
 LIDAR_LIB_PATH = os.path.join(_HERE, 'libdurf_lidar.so')            # LIDAR sweeps (include/durf_lidar.h), likewise
 FLOW_LIB_PATH = os.path.join(_HERE, 'libdurf_flow.so')              # motion between frames (include/durf_flow.h), likewise
+FIELD_LIB_PATH = os.path.join(_HERE, 'libdurf_field.so')            # the field at world points (include/durf_field.h), likewise
 
 _lib = None
 _overlay = None
 _lidar = None
 _flow = None
+_field = None
 
 from ._sigs import SIGS as _SIGS       # generated from include/durf_hip.h (tools/gen_integration_stub.py)
 from ._overlay_sigs import SIGS as _OVERLAY_SIGS       # generated from include/durf_overlay.h
 from ._lidar_sigs import SIGS as _LIDAR_SIGS       # generated from include/durf_lidar.h
 from ._flow_sigs import SIGS as _FLOW_SIGS       # generated from include/durf_flow.h
+from ._field_sigs import SIGS as _FIELD_SIGS       # generated from include/durf_field.h
 
 
 def symbols():
@@ -112,6 +115,27 @@ def flow_lib():
             fn.argtypes = args
         _flow = L
     return _flow
+
+
+def field_symbols():
+    """Every symbol include/durf_field.h declares."""
+    return sorted(_FIELD_SIGS)
+
+
+def field_lib():
+    """libdurf_field.so, after libdurf_hip.so (it calls that library and reports errors through its durf_last_error): no fallback either"""
+    global _field
+    if _field is None:
+        lib()
+        if not os.path.exists(FIELD_LIB_PATH):
+            raise RuntimeError('libdurf_field.so not built (%s).  Run __graft_entry__.build().' % FIELD_LIB_PATH)
+        L = C.CDLL(FIELD_LIB_PATH)
+        for name, (res, args) in _FIELD_SIGS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _field = L
+    return _field
 
 
 class DurfError(RuntimeError):

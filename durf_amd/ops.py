@@ -2110,3 +2110,156 @@ def render_flow(cams, poses, ext, distance, acc, pairs, near, far, chunk, *, box
                                       float(far), ck, int(bool(normalise)), float(min_acc), float(znear), float(inside_tol),
                                       *[_p(res.get(name)) for name in FLOW_OUTPUTS], _p(ws), ws.numel()), 'durf_render_flow')
     return res
+
+
+# ---------------------------------------------------------------------------
+# the field at world points (include/durf_field.h, csrc/field.hip, libdurf_field.so): staged calls and the one-call walks
+# ---------------------------------------------------------------------------
+FIELD_ENC_BKGD, FIELD_ENC_OBJ = 60, 63
+
+
+class FieldArgs(C.Structure):
+    """durf_field_args (include/durf_field.h), field for field"""
+    _fields_ = ([('K', C.c_int), ('enc_flags', C.c_int), ('sigma', C.c_float), ('inside_tol', C.c_float), ('density_bias', C.c_float),
+                 ('barf_w', C.c_float * 10), ('bkgd_params', C.c_void_p), ('obj_params', C.c_void_p), ('param_stride', C.c_size_t)] +
+                [(n, C.c_void_p) for n in ('bkgd_wstream', 'obj_wstream', 'const_trunk', 'pose', 'ext', 'box_enable', 'points',
+                                           'viewdirs', 'density', 'rgb', 'raw', 'owner', 'valid')])
+
+
+def _barf_host(alpha):
+    return (C.c_float * 10)(*[float(x) for x in barf_weights(alpha)])
+
+
+def field_classify(points, pose, ext, box_enable=None, inside_tol=0.0):
+    """durf_field_classify: points [n,3], pose [K,6], ext [K,3] -> owner [n] int32 (-1 none, -2 several), local [n,3]"""
+    n, K = int(points.shape[0]), 0 if pose is None else int(pose.shape[0])
+    dev = points.device
+    owner = torch.empty(n, dtype=torch.int32, device=dev)
+    local = torch.empty(n, 3, device=dev)
+    table = torch.empty(max(K, 1) * 12, device=dev)
+    with _Timed('field_classify'):
+        _lib.check(_lib.field_lib().durf_field_classify(_stream(), n, _p(_f32(points)), K, _p(_f32(pose)) if K else None,
+                                                        _p(_f32(ext)) if K else None, _p(box_enable), float(inside_tol), _p(table),
+                                                        _p(owner), _p(local)), 'durf_field_classify')
+    return owner, local
+
+
+def field_lists(owner, K, idx=None, count=None):
+    """durf_field_lists: owner [n] int32 -> idx [(K+1), n] int32 (rows past count[c] untouched), count [K+1] int32"""
+    n, dev = int(owner.shape[0]), owner.device
+    idx = torch.empty(K + 1, n, dtype=torch.int32, device=dev) if idx is None else idx
+    count = torch.zeros(K + 1, dtype=torch.int32, device=dev) if count is None else count
+    assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() >= (K + 1) * n and count.numel() >= K + 1
+    _lib.check(_lib.field_lib().durf_field_lists(_stream(), n, K, _p(owner), _p(idx), _p(count)), 'durf_field_lists')
+    return idx, count
+
+
+def field_owned(idx, count, K):
+    """durf_field_owned: lists 0 .. K-1 one after the other -> owned [n] int32, owned_count [1] int32"""
+    n, dev = int(idx.shape[1]), idx.device
+    owned = torch.empty(n, dtype=torch.int32, device=dev)
+    ocount = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.field_lib().durf_field_owned(_stream(), n, K, _p(idx), _p(count), _p(owned), _p(ocount)), 'durf_field_owned')
+    return owned, ocount
+
+
+def field_encode(local, idx, count, K, sigma=0.0, contraction=True, alpha=10.0, enc_bkgd=None, enc_obj=None):
+    """durf_field_encode -> enc_bkgd [n,60], enc_obj [K,n,63] (fresh buffers are zero filled; rows past count are untouched)"""
+    n, dev = int(local.shape[0]), local.device
+    enc_bkgd = torch.zeros(n, FIELD_ENC_BKGD, device=dev) if enc_bkgd is None else enc_bkgd
+    enc_obj = (torch.zeros(K, n, FIELD_ENC_OBJ, device=dev) if enc_obj is None else enc_obj) if K else None
+    with _Timed('field_encode'):
+        _lib.check(_lib.field_lib().durf_field_encode(_stream(), n, K, _p(_f32(local)), _p(idx), _p(count), float(sigma),
+                                                      ENC_CONTRACT if contraction else 0, _barf_host(alpha), _p(_f32(enc_bkgd)),
+                                                      _p(enc_obj)), 'durf_field_encode')
+    return enc_bkgd, enc_obj
+
+
+def field_activate(idx, count, raw_bkgd, raw_obj, raw_const, owner, density_bias, want_rgb=True, want_raw=True):
+    """durf_field_activate -> density [n], rgb [n,3] or None, raw [n,4] or None, valid [n] uint8"""
+    n, K, dev = int(owner.shape[0]), int(idx.shape[0]) - 1, owner.device
+    density = torch.empty(n, device=dev)
+    rgb = torch.empty(n, 3, device=dev) if want_rgb else None
+    raw = torch.empty(n, 4, device=dev) if want_raw else None
+    valid = torch.empty(n, dtype=torch.uint8, device=dev)
+    with _Timed('field_activate'):
+        _lib.check(_lib.field_lib().durf_field_activate(_stream(), n, K, _p(idx), _p(count), _p(_f32(raw_bkgd)), _p(raw_obj),
+                                                        _p(raw_const), _p(owner), float(density_bias), _p(density), _p(rgb), _p(raw),
+                                                        _p(valid)), 'durf_field_activate')
+    return density, rgb, raw, valid
+
+
+def field_workspace_bytes(chunk, K):
+    return int(_lib.field_lib().durf_field_workspace_bytes(int(chunk), int(K)))
+
+
+def field_args(K, bkgd_params, bkgd_ws, obj_params, param_stride, obj_ws, trunk, pose, ext, box_enable, sigma, alpha, contraction,
+               inside_tol, density_bias):
+    """the parameter half of durf_field_args (the points and the outputs are filled per call) -> (FieldArgs, the tensors it
+    points into: keep them alive until the call is issued)"""
+    a = FieldArgs()
+    a.K, a.enc_flags = int(K), ENC_CONTRACT if contraction else 0
+    a.sigma, a.inside_tol, a.density_bias = float(sigma), float(inside_tol), float(density_bias)
+    a.barf_w = _barf_host(alpha)
+    a.bkgd_params, a.bkgd_wstream = _p(_f32(bkgd_params)), _p(bkgd_ws)
+    if K:
+        a.obj_params, a.param_stride, a.obj_wstream, a.const_trunk = _p(_f32(obj_params)), int(param_stride), _p(obj_ws), _p(trunk)
+        a.pose, a.ext, a.box_enable = _p(_f32(pose)), _p(_f32(ext)), _p(box_enable)
+    return a, (bkgd_params, bkgd_ws, obj_params, obj_ws, trunk, pose, ext, box_enable)
+
+
+def _field_outputs(a, n, dev, want_rgb):
+    out = dict(density=torch.empty(n, device=dev), rgb=torch.empty(n, 3, device=dev) if want_rgb else None,
+               raw=torch.empty(n, 4, device=dev), owner=torch.empty(n, dtype=torch.int32, device=dev),
+               valid=torch.empty(n, dtype=torch.uint8, device=dev))
+    for k, v in out.items():
+        setattr(a, k, _p(v))
+    return out
+
+
+def field_query(a, points, viewdirs, chunk):
+    """durf_field_query: n points in ONE call -> dict density [n], rgb [n,3] (None without viewdirs), raw [n,4], owner [n] int32,
+    valid [n] uint8.  The call only enqueues work."""
+    n, dev = int(points.shape[0]), points.device
+    out = _field_outputs(a, n, dev, viewdirs is not None)
+    a.points, a.viewdirs = _p(_f32(points)), None if viewdirs is None else _p(_f32(viewdirs))
+    ck = max(min(int(chunk), max(n, 1)), 1) if chunk > 0 else int(chunk)
+    L = _lib.field_lib()
+    ws = _workspace(dev, int(L.durf_field_workspace_bytes(ck, a.K)))
+    with _Timed('field_query'):
+        _lib.check(L.durf_field_query(_stream(), C.addressof(a), n, ck, _p(ws), ws.numel()), 'durf_field_query')
+    return out
+
+
+def field_grid(a, origin, du, dv, dw, shape, view, chunk, dev, want_points=False):
+    """durf_field_grid: the grid origin + i du + j dv + k dw (k fastest) of shape (nu, nv, nw) in ONE call -> field_query's
+    dict over the nu nv nw cells[, points [nu nv nw, 3]]; view: one direction (3 floats) or None (density only)"""
+    nu, nv, nw = (int(s) for s in shape)
+    n = nu * nv * nw
+    if min(nu, nv, nw) < 1 or n >= 2 ** 31:
+        raise ValueError('field_grid: a grid of %d x %d x %d cells' % (nu, nv, nw))
+    out = _field_outputs(a, n, dev, view is not None)
+    a.points = a.viewdirs = None
+    out['points'] = torch.empty(n, 3, device=dev) if want_points else None
+    f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])
+    vx, vy, vz = (float(x) for x in view) if view is not None else (0.0, 0.0, 0.0)
+    ck = max(min(int(chunk), n), 1) if chunk > 0 else int(chunk)
+    L = _lib.field_lib()
+    ws = _workspace(dev, int(L.durf_field_workspace_bytes(ck, a.K)))
+    with _Timed('field_grid'):
+        _lib.check(L.durf_field_grid(_stream(), C.addressof(a), f3(origin), f3(du), f3(dv), f3(dw), nu, nv, nw, int(view is not None),
+                                     vx, vy, vz, ck, _p(ws), ws.numel(), _p(out['points'])), 'durf_field_grid')
+    return out
+
+
+def field_columns(density, valid, shape, step, threshold):
+    """durf_field_columns over density / valid [nu nv nw] -> col_max, col_opacity [nu,nv] float, col_first [nu,nv] int32"""
+    nu, nv, nw = (int(s) for s in shape)
+    dev = density.device
+    assert density.numel() == nu * nv * nw and valid.numel() == nu * nv * nw and valid.dtype == torch.uint8 and valid.is_contiguous()
+    cmax, cop = torch.empty(nu, nv, device=dev), torch.empty(nu, nv, device=dev)
+    cfirst = torch.empty(nu, nv, dtype=torch.int32, device=dev)
+    with _Timed('field_columns'):
+        _lib.check(_lib.field_lib().durf_field_columns(_stream(), nu, nv, nw, _p(_f32(density)), _p(valid), float(step), float(threshold),
+                                                       _p(cmax), _p(cop), _p(cfirst)), 'durf_field_columns')
+    return cmax, cop, cfirst

@@ -3,7 +3,7 @@
 embedded in INTEGRATION.md, and the product's own table durf_amd/_sigs.py, so that no copy can drift from the header;
 include/durf_overlay.h (libdurf_overlay.so, a library of its own) -> durf_amd/_overlay_sigs.py,
 include/durf_lidar.h (libdurf_lidar.so) -> durf_amd/_lidar_sigs.py and include/durf_flow.h (libdurf_flow.so) ->
-durf_amd/_flow_sigs.py likewise:
+durf_amd/_flow_sigs.py and include/durf_field.h (libdurf_field.so) -> durf_amd/_field_sigs.py likewise:
     python tools/gen_integration_stub.py            # rewrite both
     python tools/gen_integration_stub.py --check    # exit 1 if either is stale (tests/test_host_logic.py)
 The parser handles exactly the C subset the header uses (scalar / pointer parameters, /* */ comments)."""
@@ -22,6 +22,8 @@ LIDAR_HDR = os.path.join(ROOT, 'include', 'durf_lidar.h')
 LIDAR_SIGS = os.path.join(ROOT, 'durf_amd', '_lidar_sigs.py')      # the binding table of libdurf_lidar.so
 FLOW_HDR = os.path.join(ROOT, 'include', 'durf_flow.h')
 FLOW_SIGS = os.path.join(ROOT, 'durf_amd', '_flow_sigs.py')        # the binding table of libdurf_flow.so
+FIELD_HDR = os.path.join(ROOT, 'include', 'durf_field.h')
+FIELD_SIGS = os.path.join(ROOT, 'durf_amd', '_field_sigs.py')      # the binding table of libdurf_field.so
 BEGIN, END = '<!-- BEGIN GENERATED: tools/gen_integration_stub.py -->', '<!-- END GENERATED -->'
 
 SCALARS = {'int': 'i32', 'float': 'f32', 'size_t': 'u64', 'int32_t': 'i32', 'uint32_t': 'C.c_uint32'}
@@ -37,7 +39,7 @@ def ctype_of(param):
     if stars == 0:
         return SCALARS[base], name
     if stars == 1 and base == 'float' and name in ('barf_w', 'mults', 'cams_host', 'times_host', 'sensor_host', 'sweeps_host',
-                                                     'to_sensor_host', 'cam_a_host', 'cam_b_host'):
+                                                     'to_sensor_host', 'cam_a_host', 'cam_b_host', 'origin_host', 'du_host', 'dv_host', 'dw_host'):
         return 'C.POINTER(f32)', name          # HOST float arrays (documented as such in the header)
     if stars == 1 and base == 'size_t':
         return 'C.POINTER(u64)', name          # HOST array (per-segment row capacities)
@@ -103,6 +105,7 @@ def main():
     overlay_sigs = render_sigs(OVERLAY_HDR, 'libdurf_overlay.so')
     lidar_sigs = render_sigs(LIDAR_HDR, 'libdurf_lidar.so')
     flow_sigs = render_sigs(FLOW_HDR, 'libdurf_flow.so')
+    field_sigs = render_sigs(FIELD_HDR, 'libdurf_field.so')
     doc = open(DOC).read()
     new_doc = doc_with_stub(doc, stub)
     if '--check' in sys.argv:
@@ -110,7 +113,8 @@ def main():
               os.path.exists(SIGS) and open(SIGS).read() == sigs and
               os.path.exists(OVERLAY_SIGS) and open(OVERLAY_SIGS).read() == overlay_sigs and
               os.path.exists(LIDAR_SIGS) and open(LIDAR_SIGS).read() == lidar_sigs and
-              os.path.exists(FLOW_SIGS) and open(FLOW_SIGS).read() == flow_sigs)
+              os.path.exists(FLOW_SIGS) and open(FLOW_SIGS).read() == flow_sigs and
+              os.path.exists(FIELD_SIGS) and open(FIELD_SIGS).read() == field_sigs)
         if not ok:
             print('stale: run python tools/gen_integration_stub.py')
         sys.exit(0 if ok else 1)
@@ -119,6 +123,7 @@ def main():
     open(OVERLAY_SIGS, 'w').write(overlay_sigs)
     open(LIDAR_SIGS, 'w').write(lidar_sigs)
     open(FLOW_SIGS, 'w').write(flow_sigs)
+    open(FIELD_SIGS, 'w').write(field_sigs)
     open(DOC, 'w').write(new_doc)
     print('wrote %s (%d functions) and the block in INTEGRATION.md' % (os.path.relpath(STUB, ROOT), len(parse_header())))
 
