@@ -15,18 +15,21 @@ OVERLAY_LIB_PATH = os.path.join(_HERE, 'libdurf_overlay.so')        # the box ov
 LIDAR_LIB_PATH = os.path.join(_HERE, 'libdurf_lidar.so')            # LIDAR sweeps (include/durf_lidar.h), likewise
 FLOW_LIB_PATH = os.path.join(_HERE, 'libdurf_flow.so')              # motion between frames (include/durf_flow.h), likewise
 FIELD_LIB_PATH = os.path.join(_HERE, 'libdurf_field.so')            # the field at world points (include/durf_field.h), likewise
+MESH_LIB_PATH = os.path.join(_HERE, 'libdurf_mesh.so')              # the iso-surface of a density lattice (include/durf_mesh.h), likewise
 
 _lib = None
 _overlay = None
 _lidar = None
 _flow = None
 _field = None
+_mesh = None
 
 from ._sigs import SIGS as _SIGS       # generated from include/durf_hip.h (tools/gen_integration_stub.py)
 from ._overlay_sigs import SIGS as _OVERLAY_SIGS       # generated from include/durf_overlay.h
 from ._lidar_sigs import SIGS as _LIDAR_SIGS       # generated from include/durf_lidar.h
 from ._flow_sigs import SIGS as _FLOW_SIGS       # generated from include/durf_flow.h
 from ._field_sigs import SIGS as _FIELD_SIGS       # generated from include/durf_field.h
+from ._mesh_sigs import SIGS as _MESH_SIGS       # generated from include/durf_mesh.h
 
 
 def symbols():
@@ -136,6 +139,27 @@ def field_lib():
             fn.argtypes = args
         _field = L
     return _field
+
+
+def mesh_symbols():
+    """Every symbol include/durf_mesh.h declares."""
+    return sorted(_MESH_SIGS)
+
+
+def mesh_lib():
+    """libdurf_mesh.so, after libdurf_hip.so (it reports errors through that library's durf_last_error): no fallback either"""
+    global _mesh
+    if _mesh is None:
+        lib()
+        if not os.path.exists(MESH_LIB_PATH):
+            raise RuntimeError('libdurf_mesh.so not built (%s).  Run __graft_entry__.build().' % MESH_LIB_PATH)
+        L = C.CDLL(MESH_LIB_PATH)
+        for name, (res, args) in _MESH_SIGS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _mesh = L
+    return _mesh
 
 
 class DurfError(RuntimeError):

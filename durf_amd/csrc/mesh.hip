@@ -1,0 +1,502 @@
+// The iso-surface of a density lattice as an indexed triangle mesh (include/durf_mesh.h; libdurf_mesh.so): marching tetrahedra
+// on the Kuhn subdivision with welded vertices.  Classify and count per lattice point (k_mesh_classify), one workgroup's
+// exclusive scan of the block sums (k_mesh_scan), offsets (k_mesh_offsets) -- the three plain passes of durf_lidar_compact --,
+// then emit (k_mesh_emit) and the attribute gather (k_mesh_gather).  Streaming kernels, one thread per lattice point with
+// adjacent lanes along k, plain fp32 in the order the header states; no atomics, nothing synchronises or copies to the host.
+#include "workspace.h"
+#include "../../include/durf_mesh.h"
+
+// a refusal that names the offending value
+#define MESH_REQUIRE(cond, fmt, ...)                                                          \
+    do {                                                                                      \
+        if (!(cond)) {                                                                        \
+            durf_set_error("%s: requirement failed: " fmt, __func__, ##__VA_ARGS__);          \
+            return -1;                                                                        \
+        }                                                                                     \
+    } while (0)
+
+#define MESH_B DURF_MESH_BLOCK
+#define MESH_WAVES (MESH_B / DURF_WAVE)
+#define MESH_SCAN_THREADS 1024
+#define MESH_SCAN_WAVES (MESH_SCAN_THREADS / DURF_WAVE)
+
+// ---- the sixteen cases, built from the header's rule ------------------------------------------------------------------------
+// A cell corner is the code c = 4 di + 2 dj + dk; the edge from corner a to corner b (a's bits a subset of b's) is edge
+// e = b - a - 1 of the lattice point at corner a.  A tetrahedron's edges are the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) of
+// its local corners.
+struct MeshTables {
+    unsigned char corner[6][4];        // cell-corner code of local corner l of tetrahedron t
+    unsigned char eown[6][6];          // cell-corner code of the lattice point that owns tetrahedron edge E
+    unsigned char eedge[6][6];         // and which of its seven edges that is
+    unsigned char ntri[16];            // triangles of case (bit l: local corner l is in)
+    unsigned char tri[6][16][6];       // tetrahedron edges of up to two triangles, wound for a right-handed frame
+    bool ok;                           // no triangle of the construction is degenerate
+};
+
+constexpr int mesh_te(int a, int b) { return a == 0 ? b - 1 : a == 1 ? b + 1 : 5; }      // (a < b) -> 0 .. 5
+
+constexpr MeshTables mesh_make_tables() {
+    MeshTables T{};
+    T.ok = true;
+    const int perm[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+    const int pair[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}};
+    for (int t = 0; t < 6; t++) {
+        T.corner[t][0] = 0;
+        T.corner[t][1] = (unsigned char)(4 >> perm[t][0]);
+        T.corner[t][2] = (unsigned char)(T.corner[t][1] | (4 >> perm[t][1]));
+        T.corner[t][3] = 7;
+        for (int E = 0; E < 6; E++) {
+            const int a = T.corner[t][pair[E][0]], b = T.corner[t][pair[E][1]];
+            T.eown[t][E] = (unsigned char)a;
+            T.eedge[t][E] = (unsigned char)(b - a - 1);
+        }
+        for (int cs = 0; cs < 16; cs++) {
+            int in[4] = {}, out[4] = {}, ni = 0, no = 0;
+            for (int l = 0; l < 4; l++) {
+                if (cs >> l & 1) in[ni++] = l; else out[no++] = l;
+            }
+            int tr[6] = {}, nt = 0;
+            if (ni == 1 || no == 1) {
+                const int a = ni == 1 ? in[0] : out[0];
+                int k = 0;
+                for (int l = 0; l < 4; l++)
+                    if (l != a) tr[k++] = l < a ? mesh_te(l, a) : mesh_te(a, l);
+                nt = 1;
+            } else if (ni == 2) {
+                const int a = in[0], b = in[1], c = out[0], d = out[1];
+                auto e = [](int x, int y) { return x < y ? mesh_te(x, y) : mesh_te(y, x); };
+                const int ac = e(a, c), ad = e(a, d), bd = e(b, d), bc = e(b, c);
+                tr[0] = ac; tr[1] = ad; tr[2] = bd; tr[3] = ac; tr[4] = bd; tr[5] = bc;
+                nt = 2;
+            }
+            if (t == 0) T.ntri[cs] = (unsigned char)nt;
+            // the winding: edge midpoints (twice them, integers) in index space, whose frame is right-handed; the right-hand
+            // normal must point along mean(O) - mean(I) (here scaled by |I| |O|)
+            int dir[3] = {};
+            for (int x = 0; x < 3; x++) {
+                int so = 0, si = 0;
+                for (int l = 0; l < no; l++) so += T.corner[t][out[l]] >> (2 - x) & 1;
+                for (int l = 0; l < ni; l++) si += T.corner[t][in[l]] >> (2 - x) & 1;
+                dir[x] = ni * so - no * si;
+            }
+            for (int r = 0; r < nt; r++) {
+                int M[3][3] = {};
+                for (int v = 0; v < 3; v++)
+                    for (int x = 0; x < 3; x++) {
+                        const int E = tr[3 * r + v];
+                        M[v][x] = (T.corner[t][pair[E][0]] >> (2 - x) & 1) + (T.corner[t][pair[E][1]] >> (2 - x) & 1);
+                    }
+                int u[3] = {}, w[3] = {};
+                for (int x = 0; x < 3; x++) { u[x] = M[1][x] - M[0][x]; w[x] = M[2][x] - M[0][x]; }
+                const int s = (u[1] * w[2] - u[2] * w[1]) * dir[0] + (u[2] * w[0] - u[0] * w[2]) * dir[1] +
+                              (u[0] * w[1] - u[1] * w[0]) * dir[2];
+                if (s == 0) T.ok = false;
+                if (s < 0) { const int x = tr[3 * r + 1]; tr[3 * r + 1] = tr[3 * r + 2]; tr[3 * r + 2] = x; }
+            }
+            for (int q = 0; q < 6; q++) T.tri[t][cs][q] = (unsigned char)tr[q];
+        }
+    }
+    return T;
+}
+
+constexpr bool mesh_parity_rule(const MeshTables& T) {
+    // permutations 0, 3, 4 are even, 1, 2, 5 odd: the winding depends on the case and the parity alone
+    for (int cs = 0; cs < 16; cs++)
+        for (int q = 0; q < 6; q++) {
+            if (T.tri[3][cs][q] != T.tri[0][cs][q] || T.tri[4][cs][q] != T.tri[0][cs][q]) return false;
+            if (T.tri[2][cs][q] != T.tri[1][cs][q] || T.tri[5][cs][q] != T.tri[1][cs][q]) return false;
+        }
+    return true;
+}
+
+constexpr MeshTables MESH_TABLES = mesh_make_tables();
+static_assert(MESH_TABLES.ok, "no case has a degenerate triangle");
+static_assert(mesh_parity_rule(MESH_TABLES), "the winding depends on the case and the parity of the permutation");
+static_assert(MESH_TABLES.ntri[0] == 0 && MESH_TABLES.ntri[15] == 0 && MESH_TABLES.ntri[1] == 1 && MESH_TABLES.ntri[3] == 2 &&
+              MESH_TABLES.ntri[14] == 1, "0, 1 or 2 triangles");
+static_assert(MESH_TABLES.corner[3][1] == 2 && MESH_TABLES.corner[3][2] == 3, "permutation (1,2,0): +j, then +k");
+__constant__ MeshTables c_mesh = MESH_TABLES;
+
+// ---- the lattice ----------------------------------------------------------------------------------------------------------------
+struct MeshDims {
+    int nu, nv, nw, n;
+};
+
+__device__ __forceinline__ bool mesh_usable(const float* __restrict__ density, const uint8_t* __restrict__ valid, int g, float* d) {
+    const float x = density[g];
+    *d = x;
+    return (valid == nullptr || valid[g] != 0) && x == x;
+}
+
+// the eight corners of the cell at (i, j, k): bit c of *exist (the corner is inside the lattice), *usable, *in
+__device__ __forceinline__ void mesh_corners(const MeshDims D, const float* __restrict__ density, const uint8_t* __restrict__ valid,
+                                             float iso, int g, int i, int j, int k, unsigned* exist, unsigned* usable, unsigned* in) {
+    unsigned X = 0, U = 0, N = 0;
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        const int di = c >> 2, dj = c >> 1 & 1, dk = c & 1;
+        if (i + di < D.nu && j + dj < D.nv && k + dk < D.nw) {
+            X |= 1u << c;
+            float d;
+            if (mesh_usable(density, valid, g + (di * D.nv + dj) * D.nw + dk, &d)) {
+                U |= 1u << c;
+                if (d >= iso) N |= 1u << c;
+            }
+        }
+    }
+    *exist = X; *usable = U; *in = N;
+}
+
+__device__ __forceinline__ int wave_incl_scan_i(int v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        int t = __shfl_up(v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
+// pass 1: per lattice point the seven activity bits and the counts of its vertices (into voff) and of its cell's triangles
+// (into toff); per workgroup the two sums
+__global__ void __launch_bounds__(MESH_B)
+k_mesh_classify(const MeshDims D, const float* __restrict__ density, const uint8_t* __restrict__ valid, float iso,
+                int32_t* __restrict__ voff, int32_t* __restrict__ toff, uint8_t* __restrict__ mask, int32_t* __restrict__ sums_v,
+                int32_t* __restrict__ sums_t) {
+    __shared__ int s_v[MESH_WAVES], s_t[MESH_WAVES];
+    const int t = threadIdx.x, lane = t & (DURF_WAVE - 1), g = blockIdx.x * MESH_B + t;
+    int cv = 0, ct = 0;
+    if (g < D.n) {
+        const int k = g % D.nw, r = g / D.nw, j = r % D.nv, i = r / D.nv;
+        unsigned X, U, N;
+        mesh_corners(D, density, valid, iso, g, i, j, k, &X, &U, &N);
+        unsigned m = 0;
+        if (U & 1u) {
+#pragma unroll
+            for (int e = 0; e < 7; e++)
+                if ((U >> (e + 1) & 1u) && ((N >> (e + 1) ^ N) & 1u)) m |= 1u << e;
+        }
+        cv = __popc(m);
+        if (X >> 7 & 1u) {
+#pragma unroll
+            for (int q = 0; q < 6; q++) {
+                const unsigned c1 = c_mesh.corner[q][1], c2 = c_mesh.corner[q][2];
+                if ((U & 1u) && (U >> c1 & 1u) && (U >> c2 & 1u) && (U >> 7 & 1u))
+                    ct += c_mesh.ntri[(N & 1u) | (N >> c1 & 1u) << 1 | (N >> c2 & 1u) << 2 | (N >> 7 & 1u) << 3];
+            }
+        }
+        mask[g] = (uint8_t)m;
+        voff[g] = cv;
+        toff[g] = ct;
+    }
+    const int iv = wave_incl_scan_i(cv, lane), it = wave_incl_scan_i(ct, lane);
+    if (lane == DURF_WAVE - 1) { s_v[t / DURF_WAVE] = iv; s_t[t / DURF_WAVE] = it; }
+    __syncthreads();
+    if (t == 0) {
+        int a = 0, b = 0;
+#pragma unroll
+        for (int v = 0; v < MESH_WAVES; v++) { a += s_v[v]; b += s_t[v]; }
+        sums_v[blockIdx.x] = a;
+        sums_t[blockIdx.x] = b;
+    }
+}
+
+// pass 2: ONE workgroup turns both rows of block sums into their exclusive scans in place; the totals go to counts
+__global__ void __launch_bounds__(MESH_SCAN_THREADS)
+k_mesh_scan(int nb, int32_t* __restrict__ sums_v, int32_t* __restrict__ sums_t, int32_t* __restrict__ counts) {
+    __shared__ int s_v[MESH_SCAN_WAVES], s_t[MESH_SCAN_WAVES];
+    const int t = threadIdx.x, lane = t & (DURF_WAVE - 1), wave = t / DURF_WAVE;
+    int carry_v = 0, carry_t = 0;
+    for (int base = 0; base < nb; base += MESH_SCAN_THREADS) {            // (uniform over the workgroup)
+        const int i = base + t;
+        const int xv = i < nb ? sums_v[i] : 0, xt = i < nb ? sums_t[i] : 0;
+        const int iv = wave_incl_scan_i(xv, lane), it = wave_incl_scan_i(xt, lane);
+        if (lane == DURF_WAVE - 1) { s_v[wave] = iv; s_t[wave] = it; }
+        __syncthreads();
+        int bv = 0, tv = 0, bt = 0, tt = 0;
+#pragma unroll
+        for (int v = 0; v < MESH_SCAN_WAVES; v++) {
+            const int a = s_v[v], b = s_t[v];
+            if (v < wave) { bv += a; bt += b; }
+            tv += a; tt += b;
+        }
+        if (i < nb) {
+            sums_v[i] = carry_v + bv + iv - xv;
+            sums_t[i] = carry_t + bt + it - xt;
+        }
+        carry_v += tv;
+        carry_t += tt;
+        __syncthreads();                                                  // s_v, s_t are rewritten by the next round
+    }
+    if (t == 0) {
+        sums_v[nb] = carry_v;
+        sums_t[nb] = carry_t;
+        counts[0] = carry_v;
+        counts[1] = carry_t;
+    }
+}
+
+// pass 3: the per-point counts in voff and toff become the exclusive prefix sums in g order
+__global__ void __launch_bounds__(MESH_B)
+k_mesh_offsets(int n, int32_t* __restrict__ voff, int32_t* __restrict__ toff, const int32_t* __restrict__ sums_v,
+               const int32_t* __restrict__ sums_t) {
+    __shared__ int s_v[MESH_WAVES], s_t[MESH_WAVES];
+    const int t = threadIdx.x, lane = t & (DURF_WAVE - 1), wave = t / DURF_WAVE, g = blockIdx.x * MESH_B + t;
+    const int cv = g < n ? voff[g] : 0, ct = g < n ? toff[g] : 0;
+    const int iv = wave_incl_scan_i(cv, lane), it = wave_incl_scan_i(ct, lane);
+    if (lane == DURF_WAVE - 1) { s_v[wave] = iv; s_t[wave] = it; }
+    __syncthreads();
+    if (g >= n) return;
+    int av = sums_v[blockIdx.x] + iv - cv, at = sums_t[blockIdx.x] + it - ct;
+#pragma unroll
+    for (int u = 0; u < MESH_WAVES; u++)
+        if (u < wave) { av += s_v[u]; at += s_t[u]; }
+    voff[g] = av;
+    toff[g] = at;
+}
+
+// ---- emit -------------------------------------------------------------------------------------------------------------------
+struct MeshFrame {
+    float o[3], du[3], dv[3], dw[3], A[9];
+};
+
+// the index-space gradient at lattice point (i, j, k), index g, whose density d0 is usable
+__device__ __forceinline__ void mesh_gradient(const MeshDims D, const float* __restrict__ density, const uint8_t* __restrict__ valid,
+                                              int g, int i, int j, int k, float d0, float* gr) {
+    const int at[3] = {i, j, k}, dim[3] = {D.nu, D.nv, D.nw}, stride[3] = {D.nv * D.nw, D.nw, 1};
+#pragma unroll
+    for (int x = 0; x < 3; x++) {
+        float dp = 0.0f, dm = 0.0f;
+        const bool up = at[x] + 1 < dim[x] && mesh_usable(density, valid, g + stride[x], &dp);
+        const bool um = at[x] > 0 && mesh_usable(density, valid, g - stride[x], &dm);
+        gr[x] = up && um ? 0.5f * (dp - dm) : up ? dp - d0 : um ? d0 - dm : 0.0f;
+    }
+}
+
+__global__ void __launch_bounds__(MESH_B)
+k_mesh_emit(const MeshDims D, const float* __restrict__ density, const uint8_t* __restrict__ valid, float iso, const MeshFrame F,
+            int flip, const int32_t* __restrict__ voff, const int32_t* __restrict__ toff, const uint8_t* __restrict__ mask,
+            int max_vertices, int max_triangles, float* __restrict__ vertices, float* __restrict__ normals,
+            int32_t* __restrict__ vertex_edge, float* __restrict__ vertex_t, int32_t* __restrict__ triangles) {
+    const int g = blockIdx.x * MESH_B + threadIdx.x;
+    if (g >= D.n) return;
+    const int k = g % D.nw, r = g / D.nw, j = r % D.nv, i = r / D.nv;
+    // the vertices on this point's active edges
+    const unsigned m = mask[g];
+    if (m) {
+        int id = voff[g];
+        const float da = density[g];
+        float gra[3];
+        if (normals) mesh_gradient(D, density, valid, g, i, j, k, da, gra);
+        for (int e = 0; e < 7; e++) {
+            if (!(m >> e & 1u)) continue;
+            const int v = id++;
+            if ((unsigned)v >= (unsigned)max_vertices) continue;
+            const int di = (e + 1) >> 2, dj = (e + 1) >> 1 & 1, dk = (e + 1) & 1;
+            // an active edge exists: its far end is inside the lattice (bounds: mask comes from k_mesh_classify's own test,
+            // and a stale workspace is caught here)
+            if (i + di >= D.nu || j + dj >= D.nv || k + dk >= D.nw) continue;
+            const int gb = g + (di * D.nv + dj) * D.nw + dk;
+            const float db = density[gb];
+            float t = (iso - da) / (db - da);
+            t = fminf(fmaxf(t, 0.0f), 1.0f);
+            const float q0 = (float)i + t * (float)di, q1 = (float)j + t * (float)dj, q2 = (float)k + t * (float)dk;
+#pragma unroll
+            for (int c = 0; c < 3; c++) vertices[(size_t)v * 3 + c] = ((F.o[c] + q0 * F.du[c]) + q1 * F.dv[c]) + q2 * F.dw[c];
+            if (vertex_edge) { vertex_edge[(size_t)v * 2] = g; vertex_edge[(size_t)v * 2 + 1] = e; }
+            if (vertex_t) vertex_t[v] = t;
+            if (normals) {
+                float grb[3], gr[3], mm[3];
+                mesh_gradient(D, density, valid, gb, i + di, j + dj, k + dk, db, grb);
+#pragma unroll
+                for (int x = 0; x < 3; x++) gr[x] = gra[x] + t * (grb[x] - gra[x]);
+#pragma unroll
+                for (int c = 0; c < 3; c++) mm[c] = (F.A[c * 3] * gr[0] + F.A[c * 3 + 1] * gr[1]) + F.A[c * 3 + 2] * gr[2];
+                const float len = sqrtf((mm[0] * mm[0] + mm[1] * mm[1]) + mm[2] * mm[2]);
+                float nn[3];
+                bool fine = true;
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    nn[c] = -mm[c] / len;
+                    fine = fine && fabsf(nn[c]) <= 3.0e38f;                 // (false for NaN and the infinities)
+                }
+                fine = fine && (nn[0] != 0.0f || nn[1] != 0.0f || nn[2] != 0.0f);
+#pragma unroll
+                for (int c = 0; c < 3; c++) normals[(size_t)v * 3 + c] = fine ? nn[c] : 0.0f;
+            }
+        }
+    }
+    // the triangles of the cell at this point
+    if (i >= D.nu - 1 || j >= D.nv - 1 || k >= D.nw - 1) return;
+    unsigned X, U, N;
+    mesh_corners(D, density, valid, iso, g, i, j, k, &X, &U, &N);
+    int tid = toff[g];
+    for (int q = 0; q < 6; q++) {
+        const unsigned c1 = c_mesh.corner[q][1], c2 = c_mesh.corner[q][2];
+        if (!((U & 1u) && (U >> c1 & 1u) && (U >> c2 & 1u) && (U >> 7 & 1u))) continue;
+        const unsigned cs = (N & 1u) | (N >> c1 & 1u) << 1 | (N >> c2 & 1u) << 2 | (N >> 7 & 1u) << 3;
+        const int nt = c_mesh.ntri[cs];
+        for (int r2 = 0; r2 < nt; r2++) {
+            const int at = tid++;
+            if ((unsigned)at >= (unsigned)max_triangles) continue;
+            int ids[3];
+#pragma unroll
+            for (int v = 0; v < 3; v++) {
+                const int E = c_mesh.tri[q][cs][3 * r2 + v];
+                const int c = c_mesh.eown[q][E], e = c_mesh.eedge[q][E];
+                const int gg = g + ((c >> 2) * D.nv + (c >> 1 & 1)) * D.nw + (c & 1);          // a corner of an existing cell
+                ids[v] = voff[gg] + __popc(mask[gg] & ((1u << e) - 1u));
+            }
+            int32_t* row = triangles + (size_t)at * 3;
+            row[0] = ids[0];
+            row[1] = flip ? ids[2] : ids[1];
+            row[2] = flip ? ids[1] : ids[2];
+        }
+    }
+}
+
+// ---- lattice attributes at the vertices --------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(MESH_B)
+k_mesh_gather(const MeshDims D, const int32_t* __restrict__ counts, int max_vertices, const int32_t* __restrict__ vertex_edge,
+              const float* __restrict__ vertex_t, int C, const float* __restrict__ attr_f, float* __restrict__ out_f,
+              const int32_t* __restrict__ attr_i, const float* __restrict__ density, const uint8_t* __restrict__ valid, float iso,
+              int32_t* __restrict__ out_i) {
+    const int v = blockIdx.x * MESH_B + threadIdx.x;
+    if (v >= max_vertices || v >= counts[0]) return;
+    const int g = vertex_edge[(size_t)v * 2], e = vertex_edge[(size_t)v * 2 + 1];
+    if (g < 0 || g >= D.n || e < 0 || e > 6) return;
+    const int k = g % D.nw, r = g / D.nw, j = r % D.nv, i = r / D.nv;
+    const int di = (e + 1) >> 2, dj = (e + 1) >> 1 & 1, dk = (e + 1) & 1;
+    if (i + di >= D.nu || j + dj >= D.nv || k + dk >= D.nw) return;
+    const int gb = g + (di * D.nv + dj) * D.nw + dk;
+    if (attr_f) {
+        const float t = vertex_t[v];
+        for (int c = 0; c < C; c++) {
+            const float a = attr_f[(size_t)g * C + c], b = attr_f[(size_t)gb * C + c];
+            out_f[(size_t)v * C + c] = a + t * (b - a);
+        }
+    }
+    if (attr_i) {
+        float da;
+        const bool a_in = mesh_usable(density, valid, g, &da) && da >= iso;
+        out_i[v] = attr_i[a_in ? g : gb];
+    }
+}
+
+// ---- launchers ------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct MeshWs {
+    int32_t *voff, *toff;
+    uint8_t* mask;
+    int32_t *sums_v, *sums_t;
+    int nb;
+    size_t total;
+};
+
+MeshWs carve_mesh(void* base, int n) {
+    durf::Carver c{(char*)base, 0};
+    MeshWs w{};
+    w.nb = (int)durf_cdiv((size_t)n, MESH_B);
+    w.voff = (int32_t*)c.take((size_t)n * 4);
+    w.toff = (int32_t*)c.take((size_t)n * 4);
+    w.mask = (uint8_t*)c.take((size_t)n);
+    w.sums_v = (int32_t*)c.take((size_t)2 * (w.nb + 1) * 4);
+    w.sums_t = w.sums_v ? w.sums_v + (w.nb + 1) : nullptr;
+    w.total = c.total();
+    return w;
+}
+
+// -> n, or -1 with the refusal set
+int check_mesh_shape(const char* who, int nu, int nv, int nw) {
+    if (!(nu >= 2 && nv >= 2 && nw >= 2)) {
+        durf_set_error("%s: requirement failed: nu, nv, nw >= 2, nu = %d, nv = %d, nw = %d", who, nu, nv, nw);
+        return -1;
+    }
+    if (!((double)nu * nv * nw < (double)DURF_MESH_MAX_POINTS)) {
+        durf_set_error("%s: requirement failed: nu nv nw < 2^27 lattice points, %d x %d x %d", who, nu, nv, nw);
+        return -1;
+    }
+    return nu * nv * nw;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t durf_mesh_workspace_bytes(int nu, int nv, int nw) {
+    if (!(nu >= 2 && nv >= 2 && nw >= 2) || !((double)nu * nv * nw < (double)DURF_MESH_MAX_POINTS)) return 0;
+    return carve_mesh(nullptr, nu * nv * nw).total;
+}
+
+int durf_mesh_count(void* stream, int nu, int nv, int nw, const float* density, const uint8_t* valid, float iso, void* workspace,
+                    size_t workspace_bytes, int32_t* counts) {
+    const int n = check_mesh_shape(__func__, nu, nv, nw);
+    if (n < 0) return -1;
+    MESH_REQUIRE(iso == iso, "iso is a number, iso = %g", (double)iso);
+    MESH_REQUIRE(density && counts, "density and counts");
+    MESH_REQUIRE(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    const MeshWs w = carve_mesh(workspace, n);
+    int rc = durf::check_workspace(__func__, workspace_bytes, w.total, "durf_mesh_workspace_bytes(%d, %d, %d)", nu, nv, nw);
+    if (rc != 0) return rc;
+    const MeshDims D{nu, nv, nw, n};
+    hipLaunchKernelGGL(k_mesh_classify, dim3(w.nb), dim3(MESH_B), 0, (hipStream_t)stream, D, density, valid, iso, w.voff, w.toff, w.mask,
+                       w.sums_v, w.sums_t);
+    DURF_CHECK_LAUNCH("k_mesh_classify");
+    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(MESH_SCAN_THREADS), 0, (hipStream_t)stream, w.nb, w.sums_v, w.sums_t, counts);
+    DURF_CHECK_LAUNCH("k_mesh_scan");
+    hipLaunchKernelGGL(k_mesh_offsets, dim3(w.nb), dim3(MESH_B), 0, (hipStream_t)stream, n, w.voff, w.toff, w.sums_v, w.sums_t);
+    DURF_CHECK_LAUNCH("k_mesh_offsets");
+    return 0;
+}
+
+int durf_mesh_emit(void* stream, int nu, int nv, int nw, const float* density, const uint8_t* valid, float iso, const float* origin_host,
+                   const float* du_host, const float* dv_host, const float* dw_host, const float* normal_xform_host, int flip,
+                   const void* workspace, size_t workspace_bytes, int max_vertices, int max_triangles, float* vertices, float* normals,
+                   int32_t* vertex_edge, float* vertex_t, int32_t* triangles) {
+    const int n = check_mesh_shape(__func__, nu, nv, nw);
+    if (n < 0) return -1;
+    MESH_REQUIRE(iso == iso, "iso is a number, iso = %g", (double)iso);
+    MESH_REQUIRE(density != nullptr, "density");
+    MESH_REQUIRE(origin_host && du_host && dv_host && dw_host, "origin, du, dv and dw");
+    MESH_REQUIRE(!normals || normal_xform_host, "normals need normal_xform");
+    MESH_REQUIRE(max_vertices >= 0 && max_triangles >= 0, "capacities >= 0, max_vertices = %d, max_triangles = %d", max_vertices,
+                 max_triangles);
+    MESH_REQUIRE(vertices || max_vertices == 0, "vertices for max_vertices = %d", max_vertices);
+    MESH_REQUIRE(triangles || max_triangles == 0, "triangles for max_triangles = %d", max_triangles);
+    MESH_REQUIRE(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    const MeshWs w = carve_mesh(const_cast<void*>(workspace), n);
+    int rc = durf::check_workspace(__func__, workspace_bytes, w.total, "durf_mesh_workspace_bytes(%d, %d, %d)", nu, nv, nw);
+    if (rc != 0) return rc;
+    if (max_vertices == 0 && max_triangles == 0) return 0;
+    MeshFrame F{};
+    for (int c = 0; c < 3; c++) { F.o[c] = origin_host[c]; F.du[c] = du_host[c]; F.dv[c] = dv_host[c]; F.dw[c] = dw_host[c]; }
+    if (normals)
+        for (int c = 0; c < 9; c++) F.A[c] = normal_xform_host[c];
+    const MeshDims D{nu, nv, nw, n};
+    hipLaunchKernelGGL(k_mesh_emit, dim3(w.nb), dim3(MESH_B), 0, (hipStream_t)stream, D, density, valid, iso, F, flip != 0 ? 1 : 0, w.voff,
+                       w.toff, w.mask, max_vertices, max_triangles, max_vertices ? vertices : nullptr, max_vertices ? normals : nullptr,
+                       max_vertices ? vertex_edge : nullptr, max_vertices ? vertex_t : nullptr, triangles);
+    DURF_CHECK_LAUNCH("k_mesh_emit");
+    return 0;
+}
+
+int durf_mesh_gather(void* stream, int nu, int nv, int nw, const int32_t* counts, int max_vertices, const int32_t* vertex_edge,
+                     const float* vertex_t, int C, const float* attr_f, float* out_f, const int32_t* attr_i, const float* density,
+                     const uint8_t* valid, float iso, int32_t* out_i) {
+    const int n = check_mesh_shape(__func__, nu, nv, nw);
+    if (n < 0) return -1;
+    MESH_REQUIRE(max_vertices >= 0, "max_vertices >= 0, max_vertices = %d", max_vertices);
+    MESH_REQUIRE(counts && vertex_edge && vertex_t, "counts, vertex_edge and vertex_t");
+    MESH_REQUIRE(attr_f || attr_i, "at least one attribute");
+    MESH_REQUIRE(!attr_f || (out_f && C >= 1), "attr_f needs out_f and C >= 1, C = %d", C);
+    MESH_REQUIRE(!attr_i || (out_i && density), "attr_i needs out_i and density");
+    MESH_REQUIRE(!attr_i || iso == iso, "iso is a number, iso = %g", (double)iso);
+    if (max_vertices == 0) return 0;
+    const MeshDims D{nu, nv, nw, n};
+    hipLaunchKernelGGL(k_mesh_gather, dim3(durf_cdiv((size_t)max_vertices, MESH_B)), dim3(MESH_B), 0, (hipStream_t)stream, D, counts,
+                       max_vertices, vertex_edge, vertex_t, C, attr_f, out_f, attr_i, density, valid, iso, out_i);
+    DURF_CHECK_LAUNCH("k_mesh_gather");
+    return 0;
+}
+
+}  // extern "C"

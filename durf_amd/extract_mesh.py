@@ -1,0 +1,88 @@
+"""Extract the surface of a trained scene as triangle meshes and write them to a directory:
+
+    python -m durf_amd.extract_mesh --gin_file configs/waymo.gin --data_dir DATA --train_dir CKPT --grid "ox,oy,oz;nu,nv,nw;step"
+                                    --iso V --ts T --eval_dir OUT [--objects] [--obj_step S] [--pad 0.05] [--colour query|grid|none]
+    python -m durf_amd.extract_mesh --synthetic --objects --eval_dir OUT [--grid ...]
+
+--grid: query_field's lattice (the origin of point (0, 0, 0), the point counts along x, y, z and one spacing, in scene units).
+--iso: the density at which a point counts as solid; the default is query_field's --threshold default, so the two commands
+agree.  --ts: the timestep whose box poses hold.  Written: OUT/background.ply (the scene with every box disabled), with
+--objects OUT/object_%02d.ply (box k in its own canonical frame, at spacing --obj_step, default half of the grid's),
+OUT/poses.npy ([T,K,6]: centre and rotation vector of every box at every timestep; object k at time t sits at
+X = c + R^T P) and OUT/mesh.json (counts, frames, iso).  The PLY files are binary little-endian with per-vertex normals and
+colours (durf_amd.mesh.write_ply).  --synthetic meshes train_boxpose.SyntheticTimestepDataset's scene instead (no data
+directory; --synthetic_boxes K boxes, default 3), which exercises the command end to end."""
+import argparse
+import json
+import os
+import sys
+
+from .query_field import build_parser as _field_parser, parse_grid
+from .render_traj import add_scene_arguments, open_scene, restore_model
+
+
+def default_iso():
+    """query_field's --threshold default, whatever it is"""
+    return _field_parser().get_default('threshold')
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(prog='python -m durf_amd.extract_mesh', description=__doc__.split('\n\n')[0], conflict_handler='resolve')
+    add_scene_arguments(ap)
+    ap.add_argument('--objects', dest='write_objects', action='store_true', help='also write one mesh per box, in the box\'s frame')
+    ap.add_argument('--synthetic_boxes', type=int, default=3, help='dynamic boxes of the synthetic scene')
+    ap.add_argument('--grid', default=None, help='"ox,oy,oz;nu,nv,nw;step" (--synthetic default: "-2,-2,-1;32,32,16;0.125")')
+    ap.add_argument('--iso', type=float, default=default_iso(), help='density at which a point is solid (default: query_field\'s --threshold)')
+    ap.add_argument('--ts', type=float, default=0.0, help='timestep of the box poses (fractional: interpolated)')
+    ap.add_argument('--sigma', type=float, default=0.0, help='standard deviation of the isotropic Gaussian at every lattice point')
+    ap.add_argument('--obj_step', type=float, default=None, help='--objects: spacing of the object lattices (default: half the grid\'s)')
+    ap.add_argument('--pad', type=float, default=0.05, help='--objects: the object lattice reaches ext (1 + pad)')
+    ap.add_argument('--colour', choices=('query', 'grid', 'none'), default='query', help='per-vertex colour: the field seen along -normal, '
+                    'the grid\'s own colour interpolated, or none')
+    return ap
+
+
+def _record(m):
+    return dict(vertices=int(m['vertices'].shape[0]), triangles=int(m['triangles'].shape[0]), frame=m['frame'])
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    import numpy as np
+    from . import mesh
+    if not args.synthetic and (args.data_dir is None or args.train_dir is None or args.grid is None):
+        raise SystemExit('extract_mesh: --data_dir, --train_dir and --grid are required (or --synthetic)')
+    try:
+        origin, shape, step = parse_grid(args.grid if args.grid is not None else '-2,-2,-1;32,32,16;0.125')
+    except ValueError as e:
+        raise SystemExit('extract_mesh: %s' % e)
+    if min(shape) < 2:
+        raise SystemExit('extract_mesh: --grid needs at least two points along every axis, got %s' % (shape,))
+    args.objects = args.synthetic_boxes                     # (open_scene's name for the synthetic scene's box count)
+    dev, config, dataset = open_scene(args)
+    ext = dataset.ext if args.synthetic else dataset.peek()['ext']
+    model, variables, alpha = restore_model(args, config, dataset, dev)
+    K = variables.layout.K
+    colour = None if args.colour == 'none' else args.colour
+    kw = dict(sigma=args.sigma, alpha=alpha, chunk=max(args.chunk, 1))
+    os.makedirs(args.eval_dir, exist_ok=True)
+    bg = mesh.extract(model, variables, origin, shape, step=step, iso=args.iso, colour=colour, ts=args.ts, ext=ext if K else None,
+                      box_enable=[0] * K if K else None, **kw)
+    mesh.write_ply(os.path.join(args.eval_dir, 'background.ply'), bg)
+    meta = dict(iso=args.iso, ts=args.ts, sigma=args.sigma, step=step, background=_record(bg), objects=[])
+    if args.write_objects:
+        obj_step = args.obj_step if args.obj_step is not None else 0.5 * step
+        for k in range(K):
+            o = mesh.extract_object(model, variables, k, ext, obj_step, args.iso, ts=args.ts, pad=args.pad, colour=colour, **kw)
+            mesh.write_ply(os.path.join(args.eval_dir, 'object_%02d.ply' % k), o)
+            meta['objects'].append(dict(_record(o), box=k, step=obj_step, world_frame=o['grid']['frame']))
+    np.save(os.path.join(args.eval_dir, 'poses.npy'), variables['params']['box_centers'].detach().cpu().numpy())
+    with open(os.path.join(args.eval_dir, 'mesh.json'), 'w') as f:
+        json.dump(meta, f, indent=1)
+    print('extract_mesh: background %d vertices, %d triangles; %d object meshes; written to %s'
+          % (meta['background']['vertices'], meta['background']['triangles'], len(meta['objects']), args.eval_dir))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -2263,3 +2263,98 @@ def field_columns(density, valid, shape, step, threshold):
         _lib.check(_lib.field_lib().durf_field_columns(_stream(), nu, nv, nw, _p(_f32(density)), _p(valid), float(step), float(threshold),
                                                        _p(cmax), _p(cop), _p(cfirst)), 'durf_field_columns')
     return cmax, cop, cfirst
+
+
+# ---------------------------------------------------------------------------
+# the iso-surface of a density lattice (include/durf_mesh.h, csrc/mesh.hip, libdurf_mesh.so)
+# ---------------------------------------------------------------------------
+MESH_BLOCK = 256                   # DURF_MESH_BLOCK
+
+
+def mesh_workspace_bytes(shape):
+    nu, nv, nw = (int(s) for s in shape)
+    return int(_lib.mesh_lib().durf_mesh_workspace_bytes(nu, nv, nw))
+
+
+def mesh_workspace_views(ws, shape):
+    """voff, toff int32 [n] and mask uint8 [n] of a workspace durf_mesh_count filled (the layout include/durf_mesh.h states)"""
+    n = int(shape[0]) * int(shape[1]) * int(shape[2])
+    up = lambda b: (b + 255) // 256 * 256
+    o1 = up(4 * n)
+    o2 = o1 + up(4 * n)
+    return ws[:4 * n].view(torch.int32), ws[o1:o1 + 4 * n].view(torch.int32), ws[o2:o2 + n]
+
+
+def _mesh_lattice(density, valid, shape):
+    nu, nv, nw = (int(s) for s in shape)
+    n = nu * nv * nw
+    assert density.numel() == n, (tuple(density.shape), shape)
+    if valid is not None:
+        assert valid.dtype == torch.uint8 and valid.is_contiguous() and valid.numel() == n and valid.is_cuda
+    return nu, nv, nw
+
+
+def mesh_count(density, valid, shape, iso, ws=None):
+    """durf_mesh_count: classify, count, scan -> (counts int32 [2] ON THE DEVICE: vertices, triangles; the workspace, a uint8
+    tensor durf_mesh_emit reads).  Three launches, no read-back."""
+    nu, nv, nw = _mesh_lattice(density, valid, shape)
+    dev = density.device
+    L = _lib.mesh_lib()
+    need = int(L.durf_mesh_workspace_bytes(nu, nv, nw))
+    if ws is None:
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    with _Timed('mesh_count'):
+        _lib.check(L.durf_mesh_count(_stream(), nu, nv, nw, _p(_f32(density)), _p(valid), float(iso), _p(ws), ws.numel(), _p(counts)),
+                   'durf_mesh_count')
+    return counts, ws
+
+
+def mesh_emit(density, valid, shape, iso, origin, du, dv, dw, ws, max_vertices, max_triangles, normal_xform=None, flip=False,
+              want_edge=True, want_t=True, out=None):
+    """durf_mesh_emit on the workspace of mesh_count -> dict vertices [max_vertices,3], normals (None without normal_xform),
+    vertex_edge [max_vertices,2] int32, vertex_t [max_vertices], triangles [max_triangles,3] int32.  out: buffers to write
+    into instead of fresh ones (rows at or past a capacity are left as they are)."""
+    nu, nv, nw = _mesh_lattice(density, valid, shape)
+    dev = density.device
+    mv, mt = int(max_vertices), int(max_triangles)
+    o = dict(out or {})
+    o.setdefault('vertices', torch.empty(max(mv, 0), 3, device=dev))
+    o.setdefault('normals', torch.empty(max(mv, 0), 3, device=dev) if normal_xform is not None else None)
+    o.setdefault('vertex_edge', torch.empty(max(mv, 0), 2, dtype=torch.int32, device=dev) if want_edge else None)
+    o.setdefault('vertex_t', torch.empty(max(mv, 0), device=dev) if want_t else None)
+    o.setdefault('triangles', torch.empty(max(mt, 0), 3, dtype=torch.int32, device=dev))
+    for k2, rows in (('vertices', mv), ('normals', mv), ('vertex_edge', mv), ('vertex_t', mv), ('triangles', mt)):
+        assert o[k2] is None or (o[k2].is_contiguous() and o[k2].shape[0] >= rows), k2
+    A = None if normal_xform is None else _host_floats(normal_xform, 9, 'normal_xform')
+    with _Timed('mesh_emit'):
+        _lib.check(_lib.mesh_lib().durf_mesh_emit(
+            _stream(), nu, nv, nw, _p(_f32(density)), _p(valid), float(iso), _host_floats(origin, 3, 'origin'), _host_floats(du, 3, 'du'),
+            _host_floats(dv, 3, 'dv'), _host_floats(dw, 3, 'dw'), A, int(bool(flip)), _p(ws), ws.numel(), mv, mt, _p(o['vertices']),
+            _p(o['normals']), _p(o['vertex_edge']), _p(o['vertex_t']), _p(o['triangles'])), 'durf_mesh_emit')
+    return o
+
+
+def mesh_gather(shape, counts, vertex_edge, vertex_t, attr_f=None, attr_i=None, density=None, valid=None, iso=0.0, out_f=None,
+                out_i=None):
+    """durf_mesh_gather: lattice attributes at the vertices -> (out_f [V,C] = a + t (b - a) or None, out_i [V] int32 = the label
+    of each edge's in end, or None)"""
+    nu, nv, nw = (int(s) for s in shape)
+    n = nu * nv * nw
+    V, dev = int(vertex_edge.shape[0]), vertex_edge.device
+    assert vertex_edge.dtype == torch.int32 and vertex_edge.is_contiguous() and vertex_t.numel() == V
+    Cn = 1
+    if attr_f is not None:
+        attr_f = _f32(attr_f).reshape(n, -1)
+        Cn = int(attr_f.shape[1])
+        out_f = torch.empty(V, Cn, device=dev) if out_f is None else out_f
+    if attr_i is not None:
+        assert attr_i.dtype == torch.int32 and attr_i.is_contiguous() and attr_i.numel() == n and density.numel() == n
+        out_i = torch.empty(V, dtype=torch.int32, device=dev) if out_i is None else out_i
+    if V == 0:                              # an empty surface: its zero-row tensors have no address to hand over
+        return out_f, out_i
+    with _Timed('mesh_gather'):
+        _lib.check(_lib.mesh_lib().durf_mesh_gather(
+            _stream(), nu, nv, nw, _p(counts), V, _p(vertex_edge), _p(_f32(vertex_t)), Cn, _p(attr_f), _p(out_f), _p(attr_i),
+            _p(None if density is None else _f32(density)), _p(valid), float(iso), _p(out_i)), 'durf_mesh_gather')
+    return out_f, out_i

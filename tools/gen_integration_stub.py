@@ -3,7 +3,8 @@
 embedded in INTEGRATION.md, and the product's own table durf_amd/_sigs.py, so that no copy can drift from the header;
 include/durf_overlay.h (libdurf_overlay.so, a library of its own) -> durf_amd/_overlay_sigs.py,
 include/durf_lidar.h (libdurf_lidar.so) -> durf_amd/_lidar_sigs.py and include/durf_flow.h (libdurf_flow.so) ->
-durf_amd/_flow_sigs.py and include/durf_field.h (libdurf_field.so) -> durf_amd/_field_sigs.py likewise:
+durf_amd/_flow_sigs.py, include/durf_field.h (libdurf_field.so) -> durf_amd/_field_sigs.py and include/durf_mesh.h
+(libdurf_mesh.so) -> durf_amd/_mesh_sigs.py likewise:
     python tools/gen_integration_stub.py            # rewrite both
     python tools/gen_integration_stub.py --check    # exit 1 if either is stale (tests/test_host_logic.py)
 The parser handles exactly the C subset the header uses (scalar / pointer parameters, /* */ comments)."""
@@ -24,6 +25,8 @@ FLOW_HDR = os.path.join(ROOT, 'include', 'durf_flow.h')
 FLOW_SIGS = os.path.join(ROOT, 'durf_amd', '_flow_sigs.py')        # the binding table of libdurf_flow.so
 FIELD_HDR = os.path.join(ROOT, 'include', 'durf_field.h')
 FIELD_SIGS = os.path.join(ROOT, 'durf_amd', '_field_sigs.py')      # the binding table of libdurf_field.so
+MESH_HDR = os.path.join(ROOT, 'include', 'durf_mesh.h')
+MESH_SIGS = os.path.join(ROOT, 'durf_amd', '_mesh_sigs.py')        # the binding table of libdurf_mesh.so
 BEGIN, END = '<!-- BEGIN GENERATED: tools/gen_integration_stub.py -->', '<!-- END GENERATED -->'
 
 SCALARS = {'int': 'i32', 'float': 'f32', 'size_t': 'u64', 'int32_t': 'i32', 'uint32_t': 'C.c_uint32'}
@@ -39,7 +42,7 @@ def ctype_of(param):
     if stars == 0:
         return SCALARS[base], name
     if stars == 1 and base == 'float' and name in ('barf_w', 'mults', 'cams_host', 'times_host', 'sensor_host', 'sweeps_host',
-                                                     'to_sensor_host', 'cam_a_host', 'cam_b_host', 'origin_host', 'du_host', 'dv_host', 'dw_host'):
+                                                     'to_sensor_host', 'cam_a_host', 'cam_b_host', 'origin_host', 'du_host', 'dv_host', 'dw_host', 'normal_xform_host'):
         return 'C.POINTER(f32)', name          # HOST float arrays (documented as such in the header)
     if stars == 1 and base == 'size_t':
         return 'C.POINTER(u64)', name          # HOST array (per-segment row capacities)
@@ -106,6 +109,7 @@ def main():
     lidar_sigs = render_sigs(LIDAR_HDR, 'libdurf_lidar.so')
     flow_sigs = render_sigs(FLOW_HDR, 'libdurf_flow.so')
     field_sigs = render_sigs(FIELD_HDR, 'libdurf_field.so')
+    mesh_sigs = render_sigs(MESH_HDR, 'libdurf_mesh.so')
     doc = open(DOC).read()
     new_doc = doc_with_stub(doc, stub)
     if '--check' in sys.argv:
@@ -114,7 +118,8 @@ def main():
               os.path.exists(OVERLAY_SIGS) and open(OVERLAY_SIGS).read() == overlay_sigs and
               os.path.exists(LIDAR_SIGS) and open(LIDAR_SIGS).read() == lidar_sigs and
               os.path.exists(FLOW_SIGS) and open(FLOW_SIGS).read() == flow_sigs and
-              os.path.exists(FIELD_SIGS) and open(FIELD_SIGS).read() == field_sigs)
+              os.path.exists(FIELD_SIGS) and open(FIELD_SIGS).read() == field_sigs and
+              os.path.exists(MESH_SIGS) and open(MESH_SIGS).read() == mesh_sigs)
         if not ok:
             print('stale: run python tools/gen_integration_stub.py')
         sys.exit(0 if ok else 1)
@@ -124,6 +129,7 @@ def main():
     open(LIDAR_SIGS, 'w').write(lidar_sigs)
     open(FLOW_SIGS, 'w').write(flow_sigs)
     open(FIELD_SIGS, 'w').write(field_sigs)
+    open(MESH_SIGS, 'w').write(mesh_sigs)
     open(DOC, 'w').write(new_doc)
     print('wrote %s (%d functions) and the block in INTEGRATION.md' % (os.path.relpath(STUB, ROOT), len(parse_header())))
 
