@@ -16,6 +16,7 @@ LIDAR_LIB_PATH = os.path.join(_HERE, 'libdurf_lidar.so')            # LIDAR swee
 FLOW_LIB_PATH = os.path.join(_HERE, 'libdurf_flow.so')              # motion between frames (include/durf_flow.h), likewise
 FIELD_LIB_PATH = os.path.join(_HERE, 'libdurf_field.so')            # the field at world points (include/durf_field.h), likewise
 MESH_LIB_PATH = os.path.join(_HERE, 'libdurf_mesh.so')              # the iso-surface of a density lattice (include/durf_mesh.h), likewise
+GEOM_LIB_PATH = os.path.join(_HERE, 'libdurf_geom.so')              # distances between point sets (include/durf_geom.h), likewise
 
 _lib = None
 _overlay = None
@@ -23,6 +24,7 @@ _lidar = None
 _flow = None
 _field = None
 _mesh = None
+_geom = None
 
 from ._sigs import SIGS as _SIGS       # generated from include/durf_hip.h (tools/gen_integration_stub.py)
 from ._overlay_sigs import SIGS as _OVERLAY_SIGS       # generated from include/durf_overlay.h
@@ -30,6 +32,7 @@ from ._lidar_sigs import SIGS as _LIDAR_SIGS       # generated from include/durf
 from ._flow_sigs import SIGS as _FLOW_SIGS       # generated from include/durf_flow.h
 from ._field_sigs import SIGS as _FIELD_SIGS       # generated from include/durf_field.h
 from ._mesh_sigs import SIGS as _MESH_SIGS       # generated from include/durf_mesh.h
+from ._geom_sigs import SIGS as _GEOM_SIGS       # generated from include/durf_geom.h
 
 
 def symbols():
@@ -160,6 +163,27 @@ def mesh_lib():
             fn.argtypes = args
         _mesh = L
     return _mesh
+
+
+def geom_symbols():
+    """Every symbol include/durf_geom.h declares."""
+    return sorted(_GEOM_SIGS)
+
+
+def geom_lib():
+    """libdurf_geom.so, after libdurf_hip.so (it reports errors through that library's durf_last_error): no fallback either"""
+    global _geom
+    if _geom is None:
+        lib()
+        if not os.path.exists(GEOM_LIB_PATH):
+            raise RuntimeError('libdurf_geom.so not built (%s).  Run __graft_entry__.build().' % GEOM_LIB_PATH)
+        L = C.CDLL(GEOM_LIB_PATH)
+        for name, (res, args) in _GEOM_SIGS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _geom = L
+    return _geom
 
 
 class DurfError(RuntimeError):

@@ -2358,3 +2358,87 @@ def mesh_gather(shape, counts, vertex_edge, vertex_t, attr_f=None, attr_i=None, 
             _stream(), nu, nv, nw, _p(counts), V, _p(vertex_edge), _p(_f32(vertex_t)), Cn, _p(attr_f), _p(out_f), _p(attr_i),
             _p(None if density is None else _f32(density)), _p(valid), float(iso), _p(out_i)), 'durf_mesh_gather')
     return out_f, out_i
+
+
+# ---------------------------------------------------------------------------
+# distances between point sets, mesh samples (include/durf_geom.h, csrc/geom.hip, libdurf_geom.so)
+# ---------------------------------------------------------------------------
+GEOM_BLOCK = 256                   # DURF_GEOM_BLOCK
+GEOM_STAT_CHUNK = 1024             # DURF_GEOM_STAT_CHUNK
+GEOM_MAX_CELLS = 2048              # DURF_GEOM_MAX_CELLS
+GEOM_MAX_THRESHOLDS = 8            # DURF_GEOM_MAX_THRESHOLDS
+GEOM_STAT_DOUBLES = 13             # DURF_GEOM_STAT_DOUBLES
+GEOM_STAT_FIELDS = ('usable', 'found', 'sum_found', 'sum_sq_found', 'sum_usable')        # then one count per threshold
+
+
+def geom_workspace_bytes(n_queries, n_triangles):
+    return int(_lib.geom_lib().durf_geom_workspace_bytes(int(n_queries), int(n_triangles)))
+
+
+def _geom_points(t, what):
+    assert t.dim() == 2 and t.shape[1] == 3, (what, tuple(t.shape))
+    return _f32(t)
+
+
+def geom_keys(points, origin, inv_cell, dims):
+    """durf_geom_keys: the cell key of every point [n,3] -> int64 [n] (-1: not in the grid)"""
+    n = int(_geom_points(points, 'points').shape[0])
+    keys = torch.empty(n, dtype=torch.int64, device=points.device)
+    with _Timed('geom_keys'):
+        _lib.check(_lib.geom_lib().durf_geom_keys(_stream(), n, _p(points) if n else None, _host_floats(origin, 3, 'origin'), float(inv_cell),
+                                                  int(dims[0]), int(dims[1]), int(dims[2]), _p(keys) if n else None), 'durf_geom_keys')
+    return keys
+
+
+def geom_nearest(query, ref_sorted, ref_keys, ref_index, origin, inv_cell, dims, max_dist):
+    """durf_geom_nearest: per query [q,3] the nearest of the cell-sorted reference points within max_dist -> (dist [q], index [q]
+    int32: the reference point's original index, -1 none within max_dist (dist = max_dist), -2 an unusable query (dist NaN))"""
+    q, m = int(_geom_points(query, 'query').shape[0]), int(_geom_points(ref_sorted, 'ref_sorted').shape[0])
+    assert ref_keys.dtype == torch.int64 and ref_keys.is_contiguous() and ref_keys.numel() == m
+    assert ref_index.dtype == torch.int32 and ref_index.is_contiguous() and ref_index.numel() == m
+    dev = query.device
+    dist, index = torch.empty(q, device=dev), torch.empty(q, dtype=torch.int32, device=dev)
+    z = lambda t, k: _p(t) if k else None                                # (a zero-row tensor has no address to hand over)
+    with _Timed('geom_nearest'):
+        _lib.check(_lib.geom_lib().durf_geom_nearest(
+            _stream(), q, z(query, q), m, z(ref_sorted, m), z(ref_keys, m), z(ref_index, m), _host_floats(origin, 3, 'origin'),
+            float(inv_cell), int(dims[0]), int(dims[1]), int(dims[2]), float(max_dist), z(dist, q), z(index, q)), 'durf_geom_nearest')
+    return dist, index
+
+
+def geom_stats(dist, index, thresholds=(), out=None, ws=None):
+    """durf_geom_stats -> float64 [GEOM_STAT_DOUBLES] ON THE DEVICE (GEOM_STAT_FIELDS, then one count per threshold); out: the
+    row to write into.  Two launches, no read-back."""
+    q = int(dist.numel())
+    assert index.dtype == torch.int32 and index.is_contiguous() and index.numel() == q and _f32(dist) is dist
+    th = [float(t) for t in thresholds]
+    L = _lib.geom_lib()
+    need = int(L.durf_geom_workspace_bytes(q, 0))
+    if ws is None:
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dist.device)
+    if out is None:
+        out = torch.empty(GEOM_STAT_DOUBLES, dtype=torch.float64, device=dist.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == GEOM_STAT_DOUBLES
+    arr = (C.c_float * max(len(th), 1))(*th)
+    with _Timed('geom_stats'):
+        _lib.check(L.durf_geom_stats(_stream(), q, _p(dist) if q else None, _p(index) if q else None, len(th), arr, _p(ws), ws.numel(),
+                                     _p(out)), 'durf_geom_stats')
+    return out
+
+
+def geom_sample_mesh(vertices, triangles, n, ws=None):
+    """durf_geom_sample_mesh: n area-uniform samples of the mesh (vertices [V,3], triangles [T,3] int32) -> (points [n,3], tri [n]
+    int32: the triangle of each sample, total_area float64 [1] on the device)"""
+    V, T, n = int(_geom_points(vertices, 'vertices').shape[0]), int(triangles.shape[0]), int(n)
+    assert triangles.dtype == torch.int32 and triangles.is_contiguous() and triangles.dim() == 2 and triangles.shape[1] == 3
+    dev = vertices.device
+    L = _lib.geom_lib()
+    need = int(L.durf_geom_workspace_bytes(0, T))
+    if ws is None:
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    points, tri = torch.empty(max(n, 0), 3, device=dev), torch.empty(max(n, 0), dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.float64, device=dev)
+    with _Timed('geom_sample_mesh'):
+        _lib.check(L.durf_geom_sample_mesh(_stream(), V, _p(vertices) if V else None, T, _p(triangles) if T else None, n, _p(ws), ws.numel(),
+                                           _p(points) if n > 0 else None, _p(tri) if n > 0 else None, _p(total)), 'durf_geom_sample_mesh')
+    return points, tri, total

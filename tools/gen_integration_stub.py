@@ -4,7 +4,7 @@ embedded in INTEGRATION.md, and the product's own table durf_amd/_sigs.py, so th
 include/durf_overlay.h (libdurf_overlay.so, a library of its own) -> durf_amd/_overlay_sigs.py,
 include/durf_lidar.h (libdurf_lidar.so) -> durf_amd/_lidar_sigs.py and include/durf_flow.h (libdurf_flow.so) ->
 durf_amd/_flow_sigs.py, include/durf_field.h (libdurf_field.so) -> durf_amd/_field_sigs.py and include/durf_mesh.h
-(libdurf_mesh.so) -> durf_amd/_mesh_sigs.py likewise:
+(libdurf_mesh.so) -> durf_amd/_mesh_sigs.py and include/durf_geom.h (libdurf_geom.so) -> durf_amd/_geom_sigs.py likewise:
     python tools/gen_integration_stub.py            # rewrite both
     python tools/gen_integration_stub.py --check    # exit 1 if either is stale (tests/test_host_logic.py)
 The parser handles exactly the C subset the header uses (scalar / pointer parameters, /* */ comments)."""
@@ -27,6 +27,8 @@ FIELD_HDR = os.path.join(ROOT, 'include', 'durf_field.h')
 FIELD_SIGS = os.path.join(ROOT, 'durf_amd', '_field_sigs.py')      # the binding table of libdurf_field.so
 MESH_HDR = os.path.join(ROOT, 'include', 'durf_mesh.h')
 MESH_SIGS = os.path.join(ROOT, 'durf_amd', '_mesh_sigs.py')        # the binding table of libdurf_mesh.so
+GEOM_HDR = os.path.join(ROOT, 'include', 'durf_geom.h')
+GEOM_SIGS = os.path.join(ROOT, 'durf_amd', '_geom_sigs.py')        # the binding table of libdurf_geom.so
 BEGIN, END = '<!-- BEGIN GENERATED: tools/gen_integration_stub.py -->', '<!-- END GENERATED -->'
 
 SCALARS = {'int': 'i32', 'float': 'f32', 'size_t': 'u64', 'int32_t': 'i32', 'uint32_t': 'C.c_uint32'}
@@ -42,7 +44,7 @@ def ctype_of(param):
     if stars == 0:
         return SCALARS[base], name
     if stars == 1 and base == 'float' and name in ('barf_w', 'mults', 'cams_host', 'times_host', 'sensor_host', 'sweeps_host',
-                                                     'to_sensor_host', 'cam_a_host', 'cam_b_host', 'origin_host', 'du_host', 'dv_host', 'dw_host', 'normal_xform_host'):
+                                                     'to_sensor_host', 'cam_a_host', 'cam_b_host', 'origin_host', 'du_host', 'dv_host', 'dw_host', 'normal_xform_host', 'thresholds_host'):
         return 'C.POINTER(f32)', name          # HOST float arrays (documented as such in the header)
     if stars == 1 and base == 'size_t':
         return 'C.POINTER(u64)', name          # HOST array (per-segment row capacities)
@@ -110,6 +112,7 @@ def main():
     flow_sigs = render_sigs(FLOW_HDR, 'libdurf_flow.so')
     field_sigs = render_sigs(FIELD_HDR, 'libdurf_field.so')
     mesh_sigs = render_sigs(MESH_HDR, 'libdurf_mesh.so')
+    geom_sigs = render_sigs(GEOM_HDR, 'libdurf_geom.so')
     doc = open(DOC).read()
     new_doc = doc_with_stub(doc, stub)
     if '--check' in sys.argv:
@@ -119,7 +122,8 @@ def main():
               os.path.exists(LIDAR_SIGS) and open(LIDAR_SIGS).read() == lidar_sigs and
               os.path.exists(FLOW_SIGS) and open(FLOW_SIGS).read() == flow_sigs and
               os.path.exists(FIELD_SIGS) and open(FIELD_SIGS).read() == field_sigs and
-              os.path.exists(MESH_SIGS) and open(MESH_SIGS).read() == mesh_sigs)
+              os.path.exists(MESH_SIGS) and open(MESH_SIGS).read() == mesh_sigs and
+              os.path.exists(GEOM_SIGS) and open(GEOM_SIGS).read() == geom_sigs)
         if not ok:
             print('stale: run python tools/gen_integration_stub.py')
         sys.exit(0 if ok else 1)
@@ -130,6 +134,7 @@ def main():
     open(FLOW_SIGS, 'w').write(flow_sigs)
     open(FIELD_SIGS, 'w').write(field_sigs)
     open(MESH_SIGS, 'w').write(mesh_sigs)
+    open(GEOM_SIGS, 'w').write(geom_sigs)
     open(DOC, 'w').write(new_doc)
     print('wrote %s (%d functions) and the block in INTEGRATION.md' % (os.path.relpath(STUB, ROOT), len(parse_header())))
 
