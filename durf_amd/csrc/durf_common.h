@@ -40,6 +40,15 @@ int* next_ticket();                      // a zeroed device int for one mixed la
         }                                                                    \
     } while (0)
 
+// a refusal that names the offending value
+#define DURF_REQUIREF(cond, fmt, ...)                                                         \
+    do {                                                                                      \
+        if (!(cond)) {                                                                        \
+            durf_set_error("%s: requirement failed: " fmt, __func__, ##__VA_ARGS__);          \
+            return -1;                                                                        \
+        }                                                                                     \
+    } while (0)
+
 static inline unsigned durf_cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
 // ---- device helpers -------------------------------------------------------

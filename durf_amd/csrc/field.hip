@@ -11,17 +11,7 @@
 #include "loss_common.h"
 #include "../../include/durf_field.h"
 
-// a refusal that names the offending value
-#define FIELD_REQUIRE(cond, fmt, ...)                                                         \
-    do {                                                                                      \
-        if (!(cond)) {                                                                        \
-            durf_set_error("%s: requirement failed: " fmt, __func__, ##__VA_ARGS__);          \
-            return -1;                                                                        \
-        }                                                                                     \
-    } while (0)
-
 #define FIELD_THREADS 256
-#define FIELD_POSE_ROW 12            // R row-major, then the centre
 #define FIELD_LIST_THREADS 1024
 #define FIELD_LIST_WAVES (FIELD_LIST_THREADS / DURF_WAVE)
 
@@ -31,13 +21,7 @@ __global__ void __launch_bounds__(64)
 k_field_poses(int K, const float* __restrict__ pose, float* __restrict__ table) {
     const int k = threadIdx.x;
     if (k >= K) return;
-    const float* p = pose + k * 6;
-    float R[9];
-    overlay_aa2matrix(p[3], p[4], p[5], R);
-    float* row = table + k * FIELD_POSE_ROW;          // k < K: inside DURF_FIELD_POSE_FLOATS(K)
-#pragma unroll
-    for (int i = 0; i < 9; i++) row[i] = R[i];
-    row[9] = p[0]; row[10] = p[1]; row[11] = p[2];
+    pose_row_fill(pose + k * 6, table + k * DURF_POSE_ROW);          // k < K: inside DURF_FIELD_POSE_FLOATS(K)
 }
 
 // one thread per point; the box loop runs over k, the same in every lane, so the table and the extents are read at
@@ -54,14 +38,11 @@ k_field_classify(int n, const float* __restrict__ points, int K, const float* __
     const float grow = 1.0f + inside_tol;
     for (int k = 0; k < K; k++) {
         if (enable && enable[k] == 0) continue;      // (uniform)
-        const float* row = table + k * FIELD_POSE_ROW;
-        const float d0 = X0 - row[9], d1 = X1 - row[10], d2 = X2 - row[11];
-        const float P0 = (row[0] * d0 + row[1] * d1) + row[2] * d2;
-        const float P1 = (row[3] * d0 + row[4] * d1) + row[5] * d2;
-        const float P2 = (row[6] * d0 + row[7] * d1) + row[8] * d2;
-        const bool in = fabsf(P0) <= ext[k * 3 + 0] * grow && fabsf(P1) <= ext[k * 3 + 1] * grow &&
-                        fabsf(P2) <= ext[k * 3 + 2] * grow;
-        if (in) { nin++; own = k; L0 = P0; L1 = P1; L2 = P2; }
+        float P[3];
+        pose_to_box(table + k * DURF_POSE_ROW, X0, X1, X2, P);
+        const bool in = fabsf(P[0]) <= ext[k * 3 + 0] * grow && fabsf(P[1]) <= ext[k * 3 + 1] * grow &&
+                        fabsf(P[2]) <= ext[k * 3 + 2] * grow;
+        if (in) { nin++; own = k; L0 = P[0]; L1 = P[1]; L2 = P[2]; }
     }
     if (nin > 1) { own = -2; L0 = X0; L1 = X1; L2 = X2; }
     owner[r] = own;
@@ -367,10 +348,10 @@ int durf_field_classify(void* stream, int n, const float* points, int K, const f
                         float inside_tol, float* pose_scratch, int32_t* owner, float* local) {
     int rc = check_field_K(__func__, n, K);
     if (rc != 0) return rc;
-    FIELD_REQUIRE(inside_tol >= 0.0f, "inside_tol >= 0, inside_tol = %g", (double)inside_tol);
+    DURF_REQUIREF(inside_tol >= 0.0f, "inside_tol >= 0, inside_tol = %g", (double)inside_tol);
     if (n == 0) return 0;
-    FIELD_REQUIRE(points && owner && local, "points, owner and local");
-    FIELD_REQUIRE(K == 0 || (pose && ext && pose_scratch), "pose, ext and pose_scratch for K = %d", K);
+    DURF_REQUIREF(points && owner && local, "points, owner and local");
+    DURF_REQUIREF(K == 0 || (pose && ext && pose_scratch), "pose, ext and pose_scratch for K = %d", K);
     if (K > 0) {
         hipLaunchKernelGGL(k_field_poses, dim3(1), dim3(64), 0, (hipStream_t)stream, K, pose, pose_scratch);
         DURF_CHECK_LAUNCH("k_field_poses");
@@ -385,7 +366,7 @@ int durf_field_lists(void* stream, int n, int K, const int32_t* owner, int32_t* 
     int rc = check_field_K(__func__, n, K);
     if (rc != 0) return rc;
     if (n == 0) return 0;
-    FIELD_REQUIRE(owner && idx && count, "owner, idx and count");
+    DURF_REQUIREF(owner && idx && count, "owner, idx and count");
     hipLaunchKernelGGL(k_field_lists, dim3(K + 1), dim3(FIELD_LIST_THREADS), 0, (hipStream_t)stream, n, K, owner, idx, count);
     DURF_CHECK_LAUNCH("k_field_lists");
     return 0;
@@ -395,7 +376,7 @@ int durf_field_owned(void* stream, int n, int K, const int32_t* idx, const int32
     int rc = check_field_K(__func__, n, K);
     if (rc != 0) return rc;
     if (n == 0 || K == 0) return 0;
-    FIELD_REQUIRE(idx && count && owned && owned_count, "idx, count, owned and owned_count");
+    DURF_REQUIREF(idx && count && owned && owned_count, "idx, count, owned and owned_count");
     hipLaunchKernelGGL(k_field_owned, dim3(durf_cdiv(n, FIELD_THREADS), K), dim3(FIELD_THREADS), 0, (hipStream_t)stream, n, K, idx, count,
                        owned, owned_count);
     DURF_CHECK_LAUNCH("k_field_owned");
@@ -406,12 +387,12 @@ int durf_field_encode(void* stream, int n, int K, const float* points_or_local, 
                       int enc_flags, const float* barf_w, float* enc_bkgd, float* enc_obj) {
     int rc = check_field_K(__func__, n, K);
     if (rc != 0) return rc;
-    FIELD_REQUIRE(sigma >= 0.0f, "sigma >= 0, sigma = %g", (double)sigma);
-    FIELD_REQUIRE((enc_flags & ~DURF_ENC_CONTRACT) == 0, "enc_flags is 0 or DURF_ENC_CONTRACT, enc_flags = %d", enc_flags);
+    DURF_REQUIREF(sigma >= 0.0f, "sigma >= 0, sigma = %g", (double)sigma);
+    DURF_REQUIREF((enc_flags & ~DURF_ENC_CONTRACT) == 0, "enc_flags is 0 or DURF_ENC_CONTRACT, enc_flags = %d", enc_flags);
     if (n == 0) return 0;
-    FIELD_REQUIRE(points_or_local && idx && count, "points_or_local, idx and count");
-    FIELD_REQUIRE(enc_bkgd || enc_obj, "at least one output");
-    FIELD_REQUIRE(!(enc_obj && K > 0) || barf_w, "barf_w for the object rows");
+    DURF_REQUIREF(points_or_local && idx && count, "points_or_local, idx and count");
+    DURF_REQUIREF(enc_bkgd || enc_obj, "at least one output");
+    DURF_REQUIREF(!(enc_obj && K > 0) || barf_w, "barf_w for the object rows");
     return launch_encode(stream, n, K, points_or_local, idx, count, sigma, enc_flags, barf_w, enc_bkgd, enc_obj);
 }
 
@@ -421,9 +402,9 @@ int durf_field_activate(void* stream, int n, int K, const int32_t* idx, const in
     int rc = check_field_K(__func__, n, K);
     if (rc != 0) return rc;
     if (n == 0) return 0;
-    FIELD_REQUIRE(idx && count && raw_bkgd && owner && density && valid, "idx, count, raw_bkgd, owner, density and valid");
-    FIELD_REQUIRE(K == 0 || (raw_obj && raw_const), "raw_obj and raw_const for K = %d", K);
-    FIELD_REQUIRE((((size_t)raw_bkgd | (size_t)raw_obj | (size_t)raw_const) & 15) == 0, "the raw inputs are 16-byte aligned");
+    DURF_REQUIREF(idx && count && raw_bkgd && owner && density && valid, "idx, count, raw_bkgd, owner, density and valid");
+    DURF_REQUIREF(K == 0 || (raw_obj && raw_const), "raw_obj and raw_const for K = %d", K);
+    DURF_REQUIREF((((size_t)raw_bkgd | (size_t)raw_obj | (size_t)raw_const) & 15) == 0, "the raw inputs are 16-byte aligned");
     hipLaunchKernelGGL(k_field_activate, dim3(durf_cdiv(n, FIELD_THREADS), K + 2), dim3(FIELD_THREADS), 0, (hipStream_t)stream, n, K, idx,
                        count, raw_bkgd, raw_obj, raw_const, owner, density_bias, density, rgb, raw, valid);
     DURF_CHECK_LAUNCH("k_field_activate");
@@ -436,7 +417,7 @@ int durf_field_query(void* stream, const durf_field_args* a, int n, int chunk, v
     int rc = check_field_args(__func__, a, n, chunk, false);
     if (rc != 0) return rc;
     if (n == 0) return 0;
-    FIELD_REQUIRE(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
     const FieldWs w = carve_field(workspace, chunk, a->K);
     rc = durf::check_workspace("durf_field_query", workspace_bytes, w.total, "durf_field_workspace_bytes(%d, %d)", chunk, a->K);
     if (rc != 0) return rc;
@@ -457,15 +438,15 @@ int durf_field_query(void* stream, const durf_field_args* a, int n, int chunk, v
 int durf_field_grid(void* stream, const durf_field_args* a, const float* origin_host, const float* du_host, const float* dv_host,
                     const float* dw_host, int nu, int nv, int nw, int has_view, float view_x, float view_y, float view_z, int chunk,
                     void* workspace, size_t workspace_bytes, float* points_out) {
-    FIELD_REQUIRE(nu >= 1 && nv >= 1 && nw >= 1 && nu <= (1 << 24) && nv <= (1 << 24) && nw <= (1 << 24),
+    DURF_REQUIREF(nu >= 1 && nv >= 1 && nw >= 1 && nu <= (1 << 24) && nv <= (1 << 24) && nw <= (1 << 24),
                   "1 <= nu, nv, nw <= 2^24, nu = %d, nv = %d, nw = %d", nu, nv, nw);
     const long long total = (long long)nu * nv * nw;
-    FIELD_REQUIRE((double)nu * nv * nw < 2147483648.0, "nu nv nw < 2^31, nu = %d, nv = %d, nw = %d", nu, nv, nw);
+    DURF_REQUIREF((double)nu * nv * nw < 2147483648.0, "nu nv nw < 2^31, nu = %d, nv = %d, nw = %d", nu, nv, nw);
     int rc = check_field_args(__func__, a, (int)total, chunk, true);
     if (rc != 0) return rc;
-    FIELD_REQUIRE(origin_host && du_host && dv_host && dw_host, "origin, du, dv and dw");
-    FIELD_REQUIRE(has_view || !a->rgb, "rgb needs a view direction (has_view == 0 is a density-only query)");
-    FIELD_REQUIRE(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    DURF_REQUIREF(origin_host && du_host && dv_host && dw_host, "origin, du, dv and dw");
+    DURF_REQUIREF(has_view || !a->rgb, "rgb needs a view direction (has_view == 0 is a density-only query)");
+    DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
     const FieldWs w = carve_field(workspace, chunk, a->K);
     rc = durf::check_workspace("durf_field_grid", workspace_bytes, w.total, "durf_field_workspace_bytes(%d, %d)", chunk, a->K);
     if (rc != 0) return rc;
@@ -500,11 +481,11 @@ int durf_field_grid(void* stream, const durf_field_args* a, const float* origin_
 
 int durf_field_columns(void* stream, int nu, int nv, int nw, const float* density, const uint8_t* valid, float step, float threshold,
                        float* col_max, float* col_opacity, int32_t* col_first) {
-    FIELD_REQUIRE(nu >= 1 && nv >= 1 && nw >= 1 && (double)nu * nv * nw < 2147483648.0, "nu, nv, nw >= 1 and nu nv nw < 2^31, %d x %d x %d",
+    DURF_REQUIREF(nu >= 1 && nv >= 1 && nw >= 1 && (double)nu * nv * nw < 2147483648.0, "nu, nv, nw >= 1 and nu nv nw < 2^31, %d x %d x %d",
                   nu, nv, nw);
-    FIELD_REQUIRE(step >= 0.0f, "step >= 0, step = %g", (double)step);
-    FIELD_REQUIRE(density && valid, "density and valid");
-    FIELD_REQUIRE(col_max || col_opacity || col_first, "at least one output");
+    DURF_REQUIREF(step >= 0.0f, "step >= 0, step = %g", (double)step);
+    DURF_REQUIREF(density && valid, "density and valid");
+    DURF_REQUIREF(col_max || col_opacity || col_first, "at least one output");
     const int ncol = nu * nv;
     hipLaunchKernelGGL(k_field_columns, dim3(durf_cdiv(ncol, FIELD_THREADS)), dim3(FIELD_THREADS), 0, (hipStream_t)stream, ncol, nw, density,
                        valid, step, threshold, col_max, col_opacity, col_first);

@@ -8,17 +8,7 @@
 #include "aa2matrix.h"
 #include "../../include/durf_flow.h"
 
-// a refusal that names the offending value
-#define FLOW_REQUIRE(cond, fmt, ...)                                                          \
-    do {                                                                                      \
-        if (!(cond)) {                                                                        \
-            durf_set_error("%s: requirement failed: " fmt, __func__, ##__VA_ARGS__);          \
-            return -1;                                                                        \
-        }                                                                                     \
-    } while (0)
-
 #define FLOW_THREADS 256
-#define FLOW_POSE_ROW 12            // R row-major, then the centre
 
 // ---- where a pixel goes -----------------------------------------------------------------------------------------------------
 struct FlowCams {
@@ -36,30 +26,17 @@ k_flow_poses(int K, const float* __restrict__ pose_a, const float* __restrict__ 
     const int j = threadIdx.x;
     if (j >= 2 * K) return;
     const int s = j / K, k = j - s * K;
-    const float* p = (s ? pose_b : pose_a) + k * 6;
-    float R[9];
-    overlay_aa2matrix(p[3], p[4], p[5], R);
-    float* row = table + j * FLOW_POSE_ROW;        // j < 2 K: inside DURF_FLOW_POSE_FLOATS(K)
-#pragma unroll
-    for (int i = 0; i < 9; i++) row[i] = R[i];
-    row[9] = p[0]; row[10] = p[1]; row[11] = p[2];
+    pose_row_fill((s ? pose_b : pose_a) + k * 6, table + j * DURF_POSE_ROW);        // j < 2 K: inside DURF_FLOW_POSE_FLOATS(K)
 }
 
 // picture-space position and depth of a world point in a camera (the overlay's convention)
 __device__ __forceinline__ void flow_project(const float* cam, float X0, float X1, float X2, float& xp, float& yp, float& z) {
-    const float d0 = X0 - cam[3], d1 = X1 - cam[7], d2 = X2 - cam[11];
-    const float p0 = (cam[0] * d0 + cam[4] * d1) + cam[8] * d2;
-    const float p1 = (cam[1] * d0 + cam[5] * d1) + cam[9] * d2;
-    const float p2 = (cam[2] * d0 + cam[6] * d1) + cam[10] * d2;
-    z = -p2;
-    xp = cam[13] + (cam[12] * p0) / z;
-    yp = cam[14] - (cam[12] * p1) / z;
-}
-
-// c + R^T P of one row of the pose table
-__device__ __forceinline__ void flow_to_world(const float* row, float P0, float P1, float P2, float* X) {
-#pragma unroll
-    for (int j = 0; j < 3; j++) X[j] = row[9 + j] + ((row[j] * P0 + row[3 + j] * P1) + row[6 + j] * P2);
+    const float X[3] = {X0, X1, X2};
+    float p[3];
+    overlay_to_camera(cam, X, p);
+    z = -p[2];
+    xp = cam[13] + (cam[12] * p[0]) / z;
+    yp = cam[14] - (cam[12] * p[1]) / z;
 }
 
 // one thread per pixel: consecutive lanes read and write consecutive pixels.  The box loop runs over k, the same in every lane,
@@ -85,8 +62,8 @@ k_flow_points(int n, int first, int w, int K, const float* __restrict__ origins_
         const bool h = live && hit[r * K + k] != 0;
         if (__ballot(h) != 0ull) {                   // (uniform over the wave)
             float A[3], B[3];
-            flow_to_world(table + k * FLOW_POSE_ROW, P0, P1, P2, A);
-            flow_to_world(table + (K + k) * FLOW_POSE_ROW, P0, P1, P2, B);
+            pose_to_world(table + k * DURF_POSE_ROW, P0, P1, P2, A);
+            pose_to_world(table + (K + k) * DURF_POSE_ROW, P0, P1, P2, B);
             const bool in = fabsf(P0) <= ext[k * 3 + 0] * grow && fabsf(P1) <= ext[k * 3 + 1] * grow &&
                             fabsf(P2) <= ext[k * 3 + 2] * grow;
 #pragma unroll
@@ -324,19 +301,19 @@ int durf_flow_points(void* stream, int n, int first, int K, const float* origins
                      const float* pose_b, const float* ext, int normalise, float min_acc, float znear, float inside_tol,
                      float* pose_scratch, float* flow, float* scene_flow, float* xyz, float* target, float* zcam, int32_t* moving,
                      int32_t* valid) {
-    FLOW_REQUIRE(n >= 0 && first >= 0, "n >= 0 and first >= 0, n = %d, first = %d", n, first);
+    DURF_REQUIREF(n >= 0 && first >= 0, "n >= 0 and first >= 0, n = %d, first = %d", n, first);
     int rc = check_flow_scalars(__func__, K, znear, inside_tol);
     if (rc != 0) return rc;
-    FLOW_REQUIRE(cam_a_host && cam_b_host, "the two camera rows");
-    FLOW_REQUIRE(cam_a_host[15] >= 1.0f && cam_a_host[16] >= 1.0f && (double)cam_a_host[15] * cam_a_host[16] < 2147483648.0,
+    DURF_REQUIREF(cam_a_host && cam_b_host, "the two camera rows");
+    DURF_REQUIREF(cam_a_host[15] >= 1.0f && cam_a_host[16] >= 1.0f && (double)cam_a_host[15] * cam_a_host[16] < 2147483648.0,
                  "an image of h >= 1, w >= 1, h w < 2^31, h = %g, w = %g", (double)cam_a_host[15], (double)cam_a_host[16]);
     const long long hw = (long long)(int)cam_a_host[15] * (int)cam_a_host[16];
-    FLOW_REQUIRE((long long)first + n <= hw, "pixels [first, first + n) inside the image, first = %d, n = %d, h w = %lld", first, n, hw);
+    DURF_REQUIREF((long long)first + n <= hw, "pixels [first, first + n) inside the image, first = %d, n = %d, h w = %lld", first, n, hw);
     if (n == 0) return 0;
-    FLOW_REQUIRE(flow || scene_flow || xyz || target || zcam || moving || valid, "at least one output");
-    FLOW_REQUIRE(origins_s && dirs_s && t && acc, "origins_s, dirs_s, t and acc");
-    FLOW_REQUIRE(K == 0 || (hit && pose_a && pose_b && ext && pose_scratch), "hit, pose_a, pose_b, ext and pose_scratch for K = %d", K);
-    FLOW_REQUIRE(((size_t)flow & 7) == 0, "flow is 8-byte aligned");
+    DURF_REQUIREF(flow || scene_flow || xyz || target || zcam || moving || valid, "at least one output");
+    DURF_REQUIREF(origins_s && dirs_s && t && acc, "origins_s, dirs_s, t and acc");
+    DURF_REQUIREF(K == 0 || (hit && pose_a && pose_b && ext && pose_scratch), "hit, pose_a, pose_b, ext and pose_scratch for K = %d", K);
+    DURF_REQUIREF(((size_t)flow & 7) == 0, "flow is 8-byte aligned");
     FlowCams cams;
     for (int i = 0; i < 17; i++) { cams.a[i] = cam_a_host[i]; cams.b[i] = cam_b_host[i]; }
     if ((rc = launch_flow_poses(stream, K, pose_a, pose_b, pose_scratch)) != 0) return rc;
@@ -347,14 +324,14 @@ int durf_flow_points(void* stream, int n, int first, int K, const float* origins
 
 int durf_flow_warp(void* stream, int n, int h, int w, int C, const float* target, const int32_t* valid, const float* img_b,
                    const float* zcam_b, float occ_rel, float occ_abs, float* warped, int32_t* mask) {
-    FLOW_REQUIRE(n >= 0, "n >= 0, n = %d", n);
-    FLOW_REQUIRE(h >= 1 && w >= 1 && (long long)h * w < 2147483648ll, "h >= 1, w >= 1, h w < 2^31, h = %d, w = %d", h, w);
-    FLOW_REQUIRE(C == 1 || C == 3, "C is 1 or 3, C = %d", C);
-    FLOW_REQUIRE(occ_rel >= 0.0f && occ_abs >= 0.0f, "occ_rel >= 0 and occ_abs >= 0, occ_rel = %g, occ_abs = %g", (double)occ_rel,
+    DURF_REQUIREF(n >= 0, "n >= 0, n = %d", n);
+    DURF_REQUIREF(h >= 1 && w >= 1 && (long long)h * w < 2147483648ll, "h >= 1, w >= 1, h w < 2^31, h = %d, w = %d", h, w);
+    DURF_REQUIREF(C == 1 || C == 3, "C is 1 or 3, C = %d", C);
+    DURF_REQUIREF(occ_rel >= 0.0f && occ_abs >= 0.0f, "occ_rel >= 0 and occ_abs >= 0, occ_rel = %g, occ_abs = %g", (double)occ_rel,
                  (double)occ_abs);
     if (n == 0) return 0;
-    FLOW_REQUIRE(warped || mask, "at least one output");
-    FLOW_REQUIRE(target && valid && img_b && zcam_b, "target, valid, img_b and zcam_b");
+    DURF_REQUIREF(warped || mask, "at least one output");
+    DURF_REQUIREF(target && valid && img_b && zcam_b, "target, valid, img_b and zcam_b");
     const dim3 grid(durf_cdiv(n, FLOW_THREADS)), block(FLOW_THREADS);
     if (C == 1)
         hipLaunchKernelGGL(k_flow_warp<1>, grid, block, 0, (hipStream_t)stream, n, h, w, target, valid, img_b, zcam_b, occ_rel, occ_abs,
@@ -368,11 +345,11 @@ int durf_flow_warp(void* stream, int n, int h, int w, int C, const float* target
 
 int durf_flow_consistency(void* stream, int P, int m, int C, const float* warped, const float* img_a, const int32_t* mask, float* out,
                           float* scratch) {
-    FLOW_REQUIRE(P >= 0 && P <= 65535, "0 <= P <= 65535 (the pair is the grid's y), P = %d", P);
-    FLOW_REQUIRE(m >= 1, "m >= 1 pixels, m = %d", m);
-    FLOW_REQUIRE(C == 1 || C == 3, "C is 1 or 3, C = %d", C);
+    DURF_REQUIREF(P >= 0 && P <= 65535, "0 <= P <= 65535 (the pair is the grid's y), P = %d", P);
+    DURF_REQUIREF(m >= 1, "m >= 1 pixels, m = %d", m);
+    DURF_REQUIREF(C == 1 || C == 3, "C is 1 or 3, C = %d", C);
     if (P == 0) return 0;
-    FLOW_REQUIRE(warped && img_a && mask && out && scratch, "warped, img_a, mask, out and scratch");
+    DURF_REQUIREF(warped && img_a && mask && out && scratch, "warped, img_a, mask, out and scratch");
     const int G = DURF_FLOW_CONS_GROUPS(m);
     const dim3 grid(G, P), block(FLOW_THREADS);
     if (C == 1)
@@ -386,11 +363,11 @@ int durf_flow_consistency(void* stream, int P, int m, int C, const float* warped
 }
 
 int durf_flow_color(void* stream, int n, const float* flow, float max_mag, float* rgb, uint8_t* rgb8) {
-    FLOW_REQUIRE(n >= 0, "n >= 0, n = %d", n);
-    FLOW_REQUIRE(max_mag > 0.0f, "max_mag > 0, max_mag = %g", (double)max_mag);
+    DURF_REQUIREF(n >= 0, "n >= 0, n = %d", n);
+    DURF_REQUIREF(max_mag > 0.0f, "max_mag > 0, max_mag = %g", (double)max_mag);
     if (n == 0) return 0;
-    FLOW_REQUIRE(rgb || rgb8, "at least one output");
-    FLOW_REQUIRE(flow != nullptr && ((size_t)flow & 7) == 0, "flow is given and 8-byte aligned");
+    DURF_REQUIREF(rgb || rgb8, "at least one output");
+    DURF_REQUIREF(flow != nullptr && ((size_t)flow & 7) == 0, "flow is given and 8-byte aligned");
     hipLaunchKernelGGL(k_flow_color, dim3(durf_cdiv(n, FLOW_THREADS)), dim3(FLOW_THREADS), 0, (hipStream_t)stream, n, flow, max_mag, rgb,
                        rgb8);
     DURF_CHECK_LAUNCH("k_flow_color");
@@ -403,28 +380,28 @@ int durf_render_flow(void* stream, int F, int K, const float* cams_host, const f
                      const float* distance, const float* acc, int P, const int* pairs_host, float near, float far, int chunk,
                      int normalise, float min_acc, float znear, float inside_tol, float* flow, float* scene_flow, float* xyz,
                      float* target, float* zcam, int32_t* moving, int32_t* valid, void* workspace, size_t workspace_bytes) {
-    FLOW_REQUIRE(F > 0, "F > 0 frames, F = %d", F);
-    FLOW_REQUIRE(P > 0, "P > 0 pairs, P = %d", P);
+    DURF_REQUIREF(F > 0, "F > 0 frames, F = %d", F);
+    DURF_REQUIREF(P > 0, "P > 0 pairs, P = %d", P);
     int rc = check_flow_scalars(__func__, K, znear, inside_tol);
     if (rc != 0) return rc;
-    FLOW_REQUIRE(chunk > 0, "chunk > 0, chunk = %d", chunk);
-    FLOW_REQUIRE(flow || scene_flow || xyz || target || zcam || moving || valid, "at least one output");
-    FLOW_REQUIRE(cams_host && pairs_host, "the camera rows and the pairs");
+    DURF_REQUIREF(chunk > 0, "chunk > 0, chunk = %d", chunk);
+    DURF_REQUIREF(flow || scene_flow || xyz || target || zcam || moving || valid, "at least one output");
+    DURF_REQUIREF(cams_host && pairs_host, "the camera rows and the pairs");
     for (int p = 0; p < P; p++)
         for (int s = 0; s < 2; s++) {
             const int f = pairs_host[p * 2 + s];
-            FLOW_REQUIRE(f >= 0 && f < F, "pair %d names frame %d outside [0, %d)", p, f, F);
+            DURF_REQUIREF(f >= 0 && f < F, "pair %d names frame %d outside [0, %d)", p, f, F);
         }
     const float hf = cams_host[15], wf = cams_host[16];
-    FLOW_REQUIRE(hf >= 2.0f && wf >= 1.0f && (double)hf * wf < 134217728.0, "frames of h >= 2, w >= 1, h w < 2^27, h = %g, w = %g",
+    DURF_REQUIREF(hf >= 2.0f && wf >= 1.0f && (double)hf * wf < 134217728.0, "frames of h >= 2, w >= 1, h w < 2^27, h = %g, w = %g",
                  (double)hf, (double)wf);
     for (int f = 1; f < F; f++)
-        FLOW_REQUIRE(cams_host[(size_t)f * 17 + 15] == hf && cams_host[(size_t)f * 17 + 16] == wf,
+        DURF_REQUIREF(cams_host[(size_t)f * 17 + 15] == hf && cams_host[(size_t)f * 17 + 16] == wf,
                      "frames of different sizes: frame %d is %g x %g, frame 0 is %g x %g", f, (double)cams_host[(size_t)f * 17 + 15],
                      (double)cams_host[(size_t)f * 17 + 16], (double)hf, (double)wf);
-    FLOW_REQUIRE(distance && acc && (K == 0 || (poses && ext)), "distance, acc, and the box poses and extents for K = %d", K);
-    FLOW_REQUIRE(((size_t)flow & 7) == 0, "flow is 8-byte aligned");
-    FLOW_REQUIRE(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    DURF_REQUIREF(distance && acc && (K == 0 || (poses && ext)), "distance, acc, and the box poses and extents for K = %d", K);
+    DURF_REQUIREF(((size_t)flow & 7) == 0, "flow is 8-byte aligned");
+    DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
     const FlowWs w = carve_flow(workspace, chunk, K);
     rc = durf::check_workspace("durf_render_flow", workspace_bytes, w.total, "durf_render_flow_workspace_bytes(%d, %d)", chunk, K);
     if (rc != 0) return rc;

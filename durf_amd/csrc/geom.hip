@@ -1,25 +1,15 @@
 // Distances between unordered point sets (include/durf_geom.h; libdurf_geom.so): cell keys (k_geom_keys), the nearest point
 // within a radius over a cell-sorted reference set (k_geom_nearest: nine binary-searched key ranges per query, no cell table),
 // the two-level float64 statistics of the distances (k_geom_stats_partial, k_geom_stats_final) and area-uniform mesh samples
-// (k_geom_areas, k_geom_scan, k_geom_offsets -- the three plain passes of mesh.hip's scan, in float64 -- and k_geom_sample).
+// (k_geom_areas, k_scan_block_sums, k_geom_offsets -- the three plain passes of scan.h, in float64 -- and k_geom_sample).
 // One thread per point, plain fp32 in the order the header states; no atomics, nothing synchronises or copies to the host.
 #include <cmath>
 #include "workspace.h"
+#include "scan.h"
 #include "../../include/durf_geom.h"
-
-// a refusal that names the offending value
-#define GEOM_REQUIRE(cond, fmt, ...)                                                          \
-    do {                                                                                      \
-        if (!(cond)) {                                                                        \
-            durf_set_error("%s: requirement failed: " fmt, __func__, ##__VA_ARGS__);          \
-            return -1;                                                                        \
-        }                                                                                     \
-    } while (0)
 
 #define GEOM_B DURF_GEOM_BLOCK
 #define GEOM_WAVES (GEOM_B / DURF_WAVE)
-#define GEOM_SCAN_THREADS 1024
-#define GEOM_SCAN_WAVES (GEOM_SCAN_THREADS / DURF_WAVE)
 #define GEOM_NS DURF_GEOM_STAT_DOUBLES
 
 struct GeomGrid {
@@ -164,21 +154,12 @@ k_geom_stats_final(int nb, const double* __restrict__ partials, double* __restri
 }
 
 // ---- points on a mesh -------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_incl_scan_d(double v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
 // pass 1: the area of every triangle (into cum) and the sum of every workgroup's 256
 __global__ void __launch_bounds__(GEOM_B)
 k_geom_areas(int V, const float* __restrict__ vert, int T, const int32_t* __restrict__ tri, double* __restrict__ cum,
              double* __restrict__ sums) {
     __shared__ double s_a[GEOM_WAVES];
-    const int t = threadIdx.x, lane = t & (DURF_WAVE - 1), g = blockIdx.x * GEOM_B + t;
+    const int t = threadIdx.x, g = blockIdx.x * GEOM_B + t;
     double area = 0.0;
     if (g < T) {
         const int ia = tri[(size_t)g * 3], ib = tri[(size_t)g * 3 + 1], ic = tri[(size_t)g * 3 + 2];
@@ -194,61 +175,23 @@ k_geom_areas(int V, const float* __restrict__ vert, int T, const int32_t* __rest
         }
         cum[g] = area;
     }
-    const double ia2 = wave_incl_scan_d(area, lane);
-    if (lane == DURF_WAVE - 1) s_a[t / DURF_WAVE] = ia2;
+    scan_wave_to_lds(area, s_a);
     __syncthreads();
-    if (t == 0) {
-        double a = 0.0;
-#pragma unroll
-        for (int v = 0; v < GEOM_WAVES; v++) a += s_a[v];
-        sums[blockIdx.x] = a;
-    }
+    if (t == 0) sums[blockIdx.x] = scan_block_sum<GEOM_WAVES>(s_a);
 }
 
-// pass 2: ONE workgroup turns the block sums into their exclusive scan in place; the total goes to sums[nb] and *total
-__global__ void __launch_bounds__(GEOM_SCAN_THREADS)
-k_geom_scan(int nb, double* __restrict__ sums, double* __restrict__ total) {
-    __shared__ double s_a[GEOM_SCAN_WAVES];
-    const int t = threadIdx.x, lane = t & (DURF_WAVE - 1), wave = t / DURF_WAVE;
-    double carry = 0.0;
-    for (int base = 0; base < nb; base += GEOM_SCAN_THREADS) {              // (uniform over the workgroup)
-        const int i = base + t;
-        const double x = i < nb ? sums[i] : 0.0;
-        const double ix = wave_incl_scan_d(x, lane);
-        if (lane == DURF_WAVE - 1) s_a[wave] = ix;
-        __syncthreads();
-        double before = 0.0, all = 0.0;
-#pragma unroll
-        for (int v = 0; v < GEOM_SCAN_WAVES; v++) {
-            const double a = s_a[v];
-            if (v < wave) before += a;
-            all += a;
-        }
-        if (i < nb) sums[i] = (carry + before) + (ix - x);
-        carry += all;
-        __syncthreads();                                                    // s_a is rewritten by the next round
-    }
-    if (t == 0) {
-        sums[nb] = carry;
-        *total = carry;
-    }
-}
+// pass 2: k_scan_block_sums<double, 1> (scan.h); the total goes to sums[nb] and *total
 
 // pass 3: the areas in cum become their inclusive prefix sums
 __global__ void __launch_bounds__(GEOM_B)
 k_geom_offsets(int T, double* __restrict__ cum, const double* __restrict__ sums) {
     __shared__ double s_a[GEOM_WAVES];
-    const int t = threadIdx.x, lane = t & (DURF_WAVE - 1), wave = t / DURF_WAVE, g = blockIdx.x * GEOM_B + t;
+    const int g = blockIdx.x * GEOM_B + threadIdx.x;
     const double a = g < T ? cum[g] : 0.0;
-    const double ia = wave_incl_scan_d(a, lane);
-    if (lane == DURF_WAVE - 1) s_a[wave] = ia;
+    const double ia = scan_wave_to_lds(a, s_a);
     __syncthreads();
     if (g >= T) return;
-    double before = sums[blockIdx.x];
-#pragma unroll
-    for (int u = 0; u < GEOM_WAVES; u++)
-        if (u < wave) before += s_a[u];
-    cum[g] = before + ia;
+    cum[g] = scan_before_wave<GEOM_WAVES>(sums[blockIdx.x], s_a) + ia;
 }
 
 __global__ void __launch_bounds__(GEOM_B)
@@ -341,8 +284,8 @@ size_t durf_geom_workspace_bytes(int n_queries, int n_triangles) {
 
 int durf_geom_keys(void* stream, int n, const float* points, const float* origin_host, float inv_cell, int nx, int ny, int nz,
                    int64_t* keys) {
-    GEOM_REQUIRE(n >= 0, "n >= 0, n = %d", n);
-    GEOM_REQUIRE(n == 0 || (points && keys), "points and keys for n = %d", n);
+    DURF_REQUIREF(n >= 0, "n >= 0, n = %d", n);
+    DURF_REQUIREF(n == 0 || (points && keys), "points and keys for n = %d", n);
     GeomGrid G{};
     if (check_geom_grid(__func__, origin_host, inv_cell, nx, ny, nz, &G) != 0) return -1;
     if (n == 0) return 0;
@@ -354,14 +297,14 @@ int durf_geom_keys(void* stream, int n, const float* points, const float* origin
 int durf_geom_nearest(void* stream, int q, const float* query, int m, const float* ref_sorted, const int64_t* ref_keys,
                       const int32_t* ref_index, const float* origin_host, float inv_cell, int nx, int ny, int nz, float max_dist,
                       float* dist, int32_t* index) {
-    GEOM_REQUIRE(q >= 0 && m >= 0, "q >= 0 and m >= 0, q = %d, m = %d", q, m);
-    GEOM_REQUIRE(q == 0 || (query && dist && index), "query, dist and index for q = %d", q);
-    GEOM_REQUIRE(m == 0 || (ref_sorted && ref_keys && ref_index), "ref_sorted, ref_keys and ref_index for m = %d", m);
-    GEOM_REQUIRE(max_dist >= 1e-18f && max_dist <= 1e18f, "1e-18 <= max_dist <= 1e18, max_dist = %g", (double)max_dist);
+    DURF_REQUIREF(q >= 0 && m >= 0, "q >= 0 and m >= 0, q = %d, m = %d", q, m);
+    DURF_REQUIREF(q == 0 || (query && dist && index), "query, dist and index for q = %d", q);
+    DURF_REQUIREF(m == 0 || (ref_sorted && ref_keys && ref_index), "ref_sorted, ref_keys and ref_index for m = %d", m);
+    DURF_REQUIREF(max_dist >= 1e-18f && max_dist <= 1e18f, "1e-18 <= max_dist <= 1e18, max_dist = %g", (double)max_dist);
     GeomGrid G{};
     if (check_geom_grid(__func__, origin_host, inv_cell, nx, ny, nz, &G) != 0) return -1;
     const double rule = (double)inv_cell * (double)max_dist * (1.0 + 1.0 / 1024.0);
-    GEOM_REQUIRE(rule <= 1.0 + 1.0 / 4194304.0,
+    DURF_REQUIREF(rule <= 1.0 + 1.0 / 4194304.0,
                  "the grid rule inv_cell * max_dist * (1 + 2^-10) <= 1 + 2^-22 (a cell is max_dist (1 + 2^-10) or more), inv_cell = %.9g, "
                  "max_dist = %.9g", (double)inv_cell, (double)max_dist);
     if (q == 0) return 0;
@@ -374,19 +317,19 @@ int durf_geom_nearest(void* stream, int q, const float* query, int m, const floa
 
 int durf_geom_stats(void* stream, int q, const float* dist, const int32_t* index, int n_thresholds, const float* thresholds_host,
                     void* workspace, size_t workspace_bytes, double* stats) {
-    GEOM_REQUIRE(q >= 0, "q >= 0, q = %d", q);
-    GEOM_REQUIRE(q == 0 || (dist && index), "dist and index for q = %d", q);
-    GEOM_REQUIRE(n_thresholds >= 0 && n_thresholds <= DURF_GEOM_MAX_THRESHOLDS, "0 .. %d thresholds, n_thresholds = %d",
+    DURF_REQUIREF(q >= 0, "q >= 0, q = %d", q);
+    DURF_REQUIREF(q == 0 || (dist && index), "dist and index for q = %d", q);
+    DURF_REQUIREF(n_thresholds >= 0 && n_thresholds <= DURF_GEOM_MAX_THRESHOLDS, "0 .. %d thresholds, n_thresholds = %d",
                  DURF_GEOM_MAX_THRESHOLDS, n_thresholds);
-    GEOM_REQUIRE(n_thresholds == 0 || thresholds_host, "thresholds for n_thresholds = %d", n_thresholds);
+    DURF_REQUIREF(n_thresholds == 0 || thresholds_host, "thresholds for n_thresholds = %d", n_thresholds);
     GeomThresholds T{};
     T.n = n_thresholds;
     for (int k = 0; k < n_thresholds; k++) {
-        GEOM_REQUIRE(thresholds_host[k] == thresholds_host[k], "thresholds are numbers, thresholds[%d] = %g", k, (double)thresholds_host[k]);
+        DURF_REQUIREF(thresholds_host[k] == thresholds_host[k], "thresholds are numbers, thresholds[%d] = %g", k, (double)thresholds_host[k]);
         T.t[k] = thresholds_host[k];
     }
-    GEOM_REQUIRE(stats != nullptr, "stats");
-    GEOM_REQUIRE(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    DURF_REQUIREF(stats != nullptr, "stats");
+    DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
     const GeomWs w = carve_geom(workspace, q, 0);
     int rc = durf::check_workspace(__func__, workspace_bytes, w.total, "durf_geom_workspace_bytes(%d, 0)", q);
     if (rc != 0) return rc;
@@ -401,13 +344,13 @@ int durf_geom_stats(void* stream, int q, const float* dist, const int32_t* index
 
 int durf_geom_sample_mesh(void* stream, int n_vertices, const float* vertices, int n_triangles, const int32_t* triangles, int n,
                           void* workspace, size_t workspace_bytes, float* points, int32_t* tri, double* total_area) {
-    GEOM_REQUIRE(n >= 0 && n_vertices >= 0 && n_triangles >= 0, "n, n_vertices and n_triangles >= 0, n = %d, n_vertices = %d, n_triangles = %d",
+    DURF_REQUIREF(n >= 0 && n_vertices >= 0 && n_triangles >= 0, "n, n_vertices and n_triangles >= 0, n = %d, n_vertices = %d, n_triangles = %d",
                  n, n_vertices, n_triangles);
-    GEOM_REQUIRE(n_vertices == 0 || vertices, "vertices for n_vertices = %d", n_vertices);
-    GEOM_REQUIRE(n_triangles == 0 || triangles, "triangles for n_triangles = %d", n_triangles);
-    GEOM_REQUIRE(n == 0 || (points && tri), "points and tri for n = %d", n);
-    GEOM_REQUIRE(total_area != nullptr, "total_area");
-    GEOM_REQUIRE(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    DURF_REQUIREF(n_vertices == 0 || vertices, "vertices for n_vertices = %d", n_vertices);
+    DURF_REQUIREF(n_triangles == 0 || triangles, "triangles for n_triangles = %d", n_triangles);
+    DURF_REQUIREF(n == 0 || (points && tri), "points and tri for n = %d", n);
+    DURF_REQUIREF(total_area != nullptr, "total_area");
+    DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
     const GeomWs w = carve_geom(workspace, 0, n_triangles);
     int rc = durf::check_workspace(__func__, workspace_bytes, w.total, "durf_geom_workspace_bytes(0, %d)", n_triangles);
     if (rc != 0) return rc;
@@ -416,8 +359,8 @@ int durf_geom_sample_mesh(void* stream, int n_vertices, const float* vertices, i
                            w.cum, w.sums);
         DURF_CHECK_LAUNCH("k_geom_areas");
     }
-    hipLaunchKernelGGL(k_geom_scan, dim3(1), dim3(GEOM_SCAN_THREADS), 0, (hipStream_t)stream, w.nbt, w.sums, total_area);
-    DURF_CHECK_LAUNCH("k_geom_scan");
+    hipLaunchKernelGGL((k_scan_block_sums<double, 1>), dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, w.nbt, w.sums, total_area);
+    DURF_CHECK_LAUNCH("k_scan_block_sums<double, 1>");
     if (w.nbt > 0) {
         hipLaunchKernelGGL(k_geom_offsets, dim3(w.nbt), dim3(GEOM_B), 0, (hipStream_t)stream, n_triangles, w.cum, w.sums);
         DURF_CHECK_LAUNCH("k_geom_offsets");

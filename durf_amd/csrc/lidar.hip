@@ -1,9 +1,10 @@
 // LIDAR sweeps (include/durf_lidar.h; libdurf_lidar.so): the rays of a spinning multi-beam sensor in front of the renderer
 // (k_lidar_rays), the return model behind it -- quantiles of every ray's weight distribution out of one wave scan
-// (k_lidar_returns) --, the valid returns compacted into a point cloud in three plain passes (k_lidar_count, k_lidar_scan,
-// k_lidar_scatter), and durf_render_lidar, which walks F sweeps in chunks through durf_forward_masked of libdurf_hip.so.  Plain
-// fp32 in the order the header states; nothing here synchronises or copies to the host.
+// (k_lidar_returns) --, the valid returns compacted into a point cloud in three plain passes (k_lidar_count, k_scan_block_sums
+// of scan.h, k_lidar_scatter), and durf_render_lidar, which walks F sweeps in chunks through durf_forward_masked of
+// libdurf_hip.so.  Plain fp32 in the order the header states; nothing here synchronises or copies to the host.
 #include "workspace.h"
+#include "scan.h"
 #include "../../include/durf_lidar.h"
 
 // ---- the sensor ----------------------------------------------------------------------------------------------------------
@@ -187,17 +188,6 @@ static int launch_lidar_returns(void* stream, int n, int N, const float* weights
 // ---- the point cloud --------------------------------------------------------------------------------------------------------
 #define LIDAR_CB DURF_LIDAR_COMPACT_BLOCK
 #define LIDAR_CB_WAVES (LIDAR_CB / DURF_WAVE)
-#define LIDAR_SCAN_THREADS 1024
-#define LIDAR_SCAN_WAVES (LIDAR_SCAN_THREADS / DURF_WAVE)
-
-__device__ __forceinline__ int wave_incl_scan_i(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
 
 // pass 1: the valid rays of block b of LIDAR_CB rays -> sums[b]
 __global__ void __launch_bounds__(LIDAR_CB)
@@ -215,34 +205,7 @@ k_lidar_count(int n, const int32_t* __restrict__ valid, int32_t* __restrict__ su
     }
 }
 
-// pass 2: ONE workgroup turns sums[0, nb) into its exclusive scan in place; the total goes to sums[nb] and count[0]
-__global__ void __launch_bounds__(LIDAR_SCAN_THREADS)
-k_lidar_scan(int nb, int32_t* __restrict__ sums, int32_t* __restrict__ count) {
-    __shared__ int s_wave[LIDAR_SCAN_WAVES];
-    const int t = threadIdx.x, lane = t & (DURF_WAVE - 1), wave = t / DURF_WAVE;
-    int carry = 0;
-    for (int base = 0; base < nb; base += LIDAR_SCAN_THREADS) {          // (uniform over the workgroup)
-        const int i = base + t;
-        const int x = i < nb ? sums[i] : 0;
-        const int inc = wave_incl_scan_i(x, lane);
-        if (lane == DURF_WAVE - 1) s_wave[wave] = inc;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int v = 0; v < LIDAR_SCAN_WAVES; v++) {
-            const int c = s_wave[v];
-            if (v < wave) before += c;
-            total += c;
-        }
-        if (i < nb) sums[i] = carry + before + inc - x;
-        carry += total;
-        __syncthreads();                                                  // s_wave is rewritten by the next round
-    }
-    if (t == 0) {
-        sums[nb] = carry;
-        count[0] = carry;
-    }
-}
+// pass 2: k_scan_block_sums<int32_t, 1> (scan.h); the total goes to sums[nb] and count[0]
 
 // pass 3: ray i, the m-th valid one, writes row m
 __global__ void __launch_bounds__(LIDAR_CB)
@@ -350,8 +313,8 @@ int durf_lidar_compact(void* stream, int n, const int32_t* valid, const float* x
         hipLaunchKernelGGL(k_lidar_count, dim3(nb), dim3(LIDAR_CB), 0, (hipStream_t)stream, n, valid, scratch);
         DURF_CHECK_LAUNCH("k_lidar_count");
     }
-    hipLaunchKernelGGL(k_lidar_scan, dim3(1), dim3(LIDAR_SCAN_THREADS), 0, (hipStream_t)stream, nb, scratch, count);
-    DURF_CHECK_LAUNCH("k_lidar_scan");
+    hipLaunchKernelGGL((k_scan_block_sums<int32_t, 1>), dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, nb, scratch, count);
+    DURF_CHECK_LAUNCH("k_scan_block_sums<int32_t, 1>");
     if (nb > 0) {
         hipLaunchKernelGGL(k_lidar_scatter, dim3(nb), dim3(LIDAR_CB), 0, (hipStream_t)stream, n, valid, xyz, range, rgb, dyn_mask,
                            scratch, points, source);

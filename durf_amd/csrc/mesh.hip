@@ -1,24 +1,14 @@
 // The iso-surface of a density lattice as an indexed triangle mesh (include/durf_mesh.h; libdurf_mesh.so): marching tetrahedra
 // on the Kuhn subdivision with welded vertices.  Classify and count per lattice point (k_mesh_classify), one workgroup's
-// exclusive scan of the block sums (k_mesh_scan), offsets (k_mesh_offsets) -- the three plain passes of durf_lidar_compact --,
+// exclusive scan of the block sums (k_scan_block_sums), offsets (k_mesh_offsets) -- the three plain passes of scan.h --,
 // then emit (k_mesh_emit) and the attribute gather (k_mesh_gather).  Streaming kernels, one thread per lattice point with
 // adjacent lanes along k, plain fp32 in the order the header states; no atomics, nothing synchronises or copies to the host.
 #include "workspace.h"
+#include "scan.h"
 #include "../../include/durf_mesh.h"
-
-// a refusal that names the offending value
-#define MESH_REQUIRE(cond, fmt, ...)                                                          \
-    do {                                                                                      \
-        if (!(cond)) {                                                                        \
-            durf_set_error("%s: requirement failed: " fmt, __func__, ##__VA_ARGS__);          \
-            return -1;                                                                        \
-        }                                                                                     \
-    } while (0)
 
 #define MESH_B DURF_MESH_BLOCK
 #define MESH_WAVES (MESH_B / DURF_WAVE)
-#define MESH_SCAN_THREADS 1024
-#define MESH_SCAN_WAVES (MESH_SCAN_THREADS / DURF_WAVE)
 
 // ---- the sixteen cases, built from the header's rule ------------------------------------------------------------------------
 // A cell corner is the code c = 4 di + 2 dj + dk; the edge from corner a to corner b (a's bits a subset of b's) is edge
@@ -147,15 +137,6 @@ __device__ __forceinline__ void mesh_corners(const MeshDims D, const float* __re
     *exist = X; *usable = U; *in = N;
 }
 
-__device__ __forceinline__ int wave_incl_scan_i(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
 // pass 1: per lattice point the seven activity bits and the counts of its vertices (into voff) and of its cell's triangles
 // (into toff); per workgroup the two sums
 __global__ void __launch_bounds__(MESH_B)
@@ -163,7 +144,7 @@ k_mesh_classify(const MeshDims D, const float* __restrict__ density, const uint8
                 int32_t* __restrict__ voff, int32_t* __restrict__ toff, uint8_t* __restrict__ mask, int32_t* __restrict__ sums_v,
                 int32_t* __restrict__ sums_t) {
     __shared__ int s_v[MESH_WAVES], s_t[MESH_WAVES];
-    const int t = threadIdx.x, lane = t & (DURF_WAVE - 1), g = blockIdx.x * MESH_B + t;
+    const int t = threadIdx.x, g = blockIdx.x * MESH_B + t;
     int cv = 0, ct = 0;
     if (g < D.n) {
         const int k = g % D.nw, r = g / D.nw, j = r % D.nv, i = r / D.nv;
@@ -188,70 +169,29 @@ k_mesh_classify(const MeshDims D, const float* __restrict__ density, const uint8
         voff[g] = cv;
         toff[g] = ct;
     }
-    const int iv = wave_incl_scan_i(cv, lane), it = wave_incl_scan_i(ct, lane);
-    if (lane == DURF_WAVE - 1) { s_v[t / DURF_WAVE] = iv; s_t[t / DURF_WAVE] = it; }
+    scan_wave_to_lds(cv, s_v);
+    scan_wave_to_lds(ct, s_t);
     __syncthreads();
     if (t == 0) {
-        int a = 0, b = 0;
-#pragma unroll
-        for (int v = 0; v < MESH_WAVES; v++) { a += s_v[v]; b += s_t[v]; }
-        sums_v[blockIdx.x] = a;
-        sums_t[blockIdx.x] = b;
+        sums_v[blockIdx.x] = scan_block_sum<MESH_WAVES>(s_v);
+        sums_t[blockIdx.x] = scan_block_sum<MESH_WAVES>(s_t);
     }
 }
 
-// pass 2: ONE workgroup turns both rows of block sums into their exclusive scans in place; the totals go to counts
-__global__ void __launch_bounds__(MESH_SCAN_THREADS)
-k_mesh_scan(int nb, int32_t* __restrict__ sums_v, int32_t* __restrict__ sums_t, int32_t* __restrict__ counts) {
-    __shared__ int s_v[MESH_SCAN_WAVES], s_t[MESH_SCAN_WAVES];
-    const int t = threadIdx.x, lane = t & (DURF_WAVE - 1), wave = t / DURF_WAVE;
-    int carry_v = 0, carry_t = 0;
-    for (int base = 0; base < nb; base += MESH_SCAN_THREADS) {            // (uniform over the workgroup)
-        const int i = base + t;
-        const int xv = i < nb ? sums_v[i] : 0, xt = i < nb ? sums_t[i] : 0;
-        const int iv = wave_incl_scan_i(xv, lane), it = wave_incl_scan_i(xt, lane);
-        if (lane == DURF_WAVE - 1) { s_v[wave] = iv; s_t[wave] = it; }
-        __syncthreads();
-        int bv = 0, tv = 0, bt = 0, tt = 0;
-#pragma unroll
-        for (int v = 0; v < MESH_SCAN_WAVES; v++) {
-            const int a = s_v[v], b = s_t[v];
-            if (v < wave) { bv += a; bt += b; }
-            tv += a; tt += b;
-        }
-        if (i < nb) {
-            sums_v[i] = carry_v + bv + iv - xv;
-            sums_t[i] = carry_t + bt + it - xt;
-        }
-        carry_v += tv;
-        carry_t += tt;
-        __syncthreads();                                                  // s_v, s_t are rewritten by the next round
-    }
-    if (t == 0) {
-        sums_v[nb] = carry_v;
-        sums_t[nb] = carry_t;
-        counts[0] = carry_v;
-        counts[1] = carry_t;
-    }
-}
+// pass 2: k_scan_block_sums<int32_t, 2> (scan.h) on the two rows sums_v, sums_t = sums_v + nb + 1; the totals go to counts
 
 // pass 3: the per-point counts in voff and toff become the exclusive prefix sums in g order
 __global__ void __launch_bounds__(MESH_B)
 k_mesh_offsets(int n, int32_t* __restrict__ voff, int32_t* __restrict__ toff, const int32_t* __restrict__ sums_v,
                const int32_t* __restrict__ sums_t) {
     __shared__ int s_v[MESH_WAVES], s_t[MESH_WAVES];
-    const int t = threadIdx.x, lane = t & (DURF_WAVE - 1), wave = t / DURF_WAVE, g = blockIdx.x * MESH_B + t;
+    const int g = blockIdx.x * MESH_B + threadIdx.x;
     const int cv = g < n ? voff[g] : 0, ct = g < n ? toff[g] : 0;
-    const int iv = wave_incl_scan_i(cv, lane), it = wave_incl_scan_i(ct, lane);
-    if (lane == DURF_WAVE - 1) { s_v[wave] = iv; s_t[wave] = it; }
+    const int iv = scan_wave_to_lds(cv, s_v), it = scan_wave_to_lds(ct, s_t);
     __syncthreads();
     if (g >= n) return;
-    int av = sums_v[blockIdx.x] + iv - cv, at = sums_t[blockIdx.x] + it - ct;
-#pragma unroll
-    for (int u = 0; u < MESH_WAVES; u++)
-        if (u < wave) { av += s_v[u]; at += s_t[u]; }
-    voff[g] = av;
-    toff[g] = at;
+    voff[g] = scan_before_wave<MESH_WAVES>(sums_v[blockIdx.x], s_v) + (iv - cv);
+    toff[g] = scan_before_wave<MESH_WAVES>(sums_t[blockIdx.x], s_t) + (it - ct);
 }
 
 // ---- emit -------------------------------------------------------------------------------------------------------------------
@@ -432,9 +372,9 @@ int durf_mesh_count(void* stream, int nu, int nv, int nw, const float* density, 
                     size_t workspace_bytes, int32_t* counts) {
     const int n = check_mesh_shape(__func__, nu, nv, nw);
     if (n < 0) return -1;
-    MESH_REQUIRE(iso == iso, "iso is a number, iso = %g", (double)iso);
-    MESH_REQUIRE(density && counts, "density and counts");
-    MESH_REQUIRE(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    DURF_REQUIREF(iso == iso, "iso is a number, iso = %g", (double)iso);
+    DURF_REQUIREF(density && counts, "density and counts");
+    DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
     const MeshWs w = carve_mesh(workspace, n);
     int rc = durf::check_workspace(__func__, workspace_bytes, w.total, "durf_mesh_workspace_bytes(%d, %d, %d)", nu, nv, nw);
     if (rc != 0) return rc;
@@ -442,8 +382,8 @@ int durf_mesh_count(void* stream, int nu, int nv, int nw, const float* density, 
     hipLaunchKernelGGL(k_mesh_classify, dim3(w.nb), dim3(MESH_B), 0, (hipStream_t)stream, D, density, valid, iso, w.voff, w.toff, w.mask,
                        w.sums_v, w.sums_t);
     DURF_CHECK_LAUNCH("k_mesh_classify");
-    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(MESH_SCAN_THREADS), 0, (hipStream_t)stream, w.nb, w.sums_v, w.sums_t, counts);
-    DURF_CHECK_LAUNCH("k_mesh_scan");
+    hipLaunchKernelGGL((k_scan_block_sums<int32_t, 2>), dim3(1), dim3(SCAN_THREADS), 0, (hipStream_t)stream, w.nb, w.sums_v, counts);
+    DURF_CHECK_LAUNCH("k_scan_block_sums<int32_t, 2>");
     hipLaunchKernelGGL(k_mesh_offsets, dim3(w.nb), dim3(MESH_B), 0, (hipStream_t)stream, n, w.voff, w.toff, w.sums_v, w.sums_t);
     DURF_CHECK_LAUNCH("k_mesh_offsets");
     return 0;
@@ -455,15 +395,15 @@ int durf_mesh_emit(void* stream, int nu, int nv, int nw, const float* density, c
                    int32_t* vertex_edge, float* vertex_t, int32_t* triangles) {
     const int n = check_mesh_shape(__func__, nu, nv, nw);
     if (n < 0) return -1;
-    MESH_REQUIRE(iso == iso, "iso is a number, iso = %g", (double)iso);
-    MESH_REQUIRE(density != nullptr, "density");
-    MESH_REQUIRE(origin_host && du_host && dv_host && dw_host, "origin, du, dv and dw");
-    MESH_REQUIRE(!normals || normal_xform_host, "normals need normal_xform");
-    MESH_REQUIRE(max_vertices >= 0 && max_triangles >= 0, "capacities >= 0, max_vertices = %d, max_triangles = %d", max_vertices,
+    DURF_REQUIREF(iso == iso, "iso is a number, iso = %g", (double)iso);
+    DURF_REQUIREF(density != nullptr, "density");
+    DURF_REQUIREF(origin_host && du_host && dv_host && dw_host, "origin, du, dv and dw");
+    DURF_REQUIREF(!normals || normal_xform_host, "normals need normal_xform");
+    DURF_REQUIREF(max_vertices >= 0 && max_triangles >= 0, "capacities >= 0, max_vertices = %d, max_triangles = %d", max_vertices,
                  max_triangles);
-    MESH_REQUIRE(vertices || max_vertices == 0, "vertices for max_vertices = %d", max_vertices);
-    MESH_REQUIRE(triangles || max_triangles == 0, "triangles for max_triangles = %d", max_triangles);
-    MESH_REQUIRE(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    DURF_REQUIREF(vertices || max_vertices == 0, "vertices for max_vertices = %d", max_vertices);
+    DURF_REQUIREF(triangles || max_triangles == 0, "triangles for max_triangles = %d", max_triangles);
+    DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
     const MeshWs w = carve_mesh(const_cast<void*>(workspace), n);
     int rc = durf::check_workspace(__func__, workspace_bytes, w.total, "durf_mesh_workspace_bytes(%d, %d, %d)", nu, nv, nw);
     if (rc != 0) return rc;
@@ -485,12 +425,12 @@ int durf_mesh_gather(void* stream, int nu, int nv, int nw, const int32_t* counts
                      const uint8_t* valid, float iso, int32_t* out_i) {
     const int n = check_mesh_shape(__func__, nu, nv, nw);
     if (n < 0) return -1;
-    MESH_REQUIRE(max_vertices >= 0, "max_vertices >= 0, max_vertices = %d", max_vertices);
-    MESH_REQUIRE(counts && vertex_edge && vertex_t, "counts, vertex_edge and vertex_t");
-    MESH_REQUIRE(attr_f || attr_i, "at least one attribute");
-    MESH_REQUIRE(!attr_f || (out_f && C >= 1), "attr_f needs out_f and C >= 1, C = %d", C);
-    MESH_REQUIRE(!attr_i || (out_i && density), "attr_i needs out_i and density");
-    MESH_REQUIRE(!attr_i || iso == iso, "iso is a number, iso = %g", (double)iso);
+    DURF_REQUIREF(max_vertices >= 0, "max_vertices >= 0, max_vertices = %d", max_vertices);
+    DURF_REQUIREF(counts && vertex_edge && vertex_t, "counts, vertex_edge and vertex_t");
+    DURF_REQUIREF(attr_f || attr_i, "at least one attribute");
+    DURF_REQUIREF(!attr_f || (out_f && C >= 1), "attr_f needs out_f and C >= 1, C = %d", C);
+    DURF_REQUIREF(!attr_i || (out_i && density), "attr_i needs out_i and density");
+    DURF_REQUIREF(!attr_i || iso == iso, "iso is a number, iso = %g", (double)iso);
     if (max_vertices == 0) return 0;
     const MeshDims D{nu, nv, nw, n};
     hipLaunchKernelGGL(k_mesh_gather, dim3(durf_cdiv((size_t)max_vertices, MESH_B)), dim3(MESH_B), 0, (hipStream_t)stream, D, counts,

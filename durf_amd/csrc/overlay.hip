@@ -8,14 +8,8 @@
 #include "../../include/durf_overlay.h"
 
 // ---- projection ----------------------------------------------------------------------------------------------------------
-// overlay_aa2matrix, the world->object matrix of a box pose: aa2matrix.h (shared with flow.hip)
-
-// camera space of a world point: pc = R_c^T (P - o), R_c[a][j] = cam[4 a + j], o[a] = cam[4 a + 3]
-__device__ __forceinline__ void overlay_to_camera(const float* cam, const float* P, float* pc) {
-    const float d0 = P[0] - cam[3], d1 = P[1] - cam[7], d2 = P[2] - cam[11];
-#pragma unroll
-    for (int j = 0; j < 3; j++) pc[j] = (cam[j] * d0 + cam[4 + j] * d1) + cam[8 + j] * d2;
-}
+// overlay_aa2matrix, the world->object matrix of a box pose, and overlay_to_camera, camera space of a world point: aa2matrix.h
+// (shared with flow.hip and field.hip)
 
 // one thread per (frame, box)
 __global__ void __launch_bounds__(64)

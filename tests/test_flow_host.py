@@ -5,8 +5,6 @@ of durf_amd/flow.py (.flo files, the pairs)."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -36,15 +34,7 @@ def _row(cam):
 # ---- the library ----------------------------------------------------------------------------------------------------------
 def test_symbols_are_declared_bound_and_exported_by_a_library_of_their_own():
     hdr = open(os.path.join(ROOT, 'include', 'durf_flow.h')).read()
-    declared = set(re.findall(r'\b(durf_[a-z0-9_]+)\s*\(', re.sub(r'/\*.*?\*/', ' ', hdr, flags=re.S)))
-    assert declared == ENTRY == set(_lib.flow_symbols())
-    _lib.flow_lib()
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.FLOW_LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert {ln.split()[-1] for ln in out.splitlines() if ' T ' in ln and ln.split()[-1].startswith('durf_')} == declared
-    assert not declared & set(_lib.symbols()) and not declared & set(_lib.overlay_symbols()) and not declared & set(_lib.lidar_symbols())
-    base = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert not declared & {ln.split()[-1] for ln in base.splitlines()}, 'libdurf_hip.so keeps its own set of entry points'
-    assert subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'gen_integration_stub.py'), '--check'], cwd=ROOT).returncode == 0
+    assert ENTRY == set(_lib.flow_symbols())           # (header == table == symbol table: tests/test_satellites_host.py)
     for name, value in (('CONS_FLOATS', ops.FLOW_CONS_FLOATS), ('CONS_SPAN', ops.FLOW_CONS_SPAN), ('WHEEL', ops.FLOW_WHEEL)):
         assert int(re.search(r'#define DURF_FLOW_%s (\d+)' % name, hdr).group(1)) == value, name
     assert len(ops.FLOW_CONS_FIELDS) == ops.FLOW_CONS_FLOATS and FR.CONS_SPAN == ops.FLOW_CONS_SPAN and FR.WHEEL == ops.FLOW_WHEEL

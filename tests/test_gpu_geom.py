@@ -9,6 +9,7 @@ says what that fp32 answer is worth: dist within 4 * 2^-24 relative (each differ
 of that plus the root's own rounding: 3.5 * 2^-24), and the same index wherever float64 itself separates the best from the
 runner-up and from max_dist by more than 16 * 2^-24 relative.  Sizes are a few thousand points: more than one workgroup, odd
 counts, and the grid's limit of 2048 cells on an axis, where the rule is tightest."""
+import functools
 import json
 import os
 import subprocess
@@ -235,20 +236,30 @@ def test_cloud_distance_is_the_two_directions(cuda):
 
 
 # ---- 6. the mesh sampler ------------------------------------------------------------------------------------------------------------
+def _strip(m):
+    """2 m right triangles with legs 1/128 and 1/2 in a row: area 2^-9 each, so every partial sum of the areas is exact in
+    float64 in any association (x = k / 128 is exact in fp32 far beyond m = 2^17)"""
+    x = np.arange(m + 1, dtype=np.float32) / 128
+    sv = np.concatenate([np.stack([x, 0 * x, 0 * x], 1), np.stack([x, 0 * x + 0.5, 0 * x], 1)])
+    k = np.arange(m, dtype=np.int32)
+    st = np.stack([np.stack([k, k + 1, m + 1 + k], 1), np.stack([k + 1, m + 2 + k, m + 1 + k], 1)], 1).reshape(-1, 3)
+    return sv, st
+
+
+@functools.lru_cache(maxsize=None)
 def _meshes():
     square = (np.float32([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0]]), np.int32([[0, 1, 2], [0, 2, 3]]))
     v = np.float32([[0, 0, 0], [2, 0, 0], [2, 1, 0], [0, 1, 0], [np.nan, 0, 0], [0, 0, 3]])                 # areas 1, 1, 3/2: exact sums
     holes = (v, np.int32([[0, 1, 1], [0, 1, 2], [0, 1, 4], [0, 2, 3], [0, 1, 9], [0, -1, 2], [0, 3, 5]]))      # zero-area, NaN, out of range
     single = (np.float32([[1, 2, 3], [1.5, 2, 3.25], [0.75, 4, 2]]), np.int32([[0, 1, 2]]))
-    # a strip of 600 right triangles with legs 1/128 and 1/2 (area 2^-9: every partial sum is exact), more than two block sums
-    x = np.arange(301, dtype=np.float32) / 128
-    sv = np.concatenate([np.stack([x, 0 * x, 0 * x], 1), np.stack([x, 0 * x + 0.5, 0 * x], 1)])
-    st = np.concatenate([[[k, k + 1, 301 + k], [k + 1, 302 + k, 301 + k]] for k in range(300)]).astype(np.int32)
-    return dict(square=square, holes=holes, single=single, strip=(sv, st))
+    # strip: 600 triangles, more than two block sums.  long_strip: the scan of the block sums (csrc/scan.h) takes 1024 of them
+    # per round, so 1024 blocks of 256 triangles and one more block, of two triangles, is the first size with a second round;
+    # the sums being exact, the triangle ids equal the float64 oracle's there too.
+    return dict(square=square, holes=holes, single=single, strip=_strip(300), long_strip=_strip((1024 * 256 + 2) // 2))
 
 
-@pytest.mark.parametrize('n', (1, 255, 257, 2000))
-@pytest.mark.parametrize('name', ('square', 'holes', 'single', 'strip'))
+@pytest.mark.parametrize('name,n', [(name, n) for name in ('square', 'holes', 'single', 'strip') for n in (1, 255, 257, 2000)] +
+                         [('long_strip', 257), ('long_strip', 2000)])
 def test_the_mesh_sampler(cuda, name, n):
     v, t = _meshes()[name]
     p, tri = geometry.sample_mesh(dict(vertices=v, triangles=t), n)
@@ -268,11 +279,14 @@ def test_the_mesh_sampler(cuda, name, n):
     nrm = np.cross(e1, e2)
     nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
     assert (np.abs(np.einsum('ij,ij->i', w, nrm)) <= 1e-6 * max(scale, 1.0)).all()
-    for p0, p1, p2 in ((a, b, c), (b, c, a), (c, a, b)):                                            # inside: on the third vertex's side of every edge
+    # inside: on the third vertex's side of every edge, to 1e-6 on the small meshes (coordinates <= 4, whose fp32 ulp is below
+    # it).  A stored coordinate of size `scale` is off by up to half its fp32 ulp, 2^-14 on the long strip: one ulp there.
+    slack = max(1e-6, float(M.ulp32(scale)))
+    for p0, p1, p2 in ((a, b, c), (b, c, a), (c, a, b)):
         inward = np.cross(nrm, p1 - p0)
         inward /= np.linalg.norm(inward, axis=1, keepdims=True)
         inward *= np.sign(np.einsum('ij,ij->i', inward, p2 - p0))[:, None]
-        assert (np.einsum('ij,ij->i', p.astype(np.float64) - p0, inward) >= -1e-6).all()
+        assert (np.einsum('ij,ij->i', p.astype(np.float64) - p0, inward) >= -slack).all()
 
 
 def test_a_mesh_without_area_gives_nan(cuda):

@@ -249,8 +249,14 @@ def _mask(kind, n):
     return m
 
 
-@pytest.mark.parametrize('kind', ['all', 'none', 'alternating', 'ends', 'random'])
-@pytest.mark.parametrize('n', [1, B - 1, B, B + 1, 3 * B + 17])
+# the scan of the block sums (csrc/scan.h) takes 1024 of them per round: the last size with one round, the first with two (the
+# second holds one block of one ray), and one with three
+ROUND = 1024 * B
+
+
+@pytest.mark.parametrize('n,kind', [(n, kind) for kind in ('all', 'none', 'alternating', 'ends', 'random')
+                                    for n in (1, B - 1, B, B + 1, 3 * B + 17)] +
+                         [(n, kind) for kind in ('all', 'ends', 'random') for n in (ROUND, ROUND + 1, 2 * ROUND + 257)])
 def test_compaction_is_exact_and_touches_nothing_else(cuda, n, kind):
     rs = np.random.default_rng(n)
     valid = _mask(kind, n)

@@ -6,8 +6,6 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -26,13 +24,7 @@ def _err():
 # ---- the library ----------------------------------------------------------------------------------------------------------
 def test_symbols_are_declared_bound_and_exported_by_a_library_of_their_own():
     hdr = open(os.path.join(ROOT, 'include', 'durf_lidar.h')).read()
-    declared = set(re.findall(r'\b(durf_[a-z0-9_]+)\s*\(', re.sub(r'/\*.*?\*/', ' ', hdr, flags=re.S)))
-    assert declared == ENTRY == set(_lib.lidar_symbols())
-    _lib.lidar_lib()
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIDAR_LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert {ln.split()[-1] for ln in out.splitlines() if ' T ' in ln and ln.split()[-1].startswith('durf_')} == declared
-    assert not declared & set(_lib.symbols()) and not declared & set(_lib.overlay_symbols())
-    assert subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'gen_integration_stub.py'), '--check'], cwd=ROOT).returncode == 0
+    assert ENTRY == set(_lib.lidar_symbols())          # (header == table == symbol table: tests/test_satellites_host.py)
     for name, value in (('SENSOR_FLOATS', ops.LIDAR_SENSOR_FLOATS), ('SWEEP_FLOATS', ops.LIDAR_SWEEP_FLOATS),
                         ('COMPACT_BLOCK', ops.LIDAR_COMPACT_BLOCK), ('POINT_FLOATS', ops.LIDAR_POINT_FLOATS)):
         assert int(re.search(r'#define DURF_LIDAR_%s (\d+)' % name, hdr).group(1)) == value, name

@@ -6,8 +6,6 @@ durf_amd/mesh.py."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 import types
 
 import numpy as np
@@ -31,18 +29,8 @@ def _err():
 # ---- the binding ----------------------------------------------------------------------------------------------------------------
 def test_header_sigs_and_symbol_table_agree():
     hdr = open(os.path.join(ROOT, 'include', 'durf_mesh.h')).read()
-    body = re.sub(r'/\*.*?\*/', ' ', hdr, flags=re.S)
-    declared = set(re.findall(r'\b(durf_mesh_\w+)\s*\(', body))
-    assert declared == ENTRY == set(_lib.mesh_symbols())
-    _lib.mesh_lib()
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.MESH_LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert {ln.split()[-1] for ln in out.splitlines() if ' T ' in ln and ln.split()[-1].startswith('durf_')} == declared
-    for other in (_lib.symbols(), _lib.overlay_symbols(), _lib.lidar_symbols(), _lib.flow_symbols(), _lib.field_symbols()):
-        assert not declared & set(other)
-    base = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert not declared & {ln.split()[-1] for ln in base.splitlines()}, 'libdurf_hip.so keeps its own set of entry points'
+    assert ENTRY == set(_lib.mesh_symbols())           # (header == table == symbol table: tests/test_satellites_host.py)
     assert len(_lib.symbols()) == 118
-    assert subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'gen_integration_stub.py'), '--check'], cwd=ROOT).returncode == 0
     assert int(re.search(r'#define DURF_MESH_BLOCK (\d+)', hdr).group(1)) == ops.MESH_BLOCK == 256
     for rule in ('e + 1 = 4 di + 2 dj + dk', '(0,1,2), (0,2,1), (1,0,2), (1,2,0), (2,0,1), (2,1,0)', '(ab, ac, ad)',
                  '(ac, ad, bd) and (ac, bd, bc)', 'emitted as (x, z, y)'):

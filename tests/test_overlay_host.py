@@ -212,23 +212,16 @@ def test_overlay_arguments():
 
 
 def test_symbols_are_declared_bound_and_exported_by_a_library_of_their_own():
-    """include/durf_overlay.h, durf_amd/_overlay_sigs.py and libdurf_overlay.so's dynamic symbol table name the same two entry
-    points; libdurf_hip.so and its header name neither; refusals need no device and are read from libdurf_hip.so's
+    """libdurf_overlay.so has the two entry points (that its header, its table and its symbol table name the same ones, and no
+    other library does: tests/test_satellites_host.py); refusals need no device and are read from libdurf_hip.so's
     durf_last_error."""
     import os
     import re
-    import subprocess
-    import sys
     from durf_amd import _lib, ops
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     hdr = open(os.path.join(root, 'include', 'durf_overlay.h')).read()
-    declared = set(re.findall(r'\b(durf_[a-z0-9_]+)\s*\(', re.sub(r'/\*.*?\*/', ' ', hdr, flags=re.S)))
-    assert declared == {'durf_project_boxes', 'durf_draw_boxes'} == set(_lib.overlay_symbols())
+    assert {'durf_project_boxes', 'durf_draw_boxes'} == set(_lib.overlay_symbols())
     L = _lib.overlay_lib()
-    out = subprocess.run(['nm', '-D', '--defined-only', _lib.OVERLAY_LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert {ln.split()[-1] for ln in out.splitlines() if ' T ' in ln and ln.split()[-1].startswith('durf_')} == declared
-    assert not declared & set(_lib.symbols())
-    assert subprocess.run([sys.executable, os.path.join(root, 'tools', 'gen_integration_stub.py'), '--check'], cwd=root).returncode == 0
     assert int(re.search(r'#define DURF_BOX_EDGES (\d+)', hdr).group(1)) == ops.BOX_EDGES == O.EDGES
     assert int(re.search(r'#define DURF_BOX_RECT_FLOATS (\d+)', hdr).group(1)) == ops.BOX_RECT_FLOATS == len(ops.BOX_RECT_FIELDS)
     assert L.durf_project_boxes(None, 1, 17, None, None, None, None, 0.5, None, None) != 0

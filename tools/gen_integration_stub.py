@@ -1,34 +1,22 @@
 #!/usr/bin/env python3
 """include/durf_hip.h -> the reference-side ctypes binding (include/durf_ctypes_stub.py) and the copy of it
 embedded in INTEGRATION.md, and the product's own table durf_amd/_sigs.py, so that no copy can drift from the header;
-include/durf_overlay.h (libdurf_overlay.so, a library of its own) -> durf_amd/_overlay_sigs.py,
-include/durf_lidar.h (libdurf_lidar.so) -> durf_amd/_lidar_sigs.py and include/durf_flow.h (libdurf_flow.so) ->
-durf_amd/_flow_sigs.py, include/durf_field.h (libdurf_field.so) -> durf_amd/_field_sigs.py and include/durf_mesh.h
-(libdurf_mesh.so) -> durf_amd/_mesh_sigs.py and include/durf_geom.h (libdurf_geom.so) -> durf_amd/_geom_sigs.py likewise:
-    python tools/gen_integration_stub.py            # rewrite both
-    python tools/gen_integration_stub.py --check    # exit 1 if either is stale (tests/test_host_logic.py)
+include/durf_<name>.h (libdurf_<name>.so, a library of its own) -> durf_amd/_<name>_sigs.py likewise, for every <name> in
+durf_amd._lib.SATELLITES:
+    python tools/gen_integration_stub.py            # rewrite all
+    python tools/gen_integration_stub.py --check    # exit 1 if any is stale (tests/test_host_logic.py)
 The parser handles exactly the C subset the header uses (scalar / pointer parameters, /* */ comments)."""
 import os
 import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from durf_amd._lib import SATELLITES  # noqa: E402  (the import reads no satellite's table: one may be missing or stale)
 HDR = os.path.join(ROOT, 'include', 'durf_hip.h')
 STUB = os.path.join(ROOT, 'include', 'durf_ctypes_stub.py')
 SIGS = os.path.join(ROOT, 'durf_amd', '_sigs.py')          # the product's own binding table (durf_amd/_lib.py)
 DOC = os.path.join(ROOT, 'INTEGRATION.md')
-OVERLAY_HDR = os.path.join(ROOT, 'include', 'durf_overlay.h')
-OVERLAY_SIGS = os.path.join(ROOT, 'durf_amd', '_overlay_sigs.py')  # the binding table of libdurf_overlay.so
-LIDAR_HDR = os.path.join(ROOT, 'include', 'durf_lidar.h')
-LIDAR_SIGS = os.path.join(ROOT, 'durf_amd', '_lidar_sigs.py')      # the binding table of libdurf_lidar.so
-FLOW_HDR = os.path.join(ROOT, 'include', 'durf_flow.h')
-FLOW_SIGS = os.path.join(ROOT, 'durf_amd', '_flow_sigs.py')        # the binding table of libdurf_flow.so
-FIELD_HDR = os.path.join(ROOT, 'include', 'durf_field.h')
-FIELD_SIGS = os.path.join(ROOT, 'durf_amd', '_field_sigs.py')      # the binding table of libdurf_field.so
-MESH_HDR = os.path.join(ROOT, 'include', 'durf_mesh.h')
-MESH_SIGS = os.path.join(ROOT, 'durf_amd', '_mesh_sigs.py')        # the binding table of libdurf_mesh.so
-GEOM_HDR = os.path.join(ROOT, 'include', 'durf_geom.h')
-GEOM_SIGS = os.path.join(ROOT, 'durf_amd', '_geom_sigs.py')        # the binding table of libdurf_geom.so
 BEGIN, END = '<!-- BEGIN GENERATED: tools/gen_integration_stub.py -->', '<!-- END GENERATED -->'
 
 SCALARS = {'int': 'i32', 'float': 'f32', 'size_t': 'u64', 'int32_t': 'i32', 'uint32_t': 'C.c_uint32'}
@@ -106,36 +94,19 @@ def doc_with_stub(doc, stub):
 
 def main():
     stub = render()
-    sigs = render_sigs()
-    overlay_sigs = render_sigs(OVERLAY_HDR, 'libdurf_overlay.so')
-    lidar_sigs = render_sigs(LIDAR_HDR, 'libdurf_lidar.so')
-    flow_sigs = render_sigs(FLOW_HDR, 'libdurf_flow.so')
-    field_sigs = render_sigs(FIELD_HDR, 'libdurf_field.so')
-    mesh_sigs = render_sigs(MESH_HDR, 'libdurf_mesh.so')
-    geom_sigs = render_sigs(GEOM_HDR, 'libdurf_geom.so')
+    files = {STUB: stub, SIGS: render_sigs()}
+    for name in SATELLITES:          # include/durf_<name>.h -> the binding table of libdurf_<name>.so
+        files[os.path.join(ROOT, 'durf_amd', '_%s_sigs.py' % name)] = render_sigs(os.path.join(ROOT, 'include', 'durf_%s.h' % name),
+                                                                              'libdurf_%s.so' % name)
     doc = open(DOC).read()
-    new_doc = doc_with_stub(doc, stub)
+    files[DOC] = doc_with_stub(doc, stub)
     if '--check' in sys.argv:
-        ok = (os.path.exists(STUB) and open(STUB).read() == stub and new_doc == doc and
-              os.path.exists(SIGS) and open(SIGS).read() == sigs and
-              os.path.exists(OVERLAY_SIGS) and open(OVERLAY_SIGS).read() == overlay_sigs and
-              os.path.exists(LIDAR_SIGS) and open(LIDAR_SIGS).read() == lidar_sigs and
-              os.path.exists(FLOW_SIGS) and open(FLOW_SIGS).read() == flow_sigs and
-              os.path.exists(FIELD_SIGS) and open(FIELD_SIGS).read() == field_sigs and
-              os.path.exists(MESH_SIGS) and open(MESH_SIGS).read() == mesh_sigs and
-              os.path.exists(GEOM_SIGS) and open(GEOM_SIGS).read() == geom_sigs)
+        ok = all(os.path.exists(path) and open(path).read() == text for path, text in files.items())
         if not ok:
             print('stale: run python tools/gen_integration_stub.py')
         sys.exit(0 if ok else 1)
-    open(STUB, 'w').write(stub)
-    open(SIGS, 'w').write(sigs)
-    open(OVERLAY_SIGS, 'w').write(overlay_sigs)
-    open(LIDAR_SIGS, 'w').write(lidar_sigs)
-    open(FLOW_SIGS, 'w').write(flow_sigs)
-    open(FIELD_SIGS, 'w').write(field_sigs)
-    open(MESH_SIGS, 'w').write(mesh_sigs)
-    open(GEOM_SIGS, 'w').write(geom_sigs)
-    open(DOC, 'w').write(new_doc)
+    for path, text in files.items():
+        open(path, 'w').write(text)
     print('wrote %s (%d functions) and the block in INTEGRATION.md' % (os.path.relpath(STUB, ROOT), len(parse_header())))
 
 
