@@ -15,7 +15,7 @@ means and the thresholds (<= max_dist) need.  The grid rule of include/durf_geom
 cells per axis) makes the result equal to a brute-force search in the same fp32 arithmetic, bit for bit."""
 import numpy as np
 
-MAX_CELLS = 2048                    # DURF_GEOM_MAX_CELLS
+from ._geom_sigs import DURF_GEOM_MAX_CELLS as MAX_CELLS        # per axis (include/durf_geom.h)
 SLACK = 1.0 + 2.0 ** -10            # a cell is max_dist * SLACK wide
 SORT_QUERIES = True                 # nearest()'s default: queries in the order of their own cell keys (profiles/geometry_time.txt)
 DEFAULT_THRESHOLDS = (0.05, 0.1, 0.2, 0.5)

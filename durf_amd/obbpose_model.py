@@ -17,7 +17,7 @@ import torch
 from . import ops
 from . import utils
 
-IN_BKGD, IN_OBJ, W_BKGD, W_OBJ = 60, 63, 256, 128
+IN_BKGD, IN_OBJ, W_BKGD, W_OBJ = 60, 63, ops.W_BKGD, ops.W_OBJ
 
 
 # ----------------------------------------------------------------------------

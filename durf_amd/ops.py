@@ -9,9 +9,22 @@ import os
 import torch
 
 from . import _lib
+from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs
 
-ENC_DIM = 64
-VIEW_DIM = 32
+
+
+def _by_prefix(table, prefix):
+    """{X: value} of a generated table's integer constants named <prefix>X, in header order"""
+    return {k[len(prefix):]: v for k, v in vars(table).items() if k.startswith(prefix) and type(v) is int}
+
+
+# The headers are the one place a constant or an argument struct is written (tools/gen_integration_stub.py renders them into
+# the tables imported above; tests/test_headers_host.py holds the tables to the C compiler).  Every `#define DURF_X <integer>`
+# of include/durf_hip.h and include/durf_<name>.h is ops.X: ENC_DIM, MAX_OBJ, TRAIN_OBJ_FP32, TIMED_STAGES, MESH_BLOCK, ...
+# -- all but OVERLAP_MIN_ROWS, launch policy that the library is asked for (__getattr__ below).
+for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs):
+    globals().update(_by_prefix(_table, 'DURF_'))
+del OVERLAP_MIN_ROWS
 
 
 def _stream():
@@ -251,13 +264,10 @@ def tile_rows(rows):
     return (rows + 31) // 32 * 32
 
 
-# include/durf_hip.h DURF_DISPATCH_*: the kernel variants the launchers choose by size (tests/test_gpu_dispatch_matrix.py)
-DISPATCH = dict(FWD256_8W=0x1, FWD256_4W=0x2, FWD128_SAMPLE=0x4, FWD128_MSPLIT=0x8, BWD256_8W=0x10, BWD256_4W=0x20,
-                BWD128_SAMPLE=0x40, BWD128_MSPLIT=0x80, DW256_256WG=0x100, DW256_512WG=0x200, DW128_128WG=0x400,
-                DW128_256WG=0x800, FWD_ENC=0x1000, FWD_RAW_FULL=0x2000, FWD_TAIL=0x4000, F32_DW_TILE=0x8000,
-                F32_DW_B2=0x10000, BWD_POSE=0x20000, FWD_MIX=0x40000, BWD_MIX=0x80000)
-# include/durf_hip.h DURF_LAYERLOG_*: marks of the scene-layer launches in the same log word (tests/test_gpu_layers.py)
-LAYER_LOG = dict(SELECT=0x100000, PASS2=0x200000, BOX_MASK=0x400000, TRAJ_RAYS=0x800000, TRAJ_POSE=0x1000000, TRAJ_PACK=0x2000000)
+# the kernel variants the launchers choose by size (tests/test_gpu_dispatch_matrix.py)
+DISPATCH = _by_prefix(_H, 'DURF_DISPATCH_')
+# marks of the scene-layer launches in the same log word (tests/test_gpu_layers.py)
+LAYER_LOG = _by_prefix(_H, 'DURF_LAYERLOG_')
 
 
 def dispatch_reset():
@@ -274,10 +284,6 @@ def layer_log_seen():
     """which scene-layer launches ran since dispatch_reset() (DURF_LAYERLOG_*)"""
     m = int(_lib.lib().durf_dispatch_seen())
     return {k for k, b in LAYER_LOG.items() if m & b}
-
-
-ENC_CONTRACT, ENC_NO_INTEGRATION, ENC_CYLINDER = 1, 2, 4
-FWD_RAW_FULL = 8          # mlp_fwd_enc only (include/durf_hip.h DURF_FWD_RAW_FULL)
 
 
 def encode_bkgd(t_vals, origins_s, dirs_s, radii, hit, contraction=True, tile=True, f32=False,
@@ -652,12 +658,7 @@ def loss_bwd(raw_bkgd, raw_obj, slot, t_vals, dirs_s, pixels, lossmult, gt_depth
     return draw, (terms if defer_sums else sums)
 
 
-class LossLevel(C.Structure):
-    """durf_loss_level (include/durf_hip.h), field for field"""
-    _fields_ = ([('raw_bkgd', C.c_void_p), ('raw_obj', C.c_void_p * 16), ('t_vals', C.c_void_p), ('norm', C.c_void_p),
-                 ('mults', C.c_float * 6), ('level', C.c_int)] +
-                [(n, C.c_void_p) for n in ('draw', 'terms', 'rgb_out', 'depth_out', 'acc_out', 'weights_out', 't_mids_out',
-                                           't_dists_out', 'draw_ray_sum')])
+LossLevel = _H.durf_loss_level
 
 
 def loss_bwd_levels(levels, slot, dirs_s, pixels, lossmult, gt_depth, sky, dyn, zo, eps, box_loss_mult, bg, density_bias=-1.0,
@@ -798,9 +799,6 @@ class Comm:
             self.handle = None
 
 
-COMM_ID_BYTES = 128
-
-
 def comm_available():
     return bool(_lib.lib().durf_comm_available())
 
@@ -898,8 +896,8 @@ def mlp_dw_finalize(width, in_dim, rows, N, nlevels, part, bpart, grad_mlp, mlp_
 # ---------------------------------------------------------------------------
 # the K object MLPs of one level as one call each (csrc/objects.hip)
 # ---------------------------------------------------------------------------
-W_OBJ_, IN_OBJ_ = 128, 63
-W_BKGD_, IN_BKGD = 256, 60
+W_OBJ_, IN_OBJ_ = W_OBJ, 63
+W_BKGD_, IN_BKGD = W_BKGD, 60
 
 
 class ObjSlabs:
@@ -1322,9 +1320,6 @@ class ObjSlabsF32:
         return [self.raw[k] for k in range(self.K)]
 
 
-F32_X3 = 16               # durf_objf32_fwd_batch flag (include/durf_hip.h DURF_F32_X3)
-
-
 def objf32_fwd_batch(slabs, idx, count, t_vals, origins_s, dirs_s, radii, alpha, view27, obj_params, param_stride, wstream,
                      disable_integration=False, cylinder=False, fused_encode=True, x3=False):
     """accurate fp32 encodings + fp32 forward of all K object MLPs of one level: ONE launch (the forward encodes its own
@@ -1385,44 +1380,8 @@ def objf32_dw_batch(slabs_levels, count, grad_obj, grad_stride, nsplit=8):
 # ---------------------------------------------------------------------------------------------------------------------
 # the whole inference forward as one C call (csrc/forward.hip, include/durf_hip.h durf_forward)
 # ---------------------------------------------------------------------------------------------------------------------
-FORWARD_MAX_LEVELS = 4
+ForwardArgs, TrainArgs, StepTiming = _H.durf_forward_args, _H.durf_train_args, _H.durf_step_timing
 _vp4 = C.c_void_p * FORWARD_MAX_LEVELS
-
-
-class ForwardArgs(C.Structure):
-    """durf_forward_args (include/durf_hip.h), field for field"""
-    _fields_ = ([(n, C.c_int) for n in ('B', 'N', 'K', 'num_levels', 'enc_flags', 'lindisp', 'bkgd_mode')] +
-                [('density_bias', C.c_float), ('resample_padding', C.c_float), ('barf_w', C.c_float * 10)] +
-                [(n, C.c_void_p) for n in ('origins', 'directions', 'viewdirs', 'radii', 'near', 'far', 'pose', 'ext',
-                                           'bkgd_params', 'obj_params')] +
-                [('obj_param_stride', C.c_size_t), ('t_rand', C.c_void_p), ('u_rand', C.c_void_p)] +
-                [(n, _vp4) for n in ('rgb', 'depth', 'acc', 'weights', 't_vals', 't_mids', 't_dists')] +
-                [('dyn_mask', C.c_void_p), ('zo', C.c_void_p), ('draw_noise', C.c_int), ('seed_lo', C.c_uint32),
-                 ('seed_hi', C.c_uint32), ('density_noise', C.c_float), ('density_rand', _vp4)])
-
-
-class TrainArgs(C.Structure):
-    """durf_train_args (include/durf_hip.h), field for field"""
-    _fields_ = ([('f', ForwardArgs)] +
-                [(n, C.c_void_p) for n in ('lossmult', 'pixels', 'gt_depth', 'sky', 'target6', 'prev6')] +
-                [('eps', C.c_float), ('box_loss_mult', C.c_float), ('bg', C.c_float), ('disable_multiscale', C.c_int),
-                 ('level_mults', (C.c_float * 6) * FORWARD_MAX_LEVELS), ('stat_mults', C.c_float * 6), ('params', C.c_void_p)] +
-                [(n, C.c_size_t) for n in ('n_params', 'box_floats', 'mlp0_floats', 'obj_floats')] +
-                [(n, C.c_void_p) for n in ('grad', 'stats', 'adam_m', 'adam_v')] +
-                [('lr', C.c_float), ('max_val', C.c_float), ('max_norm', C.c_float), ('step', C.c_int), ('grad_stats', C.c_void_p),
-                 ('flags', C.c_int), ('want_pos', C.c_int), ('want_rot', C.c_int), ('tv_loss_mult', C.c_float),
-                 ('comm', C.c_void_p), ('world', C.c_int), ('reduce_stats', C.c_int), ('weight_decay_mult', C.c_float),
-                 ('pose_used', C.c_void_p), ('cls_count', C.c_void_p), ('timing', C.c_void_p),
-                 ('const_trunk', C.c_void_p), ('const_trunk_valid', C.c_int), ('prefetch_const_trunk', C.c_int)])
-
-
-TRAIN_OBJ_FP32, TRAIN_POSE_OPT, TRAIN_OBJ_X3 = 1, 2, 4          # durf_train_args.flags
-TIMED_FWD, TIMED_BWD, TIMED_COMPOSITE, TIMED_DW, TIMED_STAGES = 0, 4, 8, 12, 13      # durf_step_timing slots
-
-
-class StepTiming(C.Structure):
-    """durf_step_timing (include/durf_hip.h)"""
-    _fields_ = [('begin', C.c_void_p * TIMED_STAGES), ('end', C.c_void_p * TIMED_STAGES)]
 
 
 def _step_timing(num_levels, keep):
@@ -1706,10 +1665,9 @@ def train_call(rays, pose, ext, params_flat, m, v, box_floats, mlp0_floats, obj_
 
 
 # ---- depth visualisations (csrc/vis.hip; include/durf_hip.h durf_vis_*) -----------------------------------------------------
-VIS_CURVES = dict(neglog=0, identity=1, inverse=2)       # DURF_VIS_CURVE_*
-VIS_STATS_FLOATS = 8                                     # DURF_VIS_STATS_FLOATS
+VIS_CURVES = {k.lower(): v for k, v in _by_prefix(_H, 'DURF_VIS_CURVE_').items()}
 VIS_STATS_FIELDS = ('near_auto', 'far_auto', 'normal_scale', 'count', 'var_x', 'var_y', 'var_depth', 'mean_depth')
-VIS_NORMALS_RAW = 1
+assert len(VIS_STATS_FIELDS) == VIS_STATS_FLOATS
 
 
 def _vis_outputs(shape, dev, want_float, want_u8, rgb, rgb8):
@@ -1788,10 +1746,9 @@ def vis_turbo_lut():
 
 
 # ---- evaluation metrics of F frames (csrc/metrics.hip; include/durf_hip.h durf_eval_frames) --------------------------------
-EVAL_FLOATS = 10                                         # DURF_EVAL_FLOATS
-EVAL_FIELDS = ('mse', 'psnr', 'ssim', 'obj_count', 'obj_mse', 'obj_psnr', 'depth_count', 'depth_abs', 'depth_rmse',
-               'nonfinite')                              # DURF_EVAL_* in index order
-EVAL_INDEX = {name: i for i, name in enumerate(EVAL_FIELDS)}
+EVAL_INDEX = {k.lower(): v for k, v in _by_prefix(_H, 'DURF_EVAL_').items() if k != 'FLOATS'}      # mse: 0, psnr: 1, ...
+EVAL_FIELDS = tuple(sorted(EVAL_INDEX, key=EVAL_INDEX.get))
+assert [EVAL_INDEX[name] for name in EVAL_FIELDS] == list(range(EVAL_FLOATS))
 
 
 def eval_frames(rgb, gt_rgb, distance=None, gt_depth=None, obj_mask=None):
@@ -1819,10 +1776,8 @@ def eval_frames(rgb, gt_rgb, distance=None, gt_depth=None, obj_mask=None):
 
 
 # ---- the scene's boxes on rendered frames (csrc/overlay.hip, libdurf_overlay.so; include/durf_overlay.h) -------
-BOX_EDGES = 12                                           # DURF_BOX_EDGES
-BOX_RECT_FLOATS = 6                                      # DURF_BOX_RECT_FLOATS
 BOX_RECT_FIELDS = ('xmin', 'ymin', 'xmax', 'ymax', 'zc', 'visible')
-MAX_OBJ = 16                                             # DURF_MAX_OBJ
+assert len(BOX_RECT_FIELDS) == BOX_RECT_FLOATS
 
 
 def project_boxes(cams, poses, ext, box_enable=None, znear=1e-2):
@@ -1862,11 +1817,10 @@ def draw_boxes(segments, colors, half_width, opacity=1.0, frames8=None, framesf=
 
 
 # ---- LIDAR sweeps (csrc/lidar.hip, libdurf_lidar.so; include/durf_lidar.h) -------------------------------------
-LIDAR_SENSOR_FLOATS = 6                                  # DURF_LIDAR_SENSOR_FLOATS: H, W, az0, az_span, radius_scale, max_range
-LIDAR_SWEEP_FLOATS = 18                                  # DURF_LIDAR_SWEEP_FLOATS: pose_start [3,4], omega [3], dp [3]
-LIDAR_COMPACT_BLOCK = 256                                # DURF_LIDAR_COMPACT_BLOCK
-LIDAR_POINT_FLOATS = 8                                   # DURF_LIDAR_POINT_FLOATS
+# (LIDAR_SENSOR_FLOATS: H, W, az0, az_span, radius_scale, max_range; LIDAR_SWEEP_FLOATS: pose_start [3,4], omega [3], dp [3])
 LIDAR_POINT_FIELDS = ('x', 'y', 'z', 'range', 'r', 'g', 'b', 'dynamic')
+assert len(LIDAR_POINT_FIELDS) == LIDAR_POINT_FLOATS
+lidar_compact_scratch = _lidar_sigs.DURF_LIDAR_COMPACT_SCRATCH          # (n): int32 elements of durf_lidar_compact's scratch
 LIDAR_OUTPUTS = ('range', 'range_mean', 'distance', 'acc', 'rgb', 'spread', 'dynamic', 'valid', 'xyz')      # in argument order
 
 
@@ -1876,11 +1830,6 @@ def _host_floats(values, n, what):
     if a.size != n:
         raise ValueError('%s: %d floats, expected %d' % (what, a.size, n))
     return (C.c_float * n)(*a.tolist())
-
-
-def lidar_compact_scratch(n):
-    """DURF_LIDAR_COMPACT_SCRATCH(n): int32 elements of durf_lidar_compact's scratch"""
-    return (n + LIDAR_COMPACT_BLOCK - 1) // LIDAR_COMPACT_BLOCK + 1
 
 
 def lidar_rays(sensor_row, inclinations, sweep_row, near, far, first=0, count=None):
@@ -1985,22 +1934,12 @@ def render_lidar(sensor_row, inclinations, sweep_rows, poses, ext, bkgd_params, 
 
 
 # ---- motion between frames (csrc/flow.hip, libdurf_flow.so; include/durf_flow.h) -------------------------------
-FLOW_CONS_FLOATS = 4                                     # DURF_FLOW_CONS_FLOATS
 FLOW_CONS_FIELDS = ('count', 'sse', 'sae', 'psnr')
-FLOW_CONS_SPAN = 4096                                    # DURF_FLOW_CONS_SPAN
-FLOW_WHEEL = 55                                          # DURF_FLOW_WHEEL
+assert len(FLOW_CONS_FIELDS) == FLOW_CONS_FLOATS
+flow_pose_floats = _flow_sigs.DURF_FLOW_POSE_FLOATS             # (K): floats of durf_flow_points' pose scratch
+flow_cons_scratch = _flow_sigs.DURF_FLOW_CONS_SCRATCH           # (P, m): floats of durf_flow_consistency's scratch
 FLOW_OUTPUTS = ('flow', 'scene_flow', 'xyz', 'target', 'zcam', 'moving', 'valid')      # in argument order
 _FLOW_COLS = dict(flow=2, scene_flow=3, xyz=3, target=3, zcam=None, moving=None, valid=None)
-
-
-def flow_pose_floats(K):
-    """DURF_FLOW_POSE_FLOATS(K): floats of durf_flow_points' pose scratch"""
-    return 2 * K * 12
-
-
-def flow_cons_scratch(P, m):
-    """DURF_FLOW_CONS_SCRATCH(P, m): floats of durf_flow_consistency's scratch"""
-    return P * ((m + FLOW_CONS_SPAN - 1) // FLOW_CONS_SPAN) * 3
 
 
 def _flow_outputs(outputs, lead, dev, out=None):
@@ -2115,15 +2054,8 @@ def render_flow(cams, poses, ext, distance, acc, pairs, near, far, chunk, *, box
 # ---------------------------------------------------------------------------
 # the field at world points (include/durf_field.h, csrc/field.hip, libdurf_field.so): staged calls and the one-call walks
 # ---------------------------------------------------------------------------
-FIELD_ENC_BKGD, FIELD_ENC_OBJ = 60, 63
-
-
-class FieldArgs(C.Structure):
-    """durf_field_args (include/durf_field.h), field for field"""
-    _fields_ = ([('K', C.c_int), ('enc_flags', C.c_int), ('sigma', C.c_float), ('inside_tol', C.c_float), ('density_bias', C.c_float),
-                 ('barf_w', C.c_float * 10), ('bkgd_params', C.c_void_p), ('obj_params', C.c_void_p), ('param_stride', C.c_size_t)] +
-                [(n, C.c_void_p) for n in ('bkgd_wstream', 'obj_wstream', 'const_trunk', 'pose', 'ext', 'box_enable', 'points',
-                                           'viewdirs', 'density', 'rgb', 'raw', 'owner', 'valid')])
+FieldArgs = _field_sigs.durf_field_args
+field_pose_floats = _field_sigs.DURF_FIELD_POSE_FLOATS          # (K): floats of durf_field_classify's pose scratch
 
 
 def _barf_host(alpha):
@@ -2136,7 +2068,7 @@ def field_classify(points, pose, ext, box_enable=None, inside_tol=0.0):
     dev = points.device
     owner = torch.empty(n, dtype=torch.int32, device=dev)
     local = torch.empty(n, 3, device=dev)
-    table = torch.empty(max(K, 1) * 12, device=dev)
+    table = torch.empty(field_pose_floats(max(K, 1)), device=dev)
     with _Timed('field_classify'):
         _lib.check(_lib.field_lib().durf_field_classify(_stream(), n, _p(_f32(points)), K, _p(_f32(pose)) if K else None,
                                                         _p(_f32(ext)) if K else None, _p(box_enable), float(inside_tol), _p(table),
@@ -2268,9 +2200,6 @@ def field_columns(density, valid, shape, step, threshold):
 # ---------------------------------------------------------------------------
 # the iso-surface of a density lattice (include/durf_mesh.h, csrc/mesh.hip, libdurf_mesh.so)
 # ---------------------------------------------------------------------------
-MESH_BLOCK = 256                   # DURF_MESH_BLOCK
-
-
 def mesh_workspace_bytes(shape):
     nu, nv, nw = (int(s) for s in shape)
     return int(_lib.mesh_lib().durf_mesh_workspace_bytes(nu, nv, nw))
@@ -2363,12 +2292,8 @@ def mesh_gather(shape, counts, vertex_edge, vertex_t, attr_f=None, attr_i=None, 
 # ---------------------------------------------------------------------------
 # distances between point sets, mesh samples (include/durf_geom.h, csrc/geom.hip, libdurf_geom.so)
 # ---------------------------------------------------------------------------
-GEOM_BLOCK = 256                   # DURF_GEOM_BLOCK
-GEOM_STAT_CHUNK = 1024             # DURF_GEOM_STAT_CHUNK
-GEOM_MAX_CELLS = 2048              # DURF_GEOM_MAX_CELLS
-GEOM_MAX_THRESHOLDS = 8            # DURF_GEOM_MAX_THRESHOLDS
-GEOM_STAT_DOUBLES = 13             # DURF_GEOM_STAT_DOUBLES
 GEOM_STAT_FIELDS = ('usable', 'found', 'sum_found', 'sum_sq_found', 'sum_usable')        # then one count per threshold
+assert len(GEOM_STAT_FIELDS) + GEOM_MAX_THRESHOLDS == GEOM_STAT_DOUBLES
 
 
 def geom_workspace_bytes(n_queries, n_triangles):

@@ -1,10 +1,204 @@
 """ctypes binding of libdurf_hip.so for a reference-side caller -- GENERATED from include/durf_hip.h by
 tools/gen_integration_stub.py (do not edit; `--check` runs in the CPU test-suite).  All `vp` arguments are
 DEVICE pointers of caller-owned buffers except `stream` (hipStream_t); C.POINTER(...) arguments are host
-arrays.  Every call is asynchronous on `stream` and returns 0 or an error code (durf_last_error())."""
+arrays.  Every call is asynchronous on `stream` and returns 0 or an error code (durf_last_error()).  The header's
+constants and argument structs (every pointer field a vp: assign addresses) come first, under their C names."""
 import ctypes as C
 
 vp, i32, f32, u64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+
+
+DURF_MAX_OBJ = 16
+DURF_MAX_LEVELS = 8
+DURF_MAX_CAMS = 8
+DURF_W_BKGD = 256
+DURF_W_OBJ = 128
+DURF_ENC_CONTRACT = 1
+DURF_ENC_NO_INTEGRATION = 2
+DURF_ENC_CYLINDER = 4
+DURF_FWD_RAW_FULL = 8
+DURF_ENC_DIM = 64
+DURF_VIEW_DIM = 32
+DURF_DISPATCH_FWD256_8W = 0x1
+DURF_DISPATCH_FWD256_4W = 0x2
+DURF_DISPATCH_FWD128_SAMPLE = 0x4
+DURF_DISPATCH_FWD128_MSPLIT = 0x8
+DURF_DISPATCH_BWD256_8W = 0x10
+DURF_DISPATCH_BWD256_4W = 0x20
+DURF_DISPATCH_BWD128_SAMPLE = 0x40
+DURF_DISPATCH_BWD128_MSPLIT = 0x80
+DURF_DISPATCH_DW256_256WG = 0x100
+DURF_DISPATCH_DW256_512WG = 0x200
+DURF_DISPATCH_DW128_128WG = 0x400
+DURF_DISPATCH_DW128_256WG = 0x800
+DURF_DISPATCH_FWD_ENC = 0x1000
+DURF_DISPATCH_FWD_RAW_FULL = 0x2000
+DURF_DISPATCH_FWD_TAIL = 0x4000
+DURF_DISPATCH_F32_DW_TILE = 0x8000
+DURF_DISPATCH_F32_DW_B2 = 0x10000
+DURF_DISPATCH_BWD_POSE = 0x20000
+DURF_DISPATCH_FWD_MIX = 0x40000
+DURF_DISPATCH_BWD_MIX = 0x80000
+DURF_LAYERLOG_SELECT = 0x100000
+DURF_LAYERLOG_PASS2 = 0x200000
+DURF_LAYERLOG_BOX_MASK = 0x400000
+DURF_LAYERLOG_TRAJ_RAYS = 0x800000
+DURF_LAYERLOG_TRAJ_POSE = 0x1000000
+DURF_LAYERLOG_TRAJ_PACK = 0x2000000
+DURF_OVERLAP_MIN_ROWS = 262144          # ((size_t)2048 * 128)
+DURF_POLICY_SIDE_FWD = 0x1
+DURF_POLICY_SIDE_BWD = 0x2
+DURF_POLICY_SIDE_DW = 0x4
+DURF_POLICY_MSPLIT = 0x8
+DURF_POLICY_MIX = 0x10
+
+
+class durf_loss_level(C.Structure):
+    _fields_ = [
+        ('raw_bkgd', vp),
+        ('raw_obj', vp * DURF_MAX_OBJ),
+        ('t_vals', vp),
+        ('norm', vp),
+        ('mults', f32 * 6),
+        ('level', i32),
+        ('draw', vp),
+        ('terms', vp),
+        ('rgb_out', vp),
+        ('depth_out', vp),
+        ('acc_out', vp),
+        ('weights_out', vp),
+        ('t_mids_out', vp),
+        ('t_dists_out', vp),
+        ('draw_ray_sum', vp),
+    ]
+
+
+DURF_FORWARD_MAX_LEVELS = 4
+
+
+class durf_forward_args(C.Structure):
+    _fields_ = [
+        ('B', i32),
+        ('N', i32),
+        ('K', i32),
+        ('num_levels', i32),
+        ('enc_flags', i32),
+        ('lindisp', i32),
+        ('bkgd_mode', i32),
+        ('density_bias', f32),
+        ('resample_padding', f32),
+        ('barf_w', f32 * 10),
+        ('origins', vp),
+        ('directions', vp),
+        ('viewdirs', vp),
+        ('radii', vp),
+        ('near', vp),
+        ('far', vp),
+        ('pose', vp),
+        ('ext', vp),
+        ('bkgd_params', vp),
+        ('obj_params', vp),
+        ('obj_param_stride', u64),
+        ('t_rand', vp),
+        ('u_rand', vp),
+        ('rgb', vp * DURF_FORWARD_MAX_LEVELS),
+        ('depth', vp * DURF_FORWARD_MAX_LEVELS),
+        ('acc', vp * DURF_FORWARD_MAX_LEVELS),
+        ('weights', vp * DURF_FORWARD_MAX_LEVELS),
+        ('t_vals', vp * DURF_FORWARD_MAX_LEVELS),
+        ('t_mids', vp * DURF_FORWARD_MAX_LEVELS),
+        ('t_dists', vp * DURF_FORWARD_MAX_LEVELS),
+        ('dyn_mask', vp),
+        ('zo', vp),
+        ('draw_noise', i32),
+        ('seed_lo', C.c_uint32),
+        ('seed_hi', C.c_uint32),
+        ('density_noise', f32),
+        ('density_rand', vp * DURF_FORWARD_MAX_LEVELS),
+    ]
+
+
+DURF_TRAIN_OBJ_FP32 = 1
+DURF_TRAIN_POSE_OPT = 2
+DURF_TRAIN_OBJ_X3 = 4
+DURF_TIMED_FWD = 0
+DURF_TIMED_BWD = 4
+DURF_TIMED_COMPOSITE = 8
+DURF_TIMED_DW = 12
+DURF_TIMED_STAGES = 13
+
+
+class durf_step_timing(C.Structure):
+    _fields_ = [
+        ('begin', vp * DURF_TIMED_STAGES),
+        ('end', vp * DURF_TIMED_STAGES),
+    ]
+
+
+class durf_train_args(C.Structure):
+    _fields_ = [
+        ('f', durf_forward_args),
+        ('lossmult', vp),
+        ('pixels', vp),
+        ('gt_depth', vp),
+        ('sky', vp),
+        ('target6', vp),
+        ('prev6', vp),
+        ('eps', f32),
+        ('box_loss_mult', f32),
+        ('bg', f32),
+        ('disable_multiscale', i32),
+        ('level_mults', (f32 * 6) * DURF_FORWARD_MAX_LEVELS),
+        ('stat_mults', f32 * 6),
+        ('params', vp),
+        ('n_params', u64),
+        ('box_floats', u64),
+        ('mlp0_floats', u64),
+        ('obj_floats', u64),
+        ('grad', vp),
+        ('stats', vp),
+        ('adam_m', vp),
+        ('adam_v', vp),
+        ('lr', f32),
+        ('max_val', f32),
+        ('max_norm', f32),
+        ('step', i32),
+        ('grad_stats', vp),
+        ('flags', i32),
+        ('want_pos', i32),
+        ('want_rot', i32),
+        ('tv_loss_mult', f32),
+        ('comm', vp),
+        ('world', i32),
+        ('reduce_stats', i32),
+        ('weight_decay_mult', f32),
+        ('pose_used', vp),
+        ('cls_count', vp),
+        ('timing', vp),
+        ('const_trunk', vp),
+        ('const_trunk_valid', i32),
+        ('prefetch_const_trunk', i32),
+    ]
+
+
+DURF_COMM_ID_BYTES = 128
+DURF_F32_X3 = 16
+DURF_EVAL_FLOATS = 10
+DURF_EVAL_MSE = 0
+DURF_EVAL_PSNR = 1
+DURF_EVAL_SSIM = 2
+DURF_EVAL_OBJ_COUNT = 3
+DURF_EVAL_OBJ_MSE = 4
+DURF_EVAL_OBJ_PSNR = 5
+DURF_EVAL_DEPTH_COUNT = 6
+DURF_EVAL_DEPTH_ABS = 7
+DURF_EVAL_DEPTH_RMSE = 8
+DURF_EVAL_NONFINITE = 9
+DURF_VIS_CURVE_NEGLOG = 0
+DURF_VIS_CURVE_IDENTITY = 1
+DURF_VIS_CURVE_INVERSE = 2
+DURF_VIS_STATS_FLOATS = 8
+DURF_VIS_NORMALS_RAW = 1
 
 
 def bind(path='durf_amd/libdurf_hip.so'):

@@ -77,9 +77,9 @@ def test_symbols_are_declared_bound_and_exported():
     assert L.durf_version() == 41
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'gen_integration_stub.py'), '--check'], cwd=ROOT)
     assert p.returncode == 0, 'the header, durf_amd/_sigs.py, the stub and INTEGRATION.md have drifted apart'
-    assert int(re.search(r'#define DURF_EVAL_FLOATS (\d+)', hdr).group(1)) == ops.EVAL_FLOATS == len(ops.EVAL_FIELDS) == 10
+    assert ops.EVAL_FLOATS == len(ops.EVAL_FIELDS) == 10          # (DURF_EVAL_* against the header: tests/test_headers_host.py)
     for i, name in enumerate(ops.EVAL_FIELDS):
-        assert int(re.search(r'#define DURF_EVAL_%s (\d+)' % name.upper(), hdr).group(1)) == i == ops.EVAL_INDEX[name]
+        assert i == ops.EVAL_INDEX[name]
     assert ops.EVAL_FIELDS == R.FIELDS
     sb = L.durf_eval_scratch_bytes
     assert sb(0, 37, 53) == 0 and sb(1, 37, 53) > 0

@@ -142,10 +142,7 @@ def test_new_symbols_are_declared_bound_and_exported():
         assert name in _lib._SIGS, name + ' is not in durf_amd/_sigs.py'
         assert hasattr(L, name)
     assert L.durf_version() == 41
-    for key, val in (('CURVE_NEGLOG', ops.VIS_CURVES['neglog']), ('CURVE_IDENTITY', ops.VIS_CURVES['identity']),
-                     ('CURVE_INVERSE', ops.VIS_CURVES['inverse']), ('STATS_FLOATS', ops.VIS_STATS_FLOATS),
-                     ('NORMALS_RAW', ops.VIS_NORMALS_RAW)):
-        assert int(re.search(r'#define DURF_VIS_%s (\d+)' % key, hdr).group(1)) == val
+    assert set(ops.VIS_CURVES) == {'neglog', 'identity', 'inverse'}       # (DURF_VIS_* against the header: tests/test_headers_host.py)
     assert len(ops.VIS_STATS_FIELDS) == ops.VIS_STATS_FLOATS
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'gen_integration_stub.py'), '--check'], cwd=ROOT)
     assert p.returncode == 0, 'the header, durf_amd/_sigs.py, the stub and INTEGRATION.md have drifted apart'
