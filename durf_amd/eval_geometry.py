@@ -4,12 +4,13 @@ precision / recall / F-score at thresholds (durf_amd.geometry):
     python -m durf_amd.eval_geometry --gin_file configs/waymo.gin --data_dir DATA --train_dir CKPT --split test --eval_dir OUT
                                      --grid "ox,oy,oz;nu,nv,nw;step" [--iso V] [--source mesh|frames|lidar] [--samples 200000]
                                      [--max_dist 0.5] [--thresholds 0.05,0.1,0.2] [--keep_objects] [--sweeps sweeps.npz]
+                                     [--min_component N] [--largest K]
     python -m durf_amd.eval_geometry --synthetic --eval_dir OUT [--source ...]
 
 Truth: the union over the split's frames of geometry.depth_points of the frame's LIDAR depth plane (eval_set()['depth']: its
 positive pixels).  Points inside any box at their frame's timestep are dropped unless --keep_objects is given: the background
 mesh is static.  Prediction (--source): `mesh` (default) extract_mesh's background mesh (--grid, --iso, --sigma: every box
-disabled) sampled with --samples area-uniform points; `frames` the rendered distance maps of the same cameras, back-projected
+disabled; --min_component, --largest: without its floaters, as extract_mesh) sampled with --samples area-uniform points; `frames` the rendered distance maps of the same cameras, back-projected
 at the truth's pixels; `lidar` the returns of rendered sweeps (--sweeps and the sensor arguments of render_lidar; the boxes are
 switched off unless --keep_objects).  Written: OUT/geometry.json (everything geometry.cloud_distance returns, the grids, the
 source and the point counts), OUT/accuracy.ply (the prediction coloured by its distance to the truth) and OUT/completeness.ply
@@ -44,6 +45,8 @@ def build_parser():
     ap.add_argument('--iso', type=float, default=default_iso(), help='--source mesh: density at which a point is solid')
     ap.add_argument('--ts', type=float, default=0.0, help='--source mesh: timestep of the box poses')
     ap.add_argument('--sigma', type=float, default=0.0, help='--source mesh: standard deviation of the Gaussian at every lattice point')
+    ap.add_argument('--min_component', type=int, default=0, help='--source mesh: drop connected solid regions of fewer lattice points')
+    ap.add_argument('--largest', type=int, default=None, help='--source mesh: keep only this many of the biggest connected solid regions')
     ap.add_argument('--sweeps', default=None, help='--source lidar: npz as for render_lidar')
     ap.add_argument('--beams', type=int, default=None, help='--source lidar: beams (default 64; --synthetic: 16)')
     ap.add_argument('--columns', type=int, default=None, help='--source lidar: azimuth columns (default 2650; --synthetic: 128)')
@@ -154,11 +157,15 @@ def main(argv=None):
     poses = variables['params']['box_centers'].detach().cpu().numpy() if K else None       # [T,K,6]: the one read of the poses
     truth, planes = truth_cloud(es, config, poses, args.keep_objects)
     if args.source == 'mesh':
+        cleaning = args.min_component or args.largest is not None
+        ckw = dict(min_points=args.min_component, largest=args.largest) if cleaning else {}
         bg = mesh.extract(model, variables, origin, shape, step=step, iso=args.iso, colour=None, ts=args.ts, ext=ext if K else None,
-                          box_enable=[0] * K if K else None, sigma=args.sigma, alpha=alpha, chunk=max(args.chunk, 1))
+                          box_enable=[0] * K if K else None, sigma=args.sigma, alpha=alpha, chunk=max(args.chunk, 1), **ckw)
         pred = geometry.sample_mesh(bg, args.samples)[0]
         source = dict(kind='mesh', vertices=int(bg['vertices'].shape[0]), triangles=int(bg['triangles'].shape[0]), iso=args.iso,
                       samples=args.samples, frame=bg['frame'])
+        if cleaning:
+            source.update(min_component=args.min_component, largest=args.largest, **bg['cleaning'])
     elif args.source == 'frames':
         pred = frames_cloud(model, config, variables, es, alpha, args.chunk, planes)
         source = dict(kind='frames', frames=len(es['ts']))

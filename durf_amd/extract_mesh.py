@@ -2,6 +2,7 @@
 
     python -m durf_amd.extract_mesh --gin_file configs/waymo.gin --data_dir DATA --train_dir CKPT --grid "ox,oy,oz;nu,nv,nw;step"
                                     --iso V --ts T --eval_dir OUT [--objects] [--obj_step S] [--pad 0.05] [--colour query|grid|none]
+                                    [--min_component N] [--largest K]
     python -m durf_amd.extract_mesh --synthetic --objects --eval_dir OUT [--grid ...]
 
 --grid: query_field's lattice (the origin of point (0, 0, 0), the point counts along x, y, z and one spacing, in scene units).
@@ -11,7 +12,10 @@ agree.  --ts: the timestep whose box poses hold.  Written: OUT/background.ply (t
 OUT/poses.npy ([T,K,6]: centre and rotation vector of every box at every timestep; object k at time t sits at
 X = c + R^T P) and OUT/mesh.json (counts, frames, iso).  The PLY files are binary little-endian with per-vertex normals and
 colours (durf_amd.mesh.write_ply).  --synthetic meshes train_boxpose.SyntheticTimestepDataset's scene instead (no data
-directory; --synthetic_boxes K boxes, default 3), which exercises the command end to end."""
+directory; --synthetic_boxes K boxes, default 3), which exercises the command end to end.  --min_component N drops the
+connected solid regions of fewer than N lattice points -- floaters -- from every mesh, --largest K all but the K biggest
+(durf_amd.parts); with either, the PLY files carry a per-vertex `component` and mesh.json gains components (the background's
+count before), kept, dropped_points and sizes (the kept ones), as does the record of every object for its own lattice."""
 import argparse
 import json
 import os
@@ -39,6 +43,8 @@ def build_parser():
     ap.add_argument('--pad', type=float, default=0.05, help='--objects: the object lattice reaches ext (1 + pad)')
     ap.add_argument('--colour', choices=('query', 'grid', 'none'), default='query', help='per-vertex colour: the field seen along -normal, '
                     'the grid\'s own colour interpolated, or none')
+    ap.add_argument('--min_component', type=int, default=0, help='drop connected solid regions of fewer lattice points (0: keep all)')
+    ap.add_argument('--largest', type=int, default=None, help='keep only this many of the biggest connected solid regions')
     return ap
 
 
@@ -65,17 +71,19 @@ def main(argv=None):
     K = variables.layout.K
     colour = None if args.colour == 'none' else args.colour
     kw = dict(sigma=args.sigma, alpha=alpha, chunk=max(args.chunk, 1))
+    if args.min_component or args.largest is not None:
+        kw.update(min_points=args.min_component, largest=args.largest)
     os.makedirs(args.eval_dir, exist_ok=True)
     bg = mesh.extract(model, variables, origin, shape, step=step, iso=args.iso, colour=colour, ts=args.ts, ext=ext if K else None,
                       box_enable=[0] * K if K else None, **kw)
     mesh.write_ply(os.path.join(args.eval_dir, 'background.ply'), bg)
-    meta = dict(iso=args.iso, ts=args.ts, sigma=args.sigma, step=step, background=_record(bg), objects=[])
+    meta = dict(iso=args.iso, ts=args.ts, sigma=args.sigma, step=step, background=_record(bg), objects=[], **bg.get('cleaning', {}))
     if args.write_objects:
         obj_step = args.obj_step if args.obj_step is not None else 0.5 * step
         for k in range(K):
             o = mesh.extract_object(model, variables, k, ext, obj_step, args.iso, ts=args.ts, pad=args.pad, colour=colour, **kw)
             mesh.write_ply(os.path.join(args.eval_dir, 'object_%02d.ply' % k), o)
-            meta['objects'].append(dict(_record(o), box=k, step=obj_step, world_frame=o['grid']['frame']))
+            meta['objects'].append(dict(_record(o), box=k, step=obj_step, world_frame=o['grid']['frame'], **o.get('cleaning', {})))
     np.save(os.path.join(args.eval_dir, 'poses.npy'), variables['params']['box_centers'].detach().cpu().numpy())
     with open(os.path.join(args.eval_dir, 'mesh.json'), 'w') as f:
         json.dump(meta, f, indent=1)

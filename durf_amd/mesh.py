@@ -106,11 +106,24 @@ def _colour(m, g, colour, model, variables, kw, entry):
     return m['rgb']
 
 
-def extract(model, variables, origin, shape, step=None, axes=None, iso=None, colour='query', view=(0.0, 0.0, -1.0), **kw):
+def _clean(m, g, iso, min_points, largest):
+    """the opt-in cleaning of extract, extract_object and extract_scene (durf_amd.parts): with the defaults m as it is"""
+    if not min_points and largest is None:
+        return m
+    from . import parts
+    m, m['cleaning'] = parts.clean(m, g, iso, min_points=min_points, largest=largest)
+    return m
+
+
+def extract(model, variables, origin, shape, step=None, axes=None, iso=None, colour='query', view=(0.0, 0.0, -1.0), min_points=0,
+            largest=None, **kw):
     """field.grid over the lattice (its arguments: sigma, ts, alpha, pose, box_enable, chunk, inside_tol, ext), then surface
     -> surface's dict plus owner [V] int32 (the owner of each edge's in end: the box a vertex belongs to, -1 background) and
     rgb [V,3].  colour='query' (default): field.query(vertices, viewdirs=-normals), the colour seen looking straight at the
-    surface; 'grid': the grid's own rgb, seen along `view`, interpolated along each edge; None: no colour."""
+    surface; 'grid': the grid's own rgb, seen along `view`, interpolated along each edge; None: no colour.
+    min_points, largest (opt-in; durf_amd.parts.keep): drop the connected solid regions of the lattice with fewer points, or all
+    but the `largest` biggest, from the mesh -- a compaction: what stays keeps its bits; adds component [V] int32 and `cleaning`
+    (components, kept, dropped_points, sizes).  With the defaults nothing of this runs."""
     from . import field
     iso = _iso(iso, 'mesh.extract')
     if colour not in ('query', 'grid', None):
@@ -119,7 +132,7 @@ def extract(model, variables, origin, shape, step=None, axes=None, iso=None, col
     m = surface(g, iso, normals=True, attrs=('rgb',) if colour == 'grid' else ())
     m['owner'] = _owner(m, g, iso)
     m['rgb'] = _colour(m, g, colour, model, variables, kw, 'mesh.extract')
-    return m
+    return _clean(m, g, iso, min_points, largest)
 
 
 def object_lattice(c, R, ext_k, step, pad):
@@ -139,13 +152,13 @@ def object_lattice(c, R, ext_k, step, pad):
     return obj, world, shape
 
 
-def extract_object(model, variables, k, ext, step, iso, ts=0, pad=0.05, colour='query', pose=None, **kw):
+def extract_object(model, variables, k, ext, step, iso, ts=0, pad=0.05, colour='query', pose=None, min_points=0, largest=None, **kw):
     """Box k as a mesh in the box's own (canonical) frame.  The 24 bytes of its pose are read once; the lattice is built in
     the box's frame (spacing `step`, centred, inside |P_j| <= ext_kj (1 + pad)) and the WORLD field is queried at c_k + R_k^T P;
     the density is set to 0 where the owner is not k, and on the lattice's outermost layer, so the object closes at its faces;
     the surface is then taken in the object frame: vertices and normals are canonical coordinates.  -> extract's dict plus
     `grid` (the world-frame lattice that was meshed: density, valid, owner, frame) and `pose` (c [3], R [3,3] float64).
-    colour='query' asks the world field at the vertices' world positions."""
+    colour='query' asks the world field at the vertices' world positions.  min_points, largest: as for extract."""
     import torch
     from . import field
     iso = _iso(iso, 'mesh.extract_object')
@@ -178,22 +191,24 @@ def extract_object(model, variables, k, ext, step, iso, ts=0, pad=0.05, colour='
         m['rgb'] = field.query(model, variables, X, vd, ts=ts, pose=p, ext=ext, **kw)['rgb']
     elif colour is None:
         m['rgb'] = None
+    m = _clean(m, g, iso, min_points, largest)
     m['grid'], m['pose'] = g, (c, R)
     return m
 
 
 def extract_scene(model, variables, origin, shape, step=None, axes=None, iso=None, ext=None, obj_step=None, ts=0, pad=0.05,
-                  colour='query', **kw):
+                  colour='query', min_points=0, largest=None, **kw):
     """The whole scene as an asset: `background` (extract with every box disabled), `objects` (extract_object of every box,
     each in its own frame, at spacing obj_step) and `poses` [T,K,6] (the boxes' centres and rotation vectors at every timestep,
-    a host array): place object k at time t with X = c + R^T P."""
+    a host array): place object k at time t with X = c + R^T P.  min_points, largest: as for extract, for every mesh."""
     iso = _iso(iso, 'mesh.extract_scene')
     K = variables.layout.K
     if K and (obj_step is None or ext is None):
         raise ValueError('mesh.extract_scene: obj_step and ext are needed for K = %d boxes' % K)
     bg = extract(model, variables, origin, shape, step=step, axes=axes, iso=iso, colour=colour, ts=ts, ext=ext,
-                 box_enable=[0] * K if K else None, **kw)
-    objs = [extract_object(model, variables, k, ext, obj_step, iso, ts=ts, pad=pad, colour=colour, **kw) for k in range(K)]
+                 box_enable=[0] * K if K else None, min_points=min_points, largest=largest, **kw)
+    objs = [extract_object(model, variables, k, ext, obj_step, iso, ts=ts, pad=pad, colour=colour, min_points=min_points, largest=largest, **kw)
+            for k in range(K)]
     poses = variables['params']['box_centers'].detach().cpu().numpy()
     return dict(background=bg, objects=objs, poses=poses)
 
@@ -201,6 +216,7 @@ def extract_scene(model, variables, origin, shape, step=None, axes=None, iso=Non
 # ---- PLY ------------------------------------------------------------------------------------------------------------------------
 _VERTEX = np.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4'), ('red', 'u1'),
                     ('green', 'u1'), ('blue', 'u1')])
+_VERTEX_COMPONENT = np.dtype(_VERTEX.descr + [('component', '<i4')])
 _FACE = np.dtype([('n', 'u1'), ('v', '<i4', (3,))])
 
 
@@ -210,9 +226,13 @@ def _host(a):
 
 def write_ply(path, m):
     """m: dict vertices [V,3], triangles [T,3], normals [V,3] or None (zeros), rgb [V,3] or None (grey; float in [0, 1] or
-    uint8) -> binary little-endian PLY: vertices x y z nx ny nz (float) red green blue (uchar), faces as uchar-int lists"""
+    uint8) -> binary little-endian PLY: vertices x y z nx ny nz (float) red green blue (uchar), faces as uchar-int lists.
+    A dict with the key `component` [V] (durf_amd.parts.select's) gets one more vertex property, component (int), and only then."""
     X, tri = _host(m['vertices']).astype('<f4').reshape(-1, 3), _host(m['triangles']).astype('<i4').reshape(-1, 3)
-    V = np.zeros(X.shape[0], _VERTEX)
+    with_component = m.get('component') is not None
+    V = np.zeros(X.shape[0], _VERTEX_COMPONENT if with_component else _VERTEX)
+    if with_component:
+        V['component'] = _host(m['component']).astype('<i4').reshape(-1)
     for c, name in enumerate('xyz'):
         V[name] = X[:, c]
     if m.get('normals') is not None:
@@ -231,7 +251,7 @@ def write_ply(path, m):
     F['n'], F['v'] = 3, tri
     head = ('ply\nformat binary_little_endian 1.0\ncomment durf_amd.mesh\nelement vertex %d\n' % X.shape[0] +
             ''.join('property float %s\n' % n for n in ('x', 'y', 'z', 'nx', 'ny', 'nz')) +
-            ''.join('property uchar %s\n' % n for n in ('red', 'green', 'blue')) +
+            ''.join('property uchar %s\n' % n for n in ('red', 'green', 'blue')) + ('property int component\n' if with_component else '') +
             'element face %d\nproperty list uchar int vertex_indices\nend_header\n' % tri.shape[0])
     with open(path, 'wb') as f:
         f.write(head.encode('ascii'))
@@ -240,7 +260,8 @@ def write_ply(path, m):
 
 
 def read_ply(path):
-    """what write_ply wrote -> dict vertices [V,3] float32, normals [V,3] float32, rgb [V,3] uint8, triangles [T,3] int32"""
+    """what write_ply wrote -> dict vertices [V,3] float32, normals [V,3] float32, rgb [V,3] uint8, triangles [T,3] int32, and
+    component [V] int32 when the file has that property"""
     blob = open(path, 'rb').read()
     end = blob.index(b'end_header\n') + len(b'end_header\n')
     lines = blob[:end].decode('ascii').split('\n')
@@ -249,13 +270,17 @@ def read_ply(path):
     nv = int([l for l in lines if l.startswith('element vertex')][0].split()[-1])
     nf = int([l for l in lines if l.startswith('element face')][0].split()[-1])
     props = [l.split()[-1] for l in lines if l.startswith('property') and ' list ' not in l]
-    if props != list(_VERTEX.names):
+    vertex = _VERTEX_COMPONENT if props == list(_VERTEX_COMPONENT.names) else _VERTEX
+    if props != list(vertex.names):
         raise ValueError('read_ply: vertex properties %s, expected %s (write_ply\'s)' % (props, list(_VERTEX.names)))
-    if len(blob) != end + nv * _VERTEX.itemsize + nf * _FACE.itemsize:
-        raise ValueError('read_ply: %s holds %d bytes, its header promises %d' % (path, len(blob), end + nv * _VERTEX.itemsize + nf * _FACE.itemsize))
-    V = np.frombuffer(blob, _VERTEX, nv, end)
-    F = np.frombuffer(blob, _FACE, nf, end + nv * _VERTEX.itemsize)
+    if len(blob) != end + nv * vertex.itemsize + nf * _FACE.itemsize:
+        raise ValueError('read_ply: %s holds %d bytes, its header promises %d' % (path, len(blob), end + nv * vertex.itemsize + nf * _FACE.itemsize))
+    V = np.frombuffer(blob, vertex, nv, end)
+    F = np.frombuffer(blob, _FACE, nf, end + nv * vertex.itemsize)
     if nf and not (F['n'] == 3).all():
         raise ValueError('read_ply: a face that is no triangle')
-    return dict(vertices=np.stack([V['x'], V['y'], V['z']], 1), normals=np.stack([V['nx'], V['ny'], V['nz']], 1),
-                rgb=np.stack([V['red'], V['green'], V['blue']], 1), triangles=np.array(F['v'], np.int32).reshape(-1, 3))
+    out = dict(vertices=np.stack([V['x'], V['y'], V['z']], 1), normals=np.stack([V['nx'], V['ny'], V['nz']], 1),
+               rgb=np.stack([V['red'], V['green'], V['blue']], 1), triangles=np.array(F['v'], np.int32).reshape(-1, 3))
+    if vertex is _VERTEX_COMPONENT:
+        out['component'] = np.array(V['component'], np.int32)
+    return out

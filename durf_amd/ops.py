@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import _lib
-from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs
+from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs, _parts_sigs
 
 
 
@@ -20,9 +20,9 @@ def _by_prefix(table, prefix):
 
 # The headers are the one place a constant or an argument struct is written (tools/gen_integration_stub.py renders them into
 # the tables imported above; tests/test_headers_host.py holds the tables to the C compiler).  Every `#define DURF_X <integer>`
-# of include/durf_hip.h and include/durf_<name>.h is ops.X: ENC_DIM, MAX_OBJ, TRAIN_OBJ_FP32, TIMED_STAGES, MESH_BLOCK, ...
+# of include/durf_hip.h and include/durf_<name>.h is ops.X: ENC_DIM, MAX_OBJ, TRAIN_OBJ_FP32, TIMED_STAGES, MESH_BLOCK, PARTS_TILE_K, ...
 # -- all but OVERLAP_MIN_ROWS, launch policy that the library is asked for (__getattr__ below).
-for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs):
+for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs, _parts_sigs):
     globals().update(_by_prefix(_table, 'DURF_'))
 del OVERLAP_MIN_ROWS
 
@@ -2287,6 +2287,82 @@ def mesh_gather(shape, counts, vertex_edge, vertex_t, attr_f=None, attr_i=None, 
             _stream(), nu, nv, nw, _p(counts), V, _p(vertex_edge), _p(_f32(vertex_t)), Cn, _p(attr_f), _p(out_f), _p(attr_i),
             _p(None if density is None else _f32(density)), _p(valid), float(iso), _p(out_i)), 'durf_mesh_gather')
     return out_f, out_i
+
+
+# ---------------------------------------------------------------------------
+# connected components of a density lattice (include/durf_parts.h, csrc/parts.hip, libdurf_parts.so)
+# ---------------------------------------------------------------------------
+def parts_workspace_bytes(shape):
+    nu, nv, nw = (int(s) for s in shape)
+    return int(_lib.parts_lib().durf_parts_workspace_bytes(nu, nv, nw))
+
+
+def _parts_ws(ws, need, dev):
+    return torch.empty(max(need, 256), dtype=torch.uint8, device=dev) if ws is None else ws
+
+
+def _i32(t, n, what):
+    assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == n, (what, t.dtype, tuple(t.shape), n)
+    return t
+
+
+def parts_label(density, valid, shape, iso, ws=None, labels=None):
+    """durf_parts_label: the label of every lattice point (the smallest index of its component, -1 where it is not in) ->
+    (labels int32 [n], the workspace).  Three launches, no read-back."""
+    nu, nv, nw = _mesh_lattice(density, valid, shape)
+    n, dev = nu * nv * nw, density.device
+    L = _lib.parts_lib()
+    ws = _parts_ws(ws, int(L.durf_parts_workspace_bytes(nu, nv, nw)), dev)
+    labels = torch.empty(n, dtype=torch.int32, device=dev) if labels is None else _i32(labels, n, 'labels')
+    with _Timed('parts_label'):
+        _lib.check(L.durf_parts_label(_stream(), nu, nv, nw, _p(_f32(density)), _p(valid), float(iso), _p(ws), ws.numel(), _p(labels)),
+                   'durf_parts_label')
+    return labels, ws
+
+
+def parts_number(labels, ws=None):
+    """durf_parts_number -> (comp int32 [n]: the number of every point's component, -1 where it has none; count int32 [1] ON
+    THE DEVICE).  No read-back."""
+    n, dev = int(labels.numel()), labels.device
+    _i32(labels, n, 'labels')
+    up = lambda b: (b + 255) // 256 * 256
+    ws = _parts_ws(ws, up(4 * n) + up(4 * ((n + PARTS_BLOCK - 1) // PARTS_BLOCK + 1)), dev)
+    comp, count = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+    with _Timed('parts_number'):
+        _lib.check(_lib.parts_lib().durf_parts_number(_stream(), n, _p(labels), _p(ws), ws.numel(), _p(comp), _p(count)), 'durf_parts_number')
+    return comp, count
+
+
+def parts_stats(comp, shape, max_components, size=None, bbox=None):
+    """durf_parts_stats -> (size int32 [max_components], bbox int32 [max_components,6]: imin, jmin, kmin, imax, jmax, kmax)"""
+    nu, nv, nw = (int(s) for s in shape)
+    mc, dev = int(max_components), comp.device
+    _i32(comp, nu * nv * nw, 'comp')
+    size = torch.empty(max(mc, 0), dtype=torch.int32, device=dev) if size is None else size
+    bbox = torch.empty(max(mc, 0), 6, dtype=torch.int32, device=dev) if bbox is None else bbox
+    with _Timed('parts_stats'):
+        _lib.check(_lib.parts_lib().durf_parts_stats(_stream(), nu, nv, nw, _p(comp), mc, _p(size) if mc > 0 else None,
+                                                     _p(bbox) if mc > 0 else None), 'durf_parts_stats')
+    return size, bbox
+
+
+def parts_select_mesh(counts, vertex_comp, triangles, keep, ws=None):
+    """durf_parts_select_mesh: the vertices whose component is kept and the triangles that hang on them, in their order ->
+    (vertex_map int32 [V], vertex_src int32 [V], triangles_out int32 [T,3], counts_out int32 [2] ON THE DEVICE).  Four
+    launches, no read-back."""
+    V, T, dev = int(vertex_comp.shape[0]), int(triangles.shape[0]), counts.device
+    _i32(counts, 2, 'counts'), _i32(vertex_comp, V, 'vertex_comp'), _i32(triangles, 3 * T, 'triangles')
+    nc = int(keep.numel())
+    assert keep.dtype == torch.uint8 and keep.is_contiguous() and keep.is_cuda
+    ws = _parts_ws(ws, (8 * ((max(V, T) + PARTS_BLOCK - 1) // PARTS_BLOCK + 1) + 255) // 256 * 256, dev)
+    vmap, vsrc = torch.empty(V, dtype=torch.int32, device=dev), torch.empty(V, dtype=torch.int32, device=dev)
+    tri, out = torch.empty(T, 3, dtype=torch.int32, device=dev), torch.empty(2, dtype=torch.int32, device=dev)
+    z = lambda t, k: _p(t) if k else None                                # (a zero-row tensor has no address to hand over)
+    with _Timed('parts_select_mesh'):
+        _lib.check(_lib.parts_lib().durf_parts_select_mesh(_stream(), _p(counts), V, T, z(vertex_comp, V), z(triangles, T), z(keep, nc), nc,
+                                                           _p(ws), ws.numel(), z(vmap, V), z(vsrc, V), z(tri, T), _p(out)),
+                   'durf_parts_select_mesh')
+    return vmap, vsrc, tri, out
 
 
 # ---------------------------------------------------------------------------
