@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import _lib
-from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs, _parts_sigs
+from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs, _parts_sigs, _raster_sigs
 
 
 
@@ -22,7 +22,7 @@ def _by_prefix(table, prefix):
 # the tables imported above; tests/test_headers_host.py holds the tables to the C compiler).  Every `#define DURF_X <integer>`
 # of include/durf_hip.h and include/durf_<name>.h is ops.X: ENC_DIM, MAX_OBJ, TRAIN_OBJ_FP32, TIMED_STAGES, MESH_BLOCK, PARTS_TILE_K, ...
 # -- all but OVERLAP_MIN_ROWS, launch policy that the library is asked for (__getattr__ below).
-for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs, _parts_sigs):
+for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs, _parts_sigs, _raster_sigs):
     globals().update(_by_prefix(_table, 'DURF_'))
 del OVERLAP_MIN_ROWS
 
@@ -2363,6 +2363,110 @@ def parts_select_mesh(counts, vertex_comp, triangles, keep, ws=None):
                                                            _p(ws), ws.numel(), z(vmap, V), z(vsrc, V), z(tri, T), _p(out)),
                    'durf_parts_select_mesh')
     return vmap, vsrc, tri, out
+
+
+# ---------------------------------------------------------------------------
+# a triangle mesh through pinhole cameras (include/durf_raster.h, csrc/raster.hip, libdurf_raster.so)
+# ---------------------------------------------------------------------------
+from .raster import COUNT_FIELDS as RASTER_COUNT_FIELDS        # noqa: E402  (written once, in the host-side module, which imports no torch)
+assert len(RASTER_COUNT_FIELDS) == RASTER_COUNTS
+
+
+def raster_workspace_bytes(F, T, h, w):
+    return int(_lib.raster_lib().durf_raster_workspace_bytes(int(F), int(T), int(h), int(w)))
+
+
+def _raster_mesh(cams, vertices, triangles):
+    assert cams.dtype == torch.float32 and cams.is_cuda and cams.is_contiguous() and cams.dim() == 2 and cams.shape[1] == 17, tuple(cams.shape)
+    V, T = int(vertices.shape[0]), int(triangles.shape[0])
+    assert vertices.numel() == 3 * V and triangles.dtype == torch.int32 and triangles.is_cuda and triangles.is_contiguous() and triangles.numel() == 3 * T
+    _f32(vertices)
+    return int(cams.shape[0]), V, T
+
+
+def _raster_ws(ws, F, T, h, w, dev):
+    need = raster_workspace_bytes(F, T, h, w)
+    return torch.empty(max(need, 256), dtype=torch.uint8, device=dev) if ws is None else ws
+
+
+def _z(t):
+    """a tensor's address, or None for no tensor and for one of zero elements (it has no address to hand over)"""
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+def raster_setup(cams, h, w, vertices, triangles, znear, cull=0, ws=None):
+    """durf_raster_setup: project, cull, snap and count per tile, scan -> (counts int32 [RASTER_COUNTS] ON THE DEVICE:
+    RASTER_COUNT_FIELDS; the workspace, a uint8 tensor raster_draw reads).  No read-back."""
+    F, V, T = _raster_mesh(cams, vertices, triangles)
+    dev = cams.device
+    ws = _raster_ws(ws, F, T, h, w, dev)
+    counts = torch.empty(RASTER_COUNTS, dtype=torch.int32, device=dev)
+    with _Timed('raster_setup'):
+        _lib.check(_lib.raster_lib().durf_raster_setup(_stream(), F, int(h), int(w), _z(cams), V, T, _z(vertices), _z(triangles), float(znear),
+                                                       int(cull), _p(ws), ws.numel(), _p(counts)), 'durf_raster_setup')
+    return counts, ws
+
+
+def raster_draw(F, T, h, w, ws, max_pairs, pairs=None, want_bary=True):
+    """durf_raster_draw on the workspace of raster_setup -> (tri int32 [F,h,w], depth [F,h,w], bary [F,h,w,3] or None).  A
+    max_pairs below counts[0] gives tri = -2 and depth = NaN everywhere.  pairs: scratch of at least max_pairs int32 to reuse."""
+    dev, mp = ws.device, int(max_pairs)
+    if pairs is None:
+        pairs = torch.empty(max(mp, 0), dtype=torch.int32, device=dev)
+    assert pairs.dtype == torch.int32 and pairs.is_contiguous() and pairs.numel() >= mp
+    tri = torch.empty(F, h, w, dtype=torch.int32, device=dev)
+    depth = torch.empty(F, h, w, device=dev)
+    bary = torch.empty(F, h, w, 3, device=dev) if want_bary else None
+    with _Timed('raster_draw'):
+        _lib.check(_lib.raster_lib().durf_raster_draw(_stream(), int(F), int(T), int(h), int(w), _p(ws), ws.numel(), _z(pairs), mp, _z(tri),
+                                                      _z(depth), _z(bary)), 'durf_raster_draw')
+    return tri, depth, bary
+
+
+def _raster_attrs(V, attr_f, attr_i):
+    Cn = 1
+    if attr_f is not None:
+        attr_f = _f32(attr_f).reshape(V, -1)
+        Cn = int(attr_f.shape[1])
+    if attr_i is not None:
+        _i32(attr_i, V, 'attr_i')
+    return Cn, attr_f, attr_i
+
+
+def raster_interp(triangles, tri, bary, n_vertices, attr_f=None, attr_i=None, fill=-1):
+    """durf_raster_interp: vertex attributes at the pixels -> (out_f [..., C] = (q0 a0 + q1 a1) + q2 a2 or None, out_i [...]
+    int32 = attr_i of the triangle's first vertex or None); 0 and `fill` where nothing covers"""
+    V, T, dev = int(n_vertices), int(triangles.shape[0]), tri.device
+    n = int(tri.numel())
+    _i32(tri, n, 'tri')
+    Cn, attr_f, attr_i = _raster_attrs(V, attr_f, attr_i)
+    out_f = torch.empty(tuple(tri.shape) + (Cn,), device=dev) if attr_f is not None else None
+    out_i = torch.empty(tuple(tri.shape), dtype=torch.int32, device=dev) if attr_i is not None else None
+    with _Timed('raster_interp'):
+        _lib.check(_lib.raster_lib().durf_raster_interp(_stream(), n, V, T, _z(triangles), _z(tri), _z(bary), Cn, _p(attr_f), _p(out_f), _p(attr_i),
+                                                        int(fill), _p(out_i)), 'durf_raster_interp')
+    return out_f, out_i
+
+
+def raster_render_mesh(cams, h, w, vertices, triangles, znear, max_pairs, cull=0, attr_f=None, attr_i=None, fill=-1, ws=None, pairs=None):
+    """durf_render_mesh: setup, draw and (with an attribute) interp in one call, for a pair capacity the caller chose -> dict
+    counts (ON THE DEVICE), tri, depth, bary, out_f, out_i.  counts[0] > max_pairs: the -2 / NaN picture."""
+    F, V, T = _raster_mesh(cams, vertices, triangles)
+    dev, mp = cams.device, int(max_pairs)
+    ws = _raster_ws(ws, F, T, h, w, dev)
+    if pairs is None:
+        pairs = torch.empty(max(mp, 0), dtype=torch.int32, device=dev)
+    Cn, attr_f, attr_i = _raster_attrs(V, attr_f, attr_i)
+    o = dict(counts=torch.empty(RASTER_COUNTS, dtype=torch.int32, device=dev), tri=torch.empty(F, h, w, dtype=torch.int32, device=dev),
+             depth=torch.empty(F, h, w, device=dev), bary=torch.empty(F, h, w, 3, device=dev),
+             out_f=torch.empty(F, h, w, Cn, device=dev) if attr_f is not None else None,
+             out_i=torch.empty(F, h, w, dtype=torch.int32, device=dev) if attr_i is not None else None)
+    with _Timed('render_mesh'):
+        _lib.check(_lib.raster_lib().durf_render_mesh(
+            _stream(), F, int(h), int(w), _z(cams), V, T, _z(vertices), _z(triangles), float(znear), int(cull), _p(ws), ws.numel(), _z(pairs), mp,
+            _p(o['counts']), _z(o['tri']), _z(o['depth']), _z(o['bary']), Cn, _p(attr_f), _p(o['out_f']), _p(attr_i), int(fill), _p(o['out_i'])),
+            'durf_render_mesh')
+    return o
 
 
 # ---------------------------------------------------------------------------
