@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import _lib
-from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs, _parts_sigs, _raster_sigs
+from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs
 
 
 
@@ -22,7 +22,7 @@ def _by_prefix(table, prefix):
 # the tables imported above; tests/test_headers_host.py holds the tables to the C compiler).  Every `#define DURF_X <integer>`
 # of include/durf_hip.h and include/durf_<name>.h is ops.X: ENC_DIM, MAX_OBJ, TRAIN_OBJ_FP32, TIMED_STAGES, MESH_BLOCK, PARTS_TILE_K, ...
 # -- all but OVERLAP_MIN_ROWS, launch policy that the library is asked for (__getattr__ below).
-for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs, _parts_sigs, _raster_sigs):
+for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs):
     globals().update(_by_prefix(_table, 'DURF_'))
 del OVERLAP_MIN_ROWS
 
@@ -2547,3 +2547,63 @@ def geom_sample_mesh(vertices, triangles, n, ws=None):
         _lib.check(L.durf_geom_sample_mesh(_stream(), V, _p(vertices) if V else None, T, _p(triangles) if T else None, n, _p(ws), ws.numel(),
                                            _p(points) if n > 0 else None, _p(tri) if n > 0 else None, _p(total)), 'durf_geom_sample_mesh')
     return points, tri, total
+
+
+# ---------------------------------------------------------------------------
+# depth frames fused into a TSDF volume (include/durf_tsdf.h, csrc/tsdf.hip, libdurf_tsdf.so)
+# ---------------------------------------------------------------------------
+def _tsdf_state(tsdf, weight, colour, shape):
+    nu, nv, nw = (int(s) for s in shape)
+    n = nu * nv * nw
+    assert _f32(tsdf).numel() == n and _f32(weight).numel() == n, (tuple(tsdf.shape), tuple(weight.shape), shape)
+    assert colour is None or _f32(colour).numel() == 4 * n, (tuple(colour.shape), shape)
+    return nu, nv, nw, n
+
+
+def tsdf_integrate(tsdf, weight, colour, shape, origin, du, dv, dw, cams, depth, trunc, acc=None, min_acc=0.5, rgb=None, label=None,
+                   select=0, other_mode=0, xform=None, frame_weight=None, max_weight=64.0, znear=1e-2):
+    """durf_tsdf_integrate: the F frames depth [F,h,w] (cams [F,17] on the device) into the state tsdf, weight [n] and colour
+    [n,4] (or None), IN PLACE, one launch.  acc [F,h,w], rgb [F,h,w,3], label int32 [F,h,w], xform [F,3,4], frame_weight [F]:
+    on the device, or None."""
+    nu, nv, nw, n = _tsdf_state(tsdf, weight, colour, shape)
+    assert _f32(depth).dim() == 3, tuple(depth.shape)
+    F, h, w = (int(s) for s in depth.shape)
+    assert _f32(cams).numel() == 17 * F, (tuple(cams.shape), F)
+    assert acc is None or _f32(acc).numel() == F * h * w
+    assert rgb is None or _f32(rgb).numel() == 3 * F * h * w
+    assert label is None or _i32(label, F * h * w, 'label') is label
+    assert xform is None or _f32(xform).numel() == 12 * F
+    assert frame_weight is None or _f32(frame_weight).numel() == F
+    with _Timed('tsdf_integrate'):
+        _lib.check(_lib.tsdf_lib().durf_tsdf_integrate(
+            _stream(), nu, nv, nw, _host_floats(origin, 3, 'origin'), _host_floats(du, 3, 'du'), _host_floats(dv, 3, 'dv'),
+            _host_floats(dw, 3, 'dw'), F, h, w, _z(cams), _z(depth), _z(acc), float(min_acc), _z(rgb), _z(label), int(select), int(other_mode),
+            _z(xform), _z(frame_weight), float(trunc), float(max_weight), float(znear), _p(tsdf), _p(weight), _p(colour)), 'durf_tsdf_integrate')
+
+
+def tsdf_lattice(tsdf, weight, colour, shape, min_weight=1.0, want_rgb=True):
+    """durf_tsdf_lattice -> (density [nu,nv,nw] = -D, valid uint8 [nu,nv,nw] = (W >= min_weight), rgb [nu,nv,nw,3] or None: the
+    colour where its weight is positive, else 0): what mesh_count and parts_label take"""
+    nu, nv, nw, n = _tsdf_state(tsdf, weight, colour, shape)
+    dev = tsdf.device
+    density, valid = torch.empty(nu, nv, nw, device=dev), torch.empty(nu, nv, nw, dtype=torch.uint8, device=dev)
+    rgb = torch.empty(nu, nv, nw, 3, device=dev) if want_rgb and colour is not None else None
+    with _Timed('tsdf_lattice'):
+        _lib.check(_lib.tsdf_lib().durf_tsdf_lattice(_stream(), nu, nv, nw, _p(tsdf), _p(weight), _p(colour), float(min_weight), _p(density),
+                                                     _p(valid), _p(rgb)), 'durf_tsdf_lattice')
+    return density, valid, rgb
+
+
+def tsdf_sample(tsdf, weight, colour, shape, origin, inv, trunc, points, min_weight=1.0, want_rgb=True):
+    """durf_tsdf_sample: points [m,3] -> (sdf [m]: trilinear D times trunc, NaN outside or beside an unobserved voxel; ok uint8
+    [m]; rgb [m,3] or None).  inv: the inverse of [du dv dw], nine host floats."""
+    nu, nv, nw, n = _tsdf_state(tsdf, weight, colour, shape)
+    m, dev = int(_geom_points(points, 'points').shape[0]), tsdf.device
+    _f32(points)
+    sdf, ok = torch.empty(m, device=dev), torch.empty(m, dtype=torch.uint8, device=dev)
+    rgb = torch.empty(m, 3, device=dev) if want_rgb and colour is not None else None
+    with _Timed('tsdf_sample'):
+        _lib.check(_lib.tsdf_lib().durf_tsdf_sample(_stream(), nu, nv, nw, _host_floats(origin, 3, 'origin'), _host_floats(inv, 9, 'inv'),
+                                                    _p(tsdf), _p(weight), _p(colour), float(trunc), float(min_weight), m, _z(points), _z(sdf),
+                                                    _z(ok), _z(rgb)), 'durf_tsdf_sample')
+    return sdf, ok, rgb

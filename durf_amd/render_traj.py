@@ -61,8 +61,9 @@ def build_parser():
     return ap
 
 
-def open_scene(args, split='test'):
-    """-> device, config and the `split` dataset the scene arguments name (the synthetic scene with --synthetic)"""
+def open_scene(args, split='test', boxes=None):
+    """-> device, config and the `split` dataset the scene arguments name (the synthetic scene with --synthetic; boxes: its count
+    of dynamic boxes, for a command whose --objects means something else; None: args.objects)"""
     import torch
     from . import train_boxpose, utils
     dev = torch.device('cuda', 0)
@@ -71,7 +72,7 @@ def open_scene(args, split='test'):
     config = utils.load_config(args.gin_file, args.gin_param)
     if args.synthetic:
         size = dict(hw=tuple(args.synthetic_size)) if getattr(args, 'synthetic_size', None) else {}
-        dataset = train_boxpose.SyntheticTimestepDataset(config, K=args.objects, device=dev, split=split, **size)
+        dataset = train_boxpose.SyntheticTimestepDataset(config, K=args.objects if boxes is None else int(boxes), device=dev, split=split, **size)
     else:
         from . import datasets
         dataset = datasets.get_dataset(split, args.data_dir, config, device=dev)

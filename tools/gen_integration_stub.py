@@ -36,7 +36,7 @@ def ctype_of(param):
     if stars == 0:
         return SCALARS[base], name
     if stars == 1 and base == 'float' and name in ('barf_w', 'mults', 'cams_host', 'times_host', 'sensor_host', 'sweeps_host',
-                                                     'to_sensor_host', 'cam_a_host', 'cam_b_host', 'origin_host', 'du_host', 'dv_host', 'dw_host', 'normal_xform_host', 'thresholds_host'):
+                                                     'to_sensor_host', 'cam_a_host', 'cam_b_host', 'origin_host', 'du_host', 'dv_host', 'dw_host', 'normal_xform_host', 'thresholds_host', 'inv_host'):
         return 'C.POINTER(f32)', name          # HOST float arrays (documented as such in the header)
     if stars == 1 and base == 'size_t':
         return 'C.POINTER(u64)', name          # HOST array (per-segment row capacities)
