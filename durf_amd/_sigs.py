@@ -236,6 +236,12 @@ class durf_forward_args(C.Structure):
     ]
 
 
+DURF_CAM_FLOATS = 17
+DURF_CAM_FOCAL = 12
+DURF_CAM_PPX = 13
+DURF_CAM_PPY = 14
+DURF_CAM_H = 15
+DURF_CAM_W = 16
 DURF_TRAIN_OBJ_FP32 = 1
 DURF_TRAIN_POSE_OPT = 2
 DURF_TRAIN_OBJ_X3 = 4

@@ -1,5 +1,5 @@
-// The frame of a box pose and the camera frame, shared by the box overlay (overlay.hip), the flow library (flow.hip) and the field
-// library (field.hip) so that all place a box and a camera with the same bits.  Internal.
+// The frame of a box pose, shared by the box overlay (overlay.hip), the flow library (flow.hip) and the field library (field.hip)
+// so that all place a box with the same bits.  Internal.
 #pragma once
 
 #define DURF_POSE_ROW 12            // one box of a pose table: R row-major, then the centre
@@ -42,11 +42,4 @@ __device__ __forceinline__ void pose_to_box(const float* row, float X0, float X1
 __device__ __forceinline__ void pose_to_world(const float* row, float P0, float P1, float P2, float* X) {
 #pragma unroll
     for (int j = 0; j < 3; j++) X[j] = row[9 + j] + ((row[j] * P0 + row[3 + j] * P1) + row[6 + j] * P2);
-}
-
-// camera space of a world point: pc = R_c^T (P - o), R_c[a][j] = cam[4 a + j], o[a] = cam[4 a + 3]
-__device__ __forceinline__ void overlay_to_camera(const float* cam, const float* P, float* pc) {
-    const float d0 = P[0] - cam[3], d1 = P[1] - cam[7], d2 = P[2] - cam[11];
-#pragma unroll
-    for (int j = 0; j < 3; j++) pc[j] = (cam[j] * d0 + cam[4 + j] * d1) + cam[8 + j] * d2;
 }

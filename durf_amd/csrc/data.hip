@@ -2,9 +2,9 @@
 // the SSIM evaluation metric (internal/math.py:66-137): the callers / data formats either side of the
 // hot path.  HBM-bound gathers and small stencils; fp32 like the reference.
 #include "durf_common.h"
-#include "pinhole.h"
+#include "camera.h"
 
-struct CamTable { float v[DURF_MAX_CAMS][17]; int first[DURF_MAX_CAMS + 1]; int n; };
+struct CamTable { CamRow v[DURF_MAX_CAMS]; int first[DURF_MAX_CAMS + 1]; int n; };
 
 // one thread per ray: flat index into the timestep's concatenated cameras -> (camera, x, y)
 __global__ void __launch_bounds__(256)
@@ -19,8 +19,8 @@ k_gen_batch(int B, CamTable cams, const int32_t* __restrict__ ray_idx, float nea
     const int r = ray_idx ? ray_idx[i] : i;
     int c = 0;
     for (int k = 1; k < cams.n; k++) c += (r >= cams.first[k]) ? 1 : 0;
-    const float* cam = cams.v[c];
-    pinhole_ray(cam, r - cams.first[c], near, far, i, origins, dirs, viewdirs, radii, near_o, far_o);      // csrc/pinhole.h
+    const float* cam = cams.v[c].v;
+    pinhole_ray(cam, r - cams.first[c], near, far, i, origins, dirs, viewdirs, radii, near_o, far_o);      // csrc/camera.h
     lossmult[i] = 1.0f;
     if (pixels) for (int a = 0; a < img_channels; a++) pixels[(size_t)i * img_channels + a] = images[(size_t)r * img_channels + a];
     if (depth_o) depth_o[i] = depth[r];
@@ -92,10 +92,11 @@ int durf_gen_batch(void* stream, int B, int n_cams, const float* cams_host, cons
     t.n = n_cams;
     int first = 0;
     for (int c = 0; c < n_cams; c++) {
-        for (int j = 0; j < 17; j++) t.v[c][j] = cams_host[c * 17 + j];
-        DURF_REQUIRE(t.v[c][15] >= 2 && t.v[c][16] >= 1, "camera height >= 2, width >= 1");
+        t.v[c] = cam_row(cams_host + c * DURF_CAM_FLOATS);
+        const float* cam = t.v[c].v;
+        DURF_REQUIRE(cam[DURF_CAM_H] >= 2 && cam[DURF_CAM_W] >= 1, "camera height >= 2, width >= 1");
         t.first[c] = first;
-        first += (int)t.v[c][15] * (int)t.v[c][16];
+        first += (int)cam[DURF_CAM_H] * (int)cam[DURF_CAM_W];
     }
     t.first[n_cams] = first;
     hipLaunchKernelGGL(k_gen_batch, dim3(durf_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, B, t, ray_idx, near, far,

@@ -291,7 +291,7 @@ int launch_layer_gather(void* stream, int count, const int32_t* idx, const float
 int launch_layer_scatter(void* stream, int count, const int32_t* idx, const float* rgb, const float* dist, const float* acc,
                          float* bg_rgb, float* bg_dist, float* bg_acc);
 // a camera trajectory (csrc/trajectory.hip): the launches of durf_render_trajectory / durf_camera_rays (csrc/forward.hip)
-int launch_camera_rays(void* stream, const float* cam17_host, int first, int count, float near, float far, float* const* rays);
+int launch_camera_rays(void* stream, const float* cam_host, int first, int count, float near, float far, float* const* rays);
 int launch_pose_interp(void* stream, int F, int K, const float* times_host, const float* box_centers, float* poses);
 int launch_frame_pack(void* stream, int count, const float* rgb, uint8_t* rgb8);
 }  // namespace durf

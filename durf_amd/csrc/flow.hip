@@ -6,13 +6,14 @@
 // states; nothing here synchronises or copies to the host.
 #include "workspace.h"
 #include "aa2matrix.h"
+#include "camera.h"
 #include "../../include/durf_flow.h"
 
 #define FLOW_THREADS 256
 
 // ---- where a pixel goes -----------------------------------------------------------------------------------------------------
 struct FlowCams {
-    float a[17], b[17];
+    CamRow a, b;
 };
 
 struct FlowOut {
@@ -27,16 +28,6 @@ k_flow_poses(int K, const float* __restrict__ pose_a, const float* __restrict__ 
     if (j >= 2 * K) return;
     const int s = j / K, k = j - s * K;
     pose_row_fill((s ? pose_b : pose_a) + k * 6, table + j * DURF_POSE_ROW);        // j < 2 K: inside DURF_FLOW_POSE_FLOATS(K)
-}
-
-// picture-space position and depth of a world point in a camera (the overlay's convention)
-__device__ __forceinline__ void flow_project(const float* cam, float X0, float X1, float X2, float& xp, float& yp, float& z) {
-    const float X[3] = {X0, X1, X2};
-    float p[3];
-    overlay_to_camera(cam, X, p);
-    z = -p[2];
-    xp = cam[13] + (cam[12] * p[0]) / z;
-    yp = cam[14] - (cam[12] * p[1]) / z;
 }
 
 // one thread per pixel: consecutive lanes read and write consecutive pixels.  The box loop runs over k, the same in every lane,
@@ -78,9 +69,13 @@ k_flow_points(int n, int first, int w, int K, const float* __restrict__ origins_
     if (!live) return;
     const int p = first + i;                         // < h w < 2^31 (checked by the caller)
     const int y = p / w, x = p - y * w;
-    float xa, ya, za, xb, yb, zb;
-    flow_project(cams.a, Xa[0], Xa[1], Xa[2], xa, ya, za);
-    flow_project(cams.b, Xb[0], Xb[1], Xb[2], xb, yb, zb);
+    float pa[3], pb[3], xa, ya, xb, yb;
+    cam_to_camera(cams.a.v, Xa[0], Xa[1], Xa[2], pa);
+    const float za = -pa[2];
+    cam_pixel(cams.a.v, pa[0], pa[1], za, xa, ya);
+    cam_to_camera(cams.b.v, Xb[0], Xb[1], Xb[2], pb);
+    const float zb = -pb[2];
+    cam_pixel(cams.b.v, pb[0], pb[1], zb, xb, yb);
     const bool ok = ac >= min_acc && nh <= 1 && isfinite(tt) && zb >= znear;
     const float nan = __builtin_nanf("");
     if (out.flow) *(f32x2*)(out.flow + r * 2) = f32x2{ok ? xb - (float)x : nan, ok ? yb - (float)y : nan};
@@ -113,7 +108,7 @@ static int launch_flow_points(void* stream, int n, int first, int K, const float
                               const float* t, const float* acc, const FlowCams& cams, const float* table, const float* ext,
                               int normalise, float min_acc, float znear, float inside_tol, const FlowOut& out) {
     hipLaunchKernelGGL(k_flow_points, dim3(durf_cdiv(n, FLOW_THREADS)), dim3(FLOW_THREADS), 0, (hipStream_t)stream, n, first,
-                       (int)cams.a[16], K, origins_s, dirs_s, hit, t, acc, cams, table, ext, normalise, min_acc, znear, inside_tol, out);
+                       (int)cams.a.v[DURF_CAM_W], K, origins_s, dirs_s, hit, t, acc, cams, table, ext, normalise, min_acc, znear, inside_tol, out);
     DURF_CHECK_LAUNCH("k_flow_points");
     return 0;
 }
@@ -305,17 +300,17 @@ int durf_flow_points(void* stream, int n, int first, int K, const float* origins
     int rc = check_flow_scalars(__func__, K, znear, inside_tol);
     if (rc != 0) return rc;
     DURF_REQUIREF(cam_a_host && cam_b_host, "the two camera rows");
-    DURF_REQUIREF(cam_a_host[15] >= 1.0f && cam_a_host[16] >= 1.0f && (double)cam_a_host[15] * cam_a_host[16] < 2147483648.0,
-                 "an image of h >= 1, w >= 1, h w < 2^31, h = %g, w = %g", (double)cam_a_host[15], (double)cam_a_host[16]);
-    const long long hw = (long long)(int)cam_a_host[15] * (int)cam_a_host[16];
+    const float ha = cam_a_host[DURF_CAM_H], wa = cam_a_host[DURF_CAM_W];
+    DURF_REQUIREF(ha >= 1.0f && wa >= 1.0f && (double)ha * wa < 2147483648.0, "an image of h >= 1, w >= 1, h w < 2^31, h = %g, w = %g",
+                 (double)ha, (double)wa);
+    const long long hw = (long long)(int)ha * (int)wa;
     DURF_REQUIREF((long long)first + n <= hw, "pixels [first, first + n) inside the image, first = %d, n = %d, h w = %lld", first, n, hw);
     if (n == 0) return 0;
     DURF_REQUIREF(flow || scene_flow || xyz || target || zcam || moving || valid, "at least one output");
     DURF_REQUIREF(origins_s && dirs_s && t && acc, "origins_s, dirs_s, t and acc");
     DURF_REQUIREF(K == 0 || (hit && pose_a && pose_b && ext && pose_scratch), "hit, pose_a, pose_b, ext and pose_scratch for K = %d", K);
     DURF_REQUIREF(((size_t)flow & 7) == 0, "flow is 8-byte aligned");
-    FlowCams cams;
-    for (int i = 0; i < 17; i++) { cams.a[i] = cam_a_host[i]; cams.b[i] = cam_b_host[i]; }
+    const FlowCams cams{cam_row(cam_a_host), cam_row(cam_b_host)};
     if ((rc = launch_flow_poses(stream, K, pose_a, pose_b, pose_scratch)) != 0) return rc;
     const FlowOut out{flow, scene_flow, xyz, target, zcam, moving, valid};
     return launch_flow_points(stream, n, first, K, origins_s, dirs_s, hit, t, acc, cams, pose_scratch, ext, normalise, min_acc, znear,
@@ -392,13 +387,14 @@ int durf_render_flow(void* stream, int F, int K, const float* cams_host, const f
             const int f = pairs_host[p * 2 + s];
             DURF_REQUIREF(f >= 0 && f < F, "pair %d names frame %d outside [0, %d)", p, f, F);
         }
-    const float hf = cams_host[15], wf = cams_host[16];
+    const float hf = cams_host[DURF_CAM_H], wf = cams_host[DURF_CAM_W];
     DURF_REQUIREF(hf >= 2.0f && wf >= 1.0f && (double)hf * wf < 134217728.0, "frames of h >= 2, w >= 1, h w < 2^27, h = %g, w = %g",
                  (double)hf, (double)wf);
-    for (int f = 1; f < F; f++)
-        DURF_REQUIREF(cams_host[(size_t)f * 17 + 15] == hf && cams_host[(size_t)f * 17 + 16] == wf,
-                     "frames of different sizes: frame %d is %g x %g, frame 0 is %g x %g", f, (double)cams_host[(size_t)f * 17 + 15],
-                     (double)cams_host[(size_t)f * 17 + 16], (double)hf, (double)wf);
+    for (int f = 1; f < F; f++) {
+        const float* cam = cams_host + (size_t)f * DURF_CAM_FLOATS;
+        DURF_REQUIREF(cam[DURF_CAM_H] == hf && cam[DURF_CAM_W] == wf, "frames of different sizes: frame %d is %g x %g, frame 0 is %g x %g",
+                     f, (double)cam[DURF_CAM_H], (double)cam[DURF_CAM_W], (double)hf, (double)wf);
+    }
     DURF_REQUIREF(distance && acc && (K == 0 || (poses && ext)), "distance, acc, and the box poses and extents for K = %d", K);
     DURF_REQUIREF(((size_t)flow & 7) == 0, "flow is 8-byte aligned");
     DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
@@ -408,10 +404,9 @@ int durf_render_flow(void* stream, int F, int K, const float* cams_host, const f
     const size_t n = (size_t)(int)hf * (int)wf;
     for (int p = 0; p < P; p++) {
         const int fa = pairs_host[p * 2], fb = pairs_host[p * 2 + 1];
-        const float* cam_a = cams_host + (size_t)fa * 17;
+        const float* cam_a = cams_host + (size_t)fa * DURF_CAM_FLOATS;
         const float* pose_a = K > 0 ? poses + (size_t)fa * K * 6 : nullptr;
-        FlowCams cams;
-        for (int i = 0; i < 17; i++) { cams.a[i] = cam_a[i]; cams.b[i] = cams_host[(size_t)fb * 17 + i]; }
+        const FlowCams cams{cam_row(cam_a), cam_row(cams_host + (size_t)fb * DURF_CAM_FLOATS)};
         if ((rc = launch_flow_poses(stream, K, pose_a, K > 0 ? poses + (size_t)fb * K * 6 : nullptr, w.table)) != 0) return rc;
         for (size_t i = 0; i < n; i += (size_t)chunk) {
             const int B = (int)(n - i < (size_t)chunk ? n - i : (size_t)chunk);

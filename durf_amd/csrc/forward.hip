@@ -292,8 +292,8 @@ int durf_render_layers(void* stream, const durf_forward_args* a, const int32_t* 
 int durf_camera_rays(void* stream, const float* cams_host, int first, int count, float near, float far, float* origins,
                      float* directions, float* viewdirs, float* radii, float* near_out, float* far_out) {
     DURF_REQUIRE(cams_host && origins && directions && viewdirs && radii && near_out && far_out, "the camera row and the six ray fields");
-    DURF_REQUIRE(cams_host[15] >= 2 && cams_host[16] >= 1, "camera height >= 2, width >= 1");
-    const long n = (long)(int)cams_host[15] * (int)cams_host[16];
+    DURF_REQUIRE(cams_host[DURF_CAM_H] >= 2 && cams_host[DURF_CAM_W] >= 1, "camera height >= 2, width >= 1");
+    const long n = (long)(int)cams_host[DURF_CAM_H] * (int)cams_host[DURF_CAM_W];
     DURF_REQUIRE(first >= 0 && count >= 0 && (long)first + count <= n, "pixels [first, first + count) inside the image");
     float* const rays[6] = {origins, directions, viewdirs, radii, near_out, far_out};
     return durf::launch_camera_rays(stream, cams_host, first, count, near, far, rays);
@@ -325,15 +325,17 @@ int durf_render_trajectory(void* stream, const durf_forward_args* a, const int32
     int h = 0, wd = 0;
     if (image) {
         DURF_REQUIRE(cams_host != nullptr, "the camera rows");
-        h = (int)cams_host[15]; wd = (int)cams_host[16];
-        DURF_REQUIRE(cams_host[15] >= 2 && cams_host[16] >= 1, "camera height >= 2, width >= 1");
+        h = (int)cams_host[DURF_CAM_H]; wd = (int)cams_host[DURF_CAM_W];
+        DURF_REQUIRE(cams_host[DURF_CAM_H] >= 2 && cams_host[DURF_CAM_W] >= 1, "camera height >= 2, width >= 1");
         DURF_REQUIRE((size_t)h * wd < ((size_t)1 << 27), "h * w < 2^27");
-        for (int f = 1; f < F; f++)
-            if ((int)cams_host[f * 17 + 15] != h || (int)cams_host[f * 17 + 16] != wd) {
+        for (int f = 1; f < F; f++) {
+            const float* cam = cams_host + (size_t)f * DURF_CAM_FLOATS;
+            if ((int)cam[DURF_CAM_H] != h || (int)cam[DURF_CAM_W] != wd) {
                 durf_set_error("durf_render_trajectory: frame %d is %d x %d, frame 0 is %d x %d: all frames share one image size", f,
-                               (int)cams_host[f * 17 + 15], (int)cams_host[f * 17 + 16], h, wd);
+                               (int)cam[DURF_CAM_H], (int)cam[DURF_CAM_W], h, wd);
                 return -1;
             }
+        }
     }
     const TrajWs w = carve_trajectory(workspace, F, chunk, a->N, K, L);
     rc = durf::check_workspace("durf_render_trajectory", workspace_bytes, w.total,
@@ -351,7 +353,7 @@ int durf_render_trajectory(void* stream, const durf_forward_args* a, const int32
     for (int f = 0; f < F; f++) {
         for (size_t i = 0; i < n; i += (size_t)chunk) {
             const int B = (int)(n - i < (size_t)chunk ? n - i : (size_t)chunk);
-            rc = durf::launch_camera_rays(stream, cams_host + (size_t)f * 17, (int)i, B, near, far, w.rays);
+            rc = durf::launch_camera_rays(stream, cams_host + (size_t)f * DURF_CAM_FLOATS, (int)i, B, near, far, w.rays);
             if (rc != 0) return rc;
             const size_t at = (size_t)f * n + i;          // (an output that is not asked for stays in the workspace, per chunk)
             rc = forward_chunk(stream, a, box_enable, B, w.rays, K > 0 ? poses + (size_t)f * K * 6 : nullptr, rgb ? rgb + at * 3 : nullptr,

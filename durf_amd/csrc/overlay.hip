@@ -5,11 +5,12 @@
 // Plain fp32 in the order the header states; nothing here synchronises or copies to the host.
 #include "durf_common.h"
 #include "aa2matrix.h"
+#include "camera.h"
 #include "../../include/durf_overlay.h"
 
 // ---- projection ----------------------------------------------------------------------------------------------------------
-// overlay_aa2matrix, the world->object matrix of a box pose, and overlay_to_camera, camera space of a world point: aa2matrix.h
-// (shared with flow.hip and field.hip)
+// overlay_aa2matrix, the world->object matrix of a box pose: aa2matrix.h (shared with flow.hip and field.hip); cam_to_camera and
+// cam_pixel, the two halves of the projection, with the near-plane clip between them: camera.h
 
 // one thread per (frame, box)
 __global__ void __launch_bounds__(64)
@@ -18,12 +19,11 @@ k_project_boxes(int FK, int K, const float* __restrict__ cams, const float* __re
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= FK) return;
     const int f = i / K, k = i - f * K;
-    float cam[17];
+    float cam[DURF_CAM_FLOATS];
 #pragma unroll
-    for (int j = 0; j < 17; j++) cam[j] = cams[(size_t)f * 17 + j];
+    for (int j = 0; j < DURF_CAM_FLOATS; j++) cam[j] = cams[(size_t)f * DURF_CAM_FLOATS + j];
     const float* pose = poses + (size_t)i * 6;
-    const float focal = cam[12], ppx = cam[13], ppy = cam[14];
-    const float xhi = cam[16] - 1.0f, yhi = cam[15] - 1.0f;
+    const float xhi = cam[DURF_CAM_W] - 1.0f, yhi = cam[DURF_CAM_H] - 1.0f;
     const float nan = __builtin_nanf("");
     const bool on = enable ? (enable[k] != 0) : true;
 
@@ -39,10 +39,10 @@ k_project_boxes(int FK, int K, const float* __restrict__ cams, const float* __re
         float P[3];
 #pragma unroll
         for (int a = 0; a < 3; a++) P[a] = c[a] + ((R[0 * 3 + a] * v0 + R[1 * 3 + a] * v1) + R[2 * 3 + a] * v2);     // c + R^T v
-        overlay_to_camera(cam, P, pc[q]);
+        cam_to_camera(cam, P[0], P[1], P[2], pc[q]);
     }
     float pcc[3];
-    overlay_to_camera(cam, c, pcc);
+    cam_to_camera(cam, c[0], c[1], c[2], pcc);
 
     float xmin = nan, ymin = nan, xmax = nan, ymax = nan;        // fminf / fmaxf return the other operand of a NaN
     bool any = false;
@@ -64,10 +64,8 @@ k_project_boxes(int FK, int K, const float* __restrict__ cams, const float* __re
                 if (!a_in) { ax = cx; ay = cy; az = znear; }
                 else { bx = cx; by = cy; bz = znear; }
             }
-            o[0] = ppx + (focal * ax) / az;
-            o[1] = ppy - (focal * ay) / az;
-            o[2] = ppx + (focal * bx) / bz;
-            o[3] = ppy - (focal * by) / bz;
+            cam_pixel(cam, ax, ay, az, o[0], o[1]);
+            cam_pixel(cam, bx, by, bz, o[2], o[3]);
             any = true;
             xmin = fminf(xmin, fminf(o[0], o[2])); xmax = fmaxf(xmax, fmaxf(o[0], o[2]));
             ymin = fminf(ymin, fminf(o[1], o[3])); ymax = fmaxf(ymax, fmaxf(o[1], o[3]));

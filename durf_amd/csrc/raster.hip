@@ -3,10 +3,10 @@
 // nearest covering triangle of each of its pixels with exact int64 edge functions; then a per-pixel attribute gather.  The only
 // atomics are integer adds on counters; the picture is a minimum over a set and does not depend on their order.  Nothing
 // synchronises or copies to the host; no workgroup waits for another.
-#include <cfloat>
 #include <climits>
 #include "workspace.h"
 #include "scan.h"
+#include "camera.h"
 #include "../../include/durf_raster.h"
 
 #define RB DURF_RASTER_BLOCK
@@ -35,8 +35,6 @@ k_raster_clear(int n_tiles, int32_t* __restrict__ tile_count, int32_t* __restric
     if (i < DURF_RASTER_COUNTS) counts[i] = 0;
 }
 
-__device__ __forceinline__ bool raster_finite(float x) { return fabsf(x) <= FLT_MAX; }      // false for NaN
-
 // the pixels whose centres lie in [lo, hi] (snapped units): ceil(lo / 256) .. floor(hi / 256); >> floors for negatives too
 __device__ __forceinline__ int raster_px_lo(int lo) { return (lo + (DURF_RASTER_SUBPIXEL - 1)) >> 8; }
 __device__ __forceinline__ int raster_px_hi(int hi) { return hi >> 8; }
@@ -56,8 +54,7 @@ k_raster_setup(const RasterDims D, const float* __restrict__ cams, int V, const 
     int packed = REC_EMPTY;
     if (live) {
         const int f = i / (unsigned)D.T, t = i - (unsigned)f * (unsigned)D.T;
-        const float* cam = cams + (size_t)f * 17;
-        const float focal = cam[12], ppx = cam[13], ppy = cam[14];
+        const float* cam = cams + (size_t)f * DURF_CAM_FLOATS;
         float x[3], y[3], z[3];
         bool valid = true;
         int v[3];
@@ -71,15 +68,12 @@ k_raster_setup(const RasterDims D, const float* __restrict__ cams, int V, const 
             for (int c = 0; c < 3; c++) {
                 const float* P = vertices + (size_t)v[c] * 3;
                 const float P0 = P[0], P1 = P[1], P2 = P[2];
-                const float d0 = P0 - cam[3], d1 = P1 - cam[7], d2 = P2 - cam[11];
                 float pc[3];
-#pragma unroll
-                for (int j = 0; j < 3; j++) pc[j] = (cam[j] * d0 + cam[4 + j] * d1) + cam[8 + j] * d2;
-                valid = valid && raster_finite(P0) && raster_finite(P1) && raster_finite(P2) && raster_finite(pc[0]) &&
-                        raster_finite(pc[1]) && raster_finite(pc[2]);
+                cam_to_camera(cam, P0, P1, P2, pc);
+                valid = valid && cam_finite(P0) && cam_finite(P1) && cam_finite(P2) && cam_finite(pc[0]) && cam_finite(pc[1]) &&
+                        cam_finite(pc[2]);
                 z[c] = -pc[2];
-                x[c] = ppx + (focal * pc[0]) / z[c];
-                y[c] = ppy - (focal * pc[1]) / z[c];
+                cam_pixel(cam, pc[0], pc[1], z[c], x[c], y[c]);
             }
         }
         const float lim = (float)DURF_RASTER_MAX_COORD;

@@ -1,11 +1,9 @@
 // A camera trajectory in one call (durf_render_trajectory, csrc/forward.hip; the reference's notebooks/durf_render_traj.ipynb
 // loop): the three kernels around the per-chunk forward launch sequence.  No rendering maths here -- a chunk's rays are the
-// pinhole generator of durf_gen_batch (csrc/pinhole.h), the boxes between two labelled timesteps are a lerp with the angles
+// pinhole generator of durf_gen_batch (csrc/camera.h), the boxes between two labelled timesteps are a lerp with the angles
 // taken along the shorter arc, and the 8-bit frame is one multiply and a round per channel.
 #include "durf_common.h"
-#include "pinhole.h"
-
-struct CamRow { float v[17]; };
+#include "camera.h"
 
 // the rays of pixels [first, first + count) of one camera into slots [0, count): one thread per ray
 __global__ void __launch_bounds__(256)
@@ -80,11 +78,9 @@ k_frame_pack(int count, const float* __restrict__ rgb, uint8_t* __restrict__ rgb
 
 namespace durf {
 
-int launch_camera_rays(void* stream, const float* cam17_host, int first, int count, float near, float far, float* const* rays) {
+int launch_camera_rays(void* stream, const float* cam_host, int first, int count, float near, float far, float* const* rays) {
     if (count <= 0) return 0;
-    CamRow c;
-    for (int j = 0; j < 17; j++) c.v[j] = cam17_host[j];
-    hipLaunchKernelGGL(k_camera_rays, dim3(durf_cdiv(count, 256)), dim3(256), 0, (hipStream_t)stream, count, c, first, near, far,
+    hipLaunchKernelGGL(k_camera_rays, dim3(durf_cdiv(count, 256)), dim3(256), 0, (hipStream_t)stream, count, cam_row(cam_host), first, near, far,
                        rays[0], rays[1], rays[2], rays[3], rays[4], rays[5]);
     DURF_CHECK_LAUNCH("k_camera_rays");
     note_dispatch(DURF_LAYERLOG_TRAJ_RAYS);

@@ -3,9 +3,9 @@
 // depth up and takes the running weighted mean.  A gather: no atomics, no counts, nothing that depends on a schedule; the
 // volume is read once and written once per call.  Then the lattice durf_mesh_count takes and a trilinear sampler.  Nothing
 // synchronises or copies to the host; no workgroup waits for another.
-#include <cfloat>
 #include <cmath>
 #include "durf_common.h"
+#include "camera.h"
 #include "../../include/durf_mesh.h"
 #include "../../include/durf_tsdf.h"
 
@@ -20,7 +20,7 @@ struct TsdfLattice {
 
 struct TsdfFrames {
     int F, h, w;
-    const float* cams;                 // [F,17]
+    const float* cams;                 // [F,DURF_CAM_FLOATS]
     const float* depth;                // [F,h,w]
     const float* acc;                  // nullable
     const float* rgb;                  // nullable
@@ -31,11 +31,11 @@ struct TsdfFrames {
     int select, other_mode;
 };
 
-__device__ __forceinline__ bool tsdf_finite(float x) { return fabsf(x) <= FLT_MAX; }        // false for NaN
-
 // ---- integrate -------------------------------------------------------------------------------------------------------------------
 // f, and with it every camera, xform and weight address, is the same for all lanes: the compiler reads those rows with scalar
-// loads.  The per-lane state is D, W, the four colour floats and the voxel's position.
+// loads (camera.h's functions take the row's pointer, never a per-lane copy).  cam_finite (camera.h) is the library's one
+// finite-and-not-NaN test: it guards depth, weights and lattice coordinates here as well as camera space.  The per-lane state is D, W, the
+// four colour floats and the voxel's position.
 __global__ void __launch_bounds__(TB)
 k_tsdf_integrate(const TsdfLattice L, const TsdfFrames A, float* __restrict__ tsdf, float* __restrict__ weight, float* __restrict__ colour) {
     const int g = blockIdx.x * TB + threadIdx.x;                             // n < 2^27
@@ -54,29 +54,27 @@ k_tsdf_integrate(const TsdfLattice L, const TsdfFrames A, float* __restrict__ ts
     bool touched = false, coloured = false;
     const float lim = (float)DURF_TSDF_MAX_COORD;
     for (int f = 0; f < A.F; f++) {
-        const float* __restrict__ cam = A.cams + (size_t)f * 17;
+        const float* __restrict__ cam = A.cams + (size_t)f * DURF_CAM_FLOATS;
         float X[3] = {P[0], P[1], P[2]};
         if (A.xform) {
             const float* __restrict__ M = A.xform + (size_t)f * 12;
 #pragma unroll
             for (int c = 0; c < 3; c++) X[c] = ((M[4 * c] * P[0] + M[4 * c + 1] * P[1]) + M[4 * c + 2] * P[2]) + M[4 * c + 3];
         }
-        const float d0 = X[0] - cam[3], d1 = X[1] - cam[7], d2 = X[2] - cam[11];
         float pc[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) pc[c] = (cam[c] * d0 + cam[4 + c] * d1) + cam[8 + c] * d2;
-        if (!(tsdf_finite(X[0]) && tsdf_finite(X[1]) && tsdf_finite(X[2]) && tsdf_finite(pc[0]) && tsdf_finite(pc[1]) && tsdf_finite(pc[2])))
+        cam_to_camera(cam, X[0], X[1], X[2], pc);
+        if (!(cam_finite(X[0]) && cam_finite(X[1]) && cam_finite(X[2]) && cam_finite(pc[0]) && cam_finite(pc[1]) && cam_finite(pc[2])))
             continue;                                                        // 1 INVALID
         const float z = -pc[2];
         if (!(z >= A.znear)) continue;                                       // 2 BEHIND
-        const float focal = cam[12];
-        const float x = cam[13] + (focal * pc[0]) / z, y = cam[14] - (focal * pc[1]) / z;
+        float x, y;
+        cam_pixel(cam, pc[0], pc[1], z, x, y);
         if (!(fabsf(x) <= lim) || !(fabsf(y) <= lim)) continue;              // 3 RANGE
         const int px = (int)rintf(x), py = (int)rintf(y);
         if (px < 0 || px >= A.w || py < 0 || py >= A.h) continue;            // 4 OUTSIDE
         const size_t p = ((size_t)f * A.h + py) * A.w + px;                  // F h w < 2^31
         const float dep = A.depth[p];
-        if (!tsdf_finite(dep) || !(dep > 0.0f)) continue;                    // 5 HOLE
+        if (!cam_finite(dep) || !(dep > 0.0f)) continue;                    // 5 HOLE
         if (A.acc && !(A.acc[p] >= A.min_acc)) continue;                     // 6 FAINT
         const float sdf = dep - z;
         if (sdf < -A.trunc) continue;                                        // 7 OCCLUDED
@@ -86,7 +84,7 @@ k_tsdf_integrate(const TsdfLattice L, const TsdfFrames A, float* __restrict__ ts
             if (!mine && (A.other_mode == 0 || !(sdf >= A.trunc))) continue; // 8 OTHER
         }
         const float wf = A.frame_weight ? A.frame_weight[f] : 1.0f;
-        if (!tsdf_finite(wf) || !(wf > 0.0f)) continue;                      // 9 WEIGHT
+        if (!cam_finite(wf) || !(wf > 0.0f)) continue;                      // 9 WEIGHT
         const float dn = fminf(sdf / A.trunc, 1.0f);
         const float Wn = W + wf;
         D = (W * D + wf * dn) / Wn;
@@ -146,7 +144,7 @@ k_tsdf_sample(int nu, int nv, int nw, const TsdfInverse Q, const float* __restri
     const int dims[3] = {nu, nv, nw};
     bool inside = true;
 #pragma unroll
-    for (int c = 0; c < 3; c++) inside = inside && tsdf_finite(q[c]) && q[c] >= 0.0f && q[c] <= (float)(dims[c] - 1);
+    for (int c = 0; c < 3; c++) inside = inside && cam_finite(q[c]) && q[c] >= 0.0f && q[c] <= (float)(dims[c] - 1);
     float v = __builtin_nanf("");
     float col[3] = {0.0f, 0.0f, 0.0f};
     bool good = false;

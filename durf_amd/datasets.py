@@ -253,7 +253,7 @@ class Waymo:
 
     def eval_set(self):
         """The split as data, for train_boxpose.evaluate_set: every image in the order next() yields them from a fresh loader
-        -> dict(cams [F,17] host rows (raygen.camera_row), ts [F] host ints (what _next_test puts into test_case['ts']),
+        -> dict(cams [F,CAM_FLOATS] host rows (camera.row), ts [F] host ints (what _next_test puts into test_case['ts']),
         pixels / depth / sky: lists of [H,W,.] views of the resident timestep data, ext: list of the [K,3] half extents of each
         frame's timestep, init [T,K,6]).  No rays are made and the iterator is not advanced."""
         tb = self.tables()

@@ -23,6 +23,7 @@ import math
 import os
 import sys
 
+from . import camera
 from .query_field import build_parser as _field_parser, parse_grid
 from .render_traj import add_scene_arguments, open_scene, restore_model
 
@@ -64,7 +65,7 @@ def truth_cloud(es, config, poses, keep_objects):
     clouds, planes = [], []
     for f in range(len(es['ts'])):
         cam = es['cams'][f]
-        h, w = int(cam[15]), int(cam[16])
+        h, w = camera.size(cam)
         d = es['depth'][f].reshape(h * w)
         plane = d > 0
         pts = geometry.depth_points(cam, d, config.near, config.far)
@@ -86,7 +87,7 @@ def frames_cloud(model, config, variables, es, alpha, chunk, planes):
     cams, ts = es['cams'], [int(t) for t in es['ts']]
     groups = {}
     for f in range(len(ts)):
-        groups.setdefault((int(cams[f][15]), int(cams[f][16]), ts[f]), []).append(f)
+        groups.setdefault(camera.size(cams[f]) + (ts[f],), []).append(f)
     clouds = [None] * len(ts)
     for (h, w, t), members in groups.items():
         out = model.render_trajectory(variables, cams[members], [float(t)] * len(members), es['ext'][members[0]], config.white_bkgd, alpha,
@@ -111,7 +112,7 @@ def lidar_cloud(args, model, config, variables, dataset, alpha, ext):
             pose_end = np.asarray(z['pose_end'], np.float64).reshape(-1, 3, 4) if 'pose_end' in z.files else None
             times = np.asarray(z['times'], np.float32).reshape(-1)
     else:
-        c2w = np.asarray(dataset.ts_data[0].cams[0, :12], np.float64).reshape(3, 4)
+        c2w = camera.c2w(dataset.ts_data[0].cams[0]).astype(np.float64)
         p0 = np.concatenate([c2w[:, :3] @ np.asarray(CAM_FROM_SENSOR), c2w[:, 3:]], 1)
         pose_start, pose_end, times = p0[None], None, np.zeros(1, np.float32)
     K = variables.layout.K

@@ -15,6 +15,8 @@ import struct
 
 import numpy as np
 
+from . import camera
+
 FLO_MAGIC = b'PIEH'
 FLO_UNKNOWN = 1e10            # what an invalid pixel is written as; the format's threshold for "unknown" is 1e9
 FLO_UNKNOWN_THRESH = 1e9
@@ -29,7 +31,7 @@ def default_pairs(F, backward=False):
 def render_flow(out, cams, ext, *, near, far, pairs=None, backward=False, normalise=True, min_acc=0.5, znear=1e-2, inside_tol=1e-3,
                 box_enable=None, chunk=8192, outputs=('flow', 'valid', 'moving')):
     """Where every pixel of a source frame lands in a target frame, for P pairs of frames as ONE library call
-    (durf_render_flow).  out: render_trajectory's own result -- it needs distance, acc [F,h,w] and poses [F,K,6]; cams [F,17]
+    (durf_render_flow).  out: render_trajectory's own result -- it needs distance, acc [F,h,w] and poses [F,K,6]; cams [F,CAM_FLOATS]
     the camera rows it was rendered with, ext [K,3]; near / far as rendered (they only fill ray fields nothing here reads).
     pairs [P,2] (source, target); None: f -> f + 1 for every consecutive pair, backward = True adds f + 1 -> f.
     -> dict of [P,h,w,.] tensors for `outputs` (ops.FLOW_OUTPUTS: flow [.,2], scene_flow, xyz, target [.,3], zcam, moving --
@@ -41,8 +43,8 @@ def render_flow(out, cams, ext, *, near, far, pairs=None, backward=False, normal
     missing = [k for k in ('distance', 'acc', 'poses') if k not in out]
     if missing:
         raise ValueError('render_flow needs the outputs %s of render_trajectory' % missing)
-    cams = np.asarray(cams, np.float32).reshape(-1, 17)
-    F, h, w = int(cams.shape[0]), int(cams[0, 15]), int(cams[0, 16])
+    cams, h, w = camera.as_rows(cams, 'flow.render_flow', one_size=False)
+    F = int(cams.shape[0])
     pairs = default_pairs(F, backward) if pairs is None else np.asarray(pairs, np.int32).reshape(-1, 2)
     poses = out['poses']
     K, dev = int(poses.shape[1]), poses.device
@@ -58,7 +60,7 @@ def render_flow(out, cams, ext, *, near, far, pairs=None, backward=False, normal
 def frame_depth(out, cams, ext, **kw):
     """every frame's own zcam [F,h,w] -- the depth along the camera's axis of what each pixel sees, NaN where invalid:
     render_flow with every frame as its own target.  What warp() tests occlusion against."""
-    F = int(np.asarray(cams).reshape(-1, 17).shape[0])
+    F = int(camera.as_rows(cams, 'flow.frame_depth', one_size=False)[0].shape[0])
     kw.pop('pairs', None)
     return render_flow(out, cams, ext, pairs=[(f, f) for f in range(F)], outputs=('zcam',), **kw)['zcam']
 

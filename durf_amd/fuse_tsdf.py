@@ -78,24 +78,15 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     origin, shape, step = check_args(args)
     import numpy as np
-    from . import mesh, trajectory, tsdf
+    from . import camera, mesh, trajectory, tsdf
     dev, config, dataset = open_scene(args, boxes=args.synthetic_boxes)  # (--objects is this command's switch, not the box count)
-    if args.synthetic:
-        cam_rows, ext = dataset.ts_data[0].cams, dataset.ext
-    else:
-        cam_rows = np.concatenate([np.asarray(dataset.camtoworlds, np.float32).reshape(-1, 12),
-                                   np.stack([dataset.focal, dataset.principal_point[:, 0], dataset.principal_point[:, 1],
-                                             dataset.h, dataset.w], -1).astype(np.float32)], -1)
-        ext = dataset.peek()['ext']
-    if not 0 <= args.cam < len(cam_rows):
-        raise SystemExit('fuse_tsdf: --cam %d of %d cameras' % (args.cam, len(cam_rows)))
-    focal, ppx, ppy, h, w = [float(x) for x in cam_rows[args.cam][12:]]
+    cam_rows, ext, key_c2w, key_t = camera.scene_cameras(args, dataset, 'fuse_tsdf')
+    focal, ppx, ppy, h, w = camera.intrinsics(cam_rows[args.cam])
     model, variables, alpha = restore_model(args, config, dataset, dev)
     if args.traj is not None:
         c2w, times = trajectory.load_trajectory(args.traj)
     else:
-        key_c2w = [dataset.ts_data[0].cams[0, :12].reshape(3, 4), dataset.ts_data[-1].cams[-1, :12].reshape(3, 4)]
-        c2w, times = trajectory.make_trajectory(key_c2w, [0.0, float(dataset.T - 1)], args.frames)
+        c2w, times = trajectory.make_trajectory(key_c2w, key_t, args.frames)
     cams = trajectory.camera_rows(c2w, focal, (ppx, ppy), int(h), int(w))
     K = variables.layout.K
     obj_step = args.obj_step if args.obj_step is not None else 0.5 * step

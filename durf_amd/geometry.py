@@ -15,6 +15,7 @@ means and the thresholds (<= max_dist) need.  The grid rule of include/durf_geom
 cells per axis) makes the result equal to a brute-force search in the same fp32 arithmetic, bit for bit."""
 import numpy as np
 
+from . import camera
 from ._geom_sigs import DURF_GEOM_MAX_CELLS as MAX_CELLS        # per axis (include/durf_geom.h)
 SLACK = 1.0 + 2.0 ** -10            # a cell is max_dist * SLACK wide
 SORT_QUERIES = True                 # nearest()'s default: queries in the order of their own cell keys (profiles/geometry_time.txt)
@@ -197,8 +198,7 @@ def depth_points(cam17, depth, near, far, mask=None):
     arithmetic, one boolean gather."""
     import torch
     from . import raygen
-    cam = np.asarray(cam17, np.float32).reshape(17)
-    h, w = int(cam[15]), int(cam[16])
+    cam, h, w = camera.as_rows(cam17, 'geometry.depth_points', frames=1)
     depth = torch.as_tensor(depth)
     if depth.numel() != h * w:
         raise ValueError('geometry.depth_points: a depth image of %d values for a camera of %d x %d' % (depth.numel(), h, w))

@@ -77,7 +77,7 @@ def sweep_motion(pose_start, pose_end):
 
 
 def sweep_rows(pose_start, pose_end=None):
-    """[F,18] float32 rows of durf_lidar.h's sweeps: pose_start [F,3,4] (or one [3,4]), pose_end likewise or None (the sensor
+    """[F,18] float32 rows of durf_lidar.h's sweeps (a sensor pose and its motion: a layout of its own, not camera.py's row): pose_start [F,3,4] (or one [3,4]), pose_end likewise or None (the sensor
     stands still: omega = dp = 0)"""
     ps = np.asarray(pose_start, np.float64).reshape(-1, 3, 4)
     rows = np.zeros((ps.shape[0], 18), np.float64)

@@ -14,7 +14,7 @@ from typing import Any
 
 import torch
 
-from . import ops
+from . import camera, ops
 from . import utils
 
 IN_BKGD, IN_OBJ, W_BKGD, W_OBJ = 60, 63, ops.W_BKGD, ops.W_OBJ
@@ -661,7 +661,7 @@ class MipNerfModel:
     def render_trajectory(self, variables, cams, times, ext, white_bkgd, alpha, *, near, far, chunk=8192, box_enable=None,
                           outputs=('rgb8', 'distance', 'acc'), out=None):
         """A camera flown through the scene while the boxes move (the reference's notebooks/durf_render_traj.ipynb loop), ONE
-        library call (durf_render_trajectory, csrc/forward.hip): cams [F,17] host camera rows (raygen.camera_row; one image
+        library call (durf_render_trajectory, csrc/forward.hip): cams [F,CAM_FLOATS] host camera rows (camera.row; one image
         size), times [F] in [0, T - 1], fractional times take the boxes between two labelled timesteps (interpolate_pose) ->
         dict of [F,h,w,.] tensors for the requested `outputs` ('rgb8' uint8, 'rgb', 'distance', 'acc') plus 'poses' [F,K,6].
         The rays are generated per chunk on the device and the frames written in place: no image-sized ray buffer, nothing
@@ -671,9 +671,8 @@ class MipNerfModel:
         outputs = tuple(outputs)
         if not outputs:           # poses only: nothing is rendered and no camera is looked at
             return self._trajectory_call(variables, None, times, ext, white_bkgd, alpha, near, far, chunk, box_enable, (), out)
-        cams = np.asarray(cams, np.float32).reshape(-1, 17)
+        cams, h, w = camera.as_rows(cams, 'render_trajectory', one_size=False)
         res = self._trajectory_call(variables, cams, times, ext, white_bkgd, alpha, near, far, chunk, box_enable, outputs, out)
-        h, w = int(cams[0, 15]), int(cams[0, 16])
         return {k: (v if k == 'poses' else v.reshape((v.shape[0], h, w) + tuple(v.shape[2:]))) for k, v in res.items()}
 
     def interpolate_pose(self, variables, t):

@@ -8,7 +8,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, camera
 from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs
 
 
@@ -1533,7 +1533,7 @@ TRAJECTORY_OUTPUTS = ('rgb8', 'rgb', 'distance', 'acc')
 def render_trajectory(cams, times, box_centers, ext, bkgd_params, obj_params, obj_param_stride, N, num_levels, alpha, enc_flags,
                       chunk, near, far, lindisp=False, bkgd_mode=BKGD_GREY, density_bias=-1.0, resample_padding=0.01,
                       box_enable=None, outputs=('rgb8', 'distance', 'acc'), out=None):
-    """A camera trajectory as ONE library call (durf_render_trajectory): cams [F,17] host rows (durf_gen_batch's layout, one
+    """A camera trajectory as ONE library call (durf_render_trajectory): cams [F,CAM_FLOATS] host rows (camera.rows, one
     image size), times [F] host floats in [0, T - 1], box_centers [T,K,6] on the device (read there: no host copy) -> dict:
     the requested `outputs` of rgb8 [F,n,3] uint8, rgb [F,n,3], distance [F,n], acc [F,n], and poses [F,K,6], the box poses
     every frame was rendered with.  outputs = (): poses only, nothing is rendered (cams may be None).  out: dict of
@@ -1551,10 +1551,10 @@ def render_trajectory(cams, times, box_centers, ext, bkgd_params, obj_params, ob
     n = 0
     cam_arr = None
     if outputs:
-        cams = np.ascontiguousarray(np.asarray(cams, np.float32).reshape(-1, 17))
+        cams, h, w = camera.as_rows(cams, 'render_trajectory', one_size=False)
         if cams.shape[0] != F:
             raise ValueError('%d camera rows for %d frame times' % (cams.shape[0], F))
-        n = int(cams[0, 15]) * int(cams[0, 16]) if F else 0
+        n = h * w
         cam_arr = (C.c_float * cams.size)(*cams.reshape(-1).tolist())
     shapes = dict(rgb8=((F, n, 3), torch.uint8), rgb=((F, n, 3), torch.float32), distance=((F, n), torch.float32),
                   acc=((F, n), torch.float32), poses=((F, K, 6), torch.float32))
@@ -1781,11 +1781,11 @@ assert len(BOX_RECT_FIELDS) == BOX_RECT_FLOATS
 
 
 def project_boxes(cams, poses, ext, box_enable=None, znear=1e-2):
-    """cams [F,17] device rows, poses [F,K,6], ext [K,3] -> (segments [F,K,12,4], rect [F,K,BOX_RECT_FLOATS]): one launch of
+    """cams [F,CAM_FLOATS] device rows, poses [F,K,6], ext [K,3] -> (segments [F,K,12,4], rect [F,K,BOX_RECT_FLOATS]): one launch of
     durf_project_boxes, no read-back.  box_enable: None or K values 0 / 1 (a box with 0 is culled whole)."""
     F, K = int(poses.shape[0]), int(poses.shape[1])
     dev = poses.device
-    assert tuple(cams.shape) == (F, 17) and tuple(poses.shape) == (F, K, 6) and tuple(ext.shape) == (K, 3), \
+    assert tuple(cams.shape) == (F, CAM_FLOATS) and tuple(poses.shape) == (F, K, 6) and tuple(ext.shape) == (K, 3), \
         (tuple(cams.shape), tuple(poses.shape), tuple(ext.shape))
     segments = torch.empty(F, K, BOX_EDGES, 4, device=dev)
     rect = torch.empty(F, K, BOX_RECT_FLOATS, device=dev)
@@ -1963,7 +1963,7 @@ def _flow_outputs(outputs, lead, dev, out=None):
 def flow_points(origins_s, dirs_s, hit, t, acc, cam_a, cam_b, pose_a, pose_b, ext, *, first=0, normalise=True, min_acc=0.5,
                 znear=1e-2, inside_tol=1e-3, outputs=FLOW_OUTPUTS, out=None):
     """where n pixels [first, first + n) of frame a go (durf_flow_points: a one-wave pose launch and one per-pixel launch):
-    origins_s, dirs_s [n,3], hit [n,K] int32 (ray_setup's outputs at pose_a), t, acc [n], cam_a / cam_b 17 host floats, pose_a /
+    origins_s, dirs_s [n,3], hit [n,K] int32 (ray_setup's outputs at pose_a), t, acc [n], cam_a / cam_b one camera row each, pose_a /
     pose_b [K,6], ext [K,3] -> dict of the requested `outputs` (FLOW_OUTPUTS), [n,.]"""
     n, K = int(origins_s.shape[0]), int(pose_a.shape[0])
     dev = origins_s.device
@@ -1976,7 +1976,7 @@ def flow_points(origins_s, dirs_s, hit, t, acc, cam_a, cam_b, pose_a, pose_b, ex
     with _Timed('flow_points'):
         _lib.check(_lib.flow_lib().durf_flow_points(
             _stream(), n, int(first), K, _p(_f32(origins_s)), _p(_f32(dirs_s)), _p(hit) if K else None, _p(_f32(t)), _p(_f32(acc)),
-            _host_floats(cam_a, 17, 'cam_a'), _host_floats(cam_b, 17, 'cam_b'), _p(_f32(pose_a)) if K else None,
+            _host_floats(cam_a, CAM_FLOATS, 'cam_a'), _host_floats(cam_b, CAM_FLOATS, 'cam_b'), _p(_f32(pose_a)) if K else None,
             _p(_f32(pose_b)) if K else None, _p(_f32(ext)) if K else None, int(bool(normalise)), float(min_acc), float(znear),
             float(inside_tol), _p(scratch), *[_p(res.get(name)) for name in FLOW_OUTPUTS]), 'durf_flow_points')
     return res
@@ -2026,14 +2026,14 @@ def flow_color(flow, max_mag, want_float=True, want_u8=False):
 
 def render_flow(cams, poses, ext, distance, acc, pairs, near, far, chunk, *, box_enable=None, normalise=True, min_acc=0.5, znear=1e-2,
                 inside_tol=1e-3, outputs=('flow', 'valid', 'moving'), out=None):
-    """P pairs of frames as ONE library call (durf_render_flow): cams [F,17] host rows, poses [F,K,6] on the device, ext [K,3],
+    """P pairs of frames as ONE library call (durf_render_flow): cams [F,CAM_FLOATS] host rows, poses [F,K,6] on the device, ext [K,3],
     distance / acc [F,n] (render_trajectory's planes), pairs [P,2] host ints (source, target) -> dict of the requested `outputs`
     (FLOW_OUTPUTS), [P,n,.].  out: dict of preallocated contiguous tensors to write into.  The call only enqueues work."""
     import numpy as np
-    cams = np.ascontiguousarray(np.asarray(cams, np.float32).reshape(-1, 17))
+    cams, h, w = camera.as_rows(cams, 'render_flow', one_size=False)
     pairs = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
     F, P, K = int(cams.shape[0]), int(pairs.shape[0]), int(poses.shape[1])
-    n = int(cams[0, 15]) * int(cams[0, 16]) if F else 0
+    n = h * w
     dev = distance.device
     if int(poses.shape[0]) != F or tuple(distance.shape) != (F, n) or tuple(acc.shape) != (F, n):
         raise ValueError('%d camera rows of %d pixels for poses %s, distance %s, acc %s' %
@@ -2377,7 +2377,7 @@ def raster_workspace_bytes(F, T, h, w):
 
 
 def _raster_mesh(cams, vertices, triangles):
-    assert cams.dtype == torch.float32 and cams.is_cuda and cams.is_contiguous() and cams.dim() == 2 and cams.shape[1] == 17, tuple(cams.shape)
+    assert cams.dtype == torch.float32 and cams.is_cuda and cams.is_contiguous() and cams.dim() == 2 and cams.shape[1] == CAM_FLOATS, tuple(cams.shape)
     V, T = int(vertices.shape[0]), int(triangles.shape[0])
     assert vertices.numel() == 3 * V and triangles.dtype == torch.int32 and triangles.is_cuda and triangles.is_contiguous() and triangles.numel() == 3 * T
     _f32(vertices)
@@ -2562,13 +2562,13 @@ def _tsdf_state(tsdf, weight, colour, shape):
 
 def tsdf_integrate(tsdf, weight, colour, shape, origin, du, dv, dw, cams, depth, trunc, acc=None, min_acc=0.5, rgb=None, label=None,
                    select=0, other_mode=0, xform=None, frame_weight=None, max_weight=64.0, znear=1e-2):
-    """durf_tsdf_integrate: the F frames depth [F,h,w] (cams [F,17] on the device) into the state tsdf, weight [n] and colour
+    """durf_tsdf_integrate: the F frames depth [F,h,w] (cams [F,CAM_FLOATS] on the device) into the state tsdf, weight [n] and colour
     [n,4] (or None), IN PLACE, one launch.  acc [F,h,w], rgb [F,h,w,3], label int32 [F,h,w], xform [F,3,4], frame_weight [F]:
     on the device, or None."""
     nu, nv, nw, n = _tsdf_state(tsdf, weight, colour, shape)
     assert _f32(depth).dim() == 3, tuple(depth.shape)
     F, h, w = (int(s) for s in depth.shape)
-    assert _f32(cams).numel() == 17 * F, (tuple(cams.shape), F)
+    assert _f32(cams).numel() == CAM_FLOATS * F, (tuple(cams.shape), F)
     assert acc is None or _f32(acc).numel() == F * h * w
     assert rgb is None or _f32(rgb).numel() == 3 * F * h * w
     assert label is None or _i32(label, F * h * w, 'label') is label

@@ -10,7 +10,7 @@ box-hit rays).  Lines are not anti-aliased."""
 import numpy as np
 import torch
 
-from . import ops
+from . import camera, ops
 
 # 16 colours, one per box index (K <= 16): fixed, so that box k has one colour in every picture
 PALETTE = np.array([[230, 25, 75], [60, 180, 75], [255, 225, 25], [0, 130, 200], [245, 130, 48], [145, 30, 180], [70, 240, 240],
@@ -24,8 +24,8 @@ def _check_k(K):
 
 
 def project_boxes(cams, poses, ext, box_enable=None, znear=1e-2):
-    """Where the boxes are in F pictures.  cams [F,17] camera rows (numpy or a tensor: trajectory.camera_rows /
-    raygen.camera_row), poses [F,K,6] device tensor (centre, rotation vector: render_trajectory's `poses`, or box_centers[t]
+    """Where the boxes are in F pictures.  cams [F,CAM_FLOATS] camera rows (numpy or a tensor: camera.rows /
+    camera.row), poses [F,K,6] device tensor (centre, rotation vector: render_trajectory's `poses`, or box_centers[t]
     repeated), ext [K,3] half extents, box_enable None or K values 0 / 1, znear > 0 the plane edges are clipped against.
     -> dict: segments [F,K,12,4] (x0, y0, x1, y1 per edge, NaN where culled), rect [F,K,6] (ops.BOX_RECT_FIELDS: xmin, ymin,
     xmax, ymax clipped to the picture, zc, visible), depth [F,K] (the centre's camera depth) and visible [F,K] bool."""
@@ -35,8 +35,7 @@ def project_boxes(cams, poses, ext, box_enable=None, znear=1e-2):
     _check_k(K)
     dev = poses.device
     cams = torch.as_tensor(np.asarray(cams, np.float32) if not torch.is_tensor(cams) else cams)
-    if tuple(cams.shape) != (F, 17):
-        raise ValueError('cams: [%d,17] camera rows for %d frames of poses, got %s' % (F, F, tuple(cams.shape)))
+    camera.check_shape(cams.shape, 'overlay.project_boxes', frames=F)
     ext = torch.as_tensor(ext)
     if tuple(ext.shape) != (K, 3):
         raise ValueError('ext: [%d,3] half extents, got %s' % (K, tuple(ext.shape)))
@@ -88,16 +87,15 @@ def draw_boxes(frames, segments, colors=None, width=1.5, opacity=1.0, label=Fals
 
 def overlay_trajectory(out, cams, ext, box_enable=None, znear=1e-2, colors=None, width=1.5, opacity=1.0, label=False):
     """The boxes on a rendered trajectory: `out` is MipNerfModel.render_trajectory's own result (its `poses` [F,K,6] and `rgb8`
-    and / or `rgb` [F,h*w,3]), cams the [F,17] rows it was rendered from, box_enable the switch it was rendered with.
+    and / or `rgb` [F,h*w,3]), cams the camera rows it was rendered from, box_enable the switch it was rendered with.
     -> dict: decorated COPIES of rgb8 / rgb in their own shapes, rect [F,K,6] (the boxes' 2D rectangles), segments, visible,
     and with label=True label [F,h,w].  Two launches and one more per picture kind; `out` is left as it is."""
     if 'poses' not in out or not ('rgb8' in out or 'rgb' in out):
         raise ValueError('out: render_trajectory\'s result with poses and rgb8 or rgb, got %s' % (sorted(out),))
-    cams_np = np.asarray(cams.cpu() if torch.is_tensor(cams) else cams, np.float32).reshape(-1, 17)
     F = int(out['poses'].shape[0])
+    cams_np, h, w = camera.as_rows(cams, 'overlay.overlay_trajectory', one_size=False) if F else (np.zeros((0, camera.CAM_FLOATS), np.float32), 1, 1)
     if cams_np.shape[0] != F:
         raise ValueError('%d camera rows for %d frames' % (cams_np.shape[0], F))
-    h, w = (int(cams_np[0, 15]), int(cams_np[0, 16])) if F else (1, 1)
     proj = project_boxes(cams_np, out['poses'], ext, box_enable, znear)
     res = dict(rect=proj['rect'], segments=proj['segments'], visible=proj['visible'])
     want_label = label

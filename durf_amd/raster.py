@@ -3,7 +3,7 @@ libdurf_raster.so): per pixel the nearest triangle, its camera depth, and the ve
 
     s = mesh.extract_scene(model, variables, origin, shape, step=0.25, iso=5.0, ext=ext, obj_step=0.05)
     m = merge(s, ts=3)                                             # one mesh in the world, the boxes at their poses of time 3
-    r = render_mesh(m, cams)                                       # cams [F,17]: trajectory.camera_rows / raygen.camera_row
+    r = render_mesh(m, cams)                                       # cams: camera.rows / camera.row
     e = depth_error(r['depth'], frames['distance'], frames['acc'])  # against render_trajectory's frames of the same cameras
     write_depth('out/depth_0000', r['depth'][0], r['mask'][0]); write_ids('out/ids_0000.ppm', r['owner'][0])
 
@@ -13,6 +13,7 @@ integer coverage: the same inputs give the same bits.  A triangle that crosses t
 (counts['crossing'] says how many)."""
 import numpy as np
 
+from . import camera
 from ._raster_sigs import DURF_RASTER_MAX_SIZE as MAX_SIZE, DURF_RASTER_RECORD_INTS as RECORD_INTS, DURF_RASTER_TILE as TILE
 
 COUNT_FIELDS = ('pairs', 'drawn', 'invalid', 'behind', 'crossing', 'range', 'degenerate', 'culled')
@@ -39,24 +40,16 @@ def default_frames_per_call(F, T, h, w, bound=WORKSPACE_BOUND):
 
 
 def _check(m, cams, znear, attrs, label, cull, per_call):
-    """every refusal of render_mesh, on the host, before anything touches the device -> (cams float32 [F,17], h, w, V, T)"""
+    """every refusal of render_mesh, on the host, before anything touches the device -> (cams float32 [F,CAM_FLOATS], h, w, V, T)"""
     entry = 'raster.render_mesh'
     if not isinstance(m, dict) or m.get('vertices') is None or m.get('triangles') is None:
         raise ValueError('%s: m is a dict with vertices [V,3] and triangles [T,3]' % entry)
     vs, ts = tuple(m['vertices'].shape), tuple(m['triangles'].shape)
     if len(vs) != 2 or vs[1] != 3 or len(ts) != 2 or ts[1] != 3:
         raise ValueError('%s: vertices of shape %s and triangles of shape %s, expected [V,3] and [T,3]' % (entry, vs, ts))
-    cams = np.ascontiguousarray(_host(cams), np.float32)
-    if cams.ndim == 1 and cams.size == 17:
-        cams = cams.reshape(1, 17)
-    if cams.ndim != 2 or cams.shape[1] != 17 or cams.shape[0] < 1:
-        raise ValueError('%s: cams of shape %s, expected [F,17] camera rows (trajectory.camera_rows)' % (entry, cams.shape))
+    cams, h, w = camera.as_rows(cams, entry)
     if not np.isfinite(cams).all():
         raise ValueError('%s: a camera row that is not finite' % entry)
-    hs, ws = np.unique(cams[:, 15]), np.unique(cams[:, 16])
-    if len(hs) != 1 or len(ws) != 1 or hs[0] != int(hs[0]) or ws[0] != int(ws[0]):
-        raise ValueError('%s: the cameras of one call share one frame size, got heights %s and widths %s' % (entry, hs.tolist(), ws.tolist()))
-    h, w = int(hs[0]), int(ws[0])
     if not (1 <= h <= MAX_SIZE and 1 <= w <= MAX_SIZE):
         raise ValueError('%s: frames of %d x %d, expected 1 .. %d each way' % (entry, h, w, MAX_SIZE))
     if vs[0] >= 2 ** 31 or ts[0] >= 2 ** 31:
@@ -80,7 +73,7 @@ def _check(m, cams, znear, attrs, label, cull, per_call):
 
 def render_mesh(m, cams, znear=1e-2, attrs=('rgb', 'normals'), label='owner', cull=0, frames_per_call=None):
     """The mesh m (mesh.surface / extract / read_ply / merge: dict vertices [V,3], triangles [T,3], host arrays are uploaded)
-    through the cameras cams [F,17] of one frame size -> dict depth [F,h,w] (camera depth, 0 where nothing covers), tri
+    through the cameras cams [F,CAM_FLOATS] of one frame size -> dict depth [F,h,w] (camera depth, 0 where nothing covers), tri
     [F,h,w] int32 (-1 there), mask [F,h,w] bool, bary [F,h,w,3], every key of `attrs` that m holds as [F,h,w,C] (float vertex
     attributes, perspective-correct; a uint8 colour counts as / 255; 0 where nothing covers), `label` as [F,h,w] int32 (the
     int attribute of the owning triangle's first vertex, -1 where nothing covers), counts (int64 [calls, 8] on the host:

@@ -2,7 +2,7 @@
 
 Mirrors what `obbpose_dataset.Waymo._generate_rays_multi` (obbpose_dataset.py:1868-1916) precomputes on the
 host for every pixel and `_next_train` (:1551-1587, batching == 'timestep') gathers per step: here the camera
-table stays on the host (17 floats per camera), the images / LIDAR depth / sky masks of a timestep stay
+table stays on the host (one row of camera.py per camera), the images / LIDAR depth / sky masks of a timestep stay
 resident in HBM, and each step's rays are generated for the sampled pixel indices only -- no per-step
 host gather, no H2D copy of rays."""
 import ctypes as C
@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, utils
+from . import _lib, camera, utils
 from .ops import _p, _stream
 
 
@@ -18,11 +18,7 @@ class TimestepData:
     """Device-resident data of one timestep: cameras (host table) + flattened images/depth/sky of its cameras."""
 
     def __init__(self, camtoworlds, focal, principal_point, h, w, images=None, depth=None, sky=None, device='cuda'):
-        n = len(h)
-        self.cams = np.zeros((n, 17), np.float32)
-        for i in range(n):
-            self.cams[i, :12] = np.asarray(camtoworlds[i], np.float32)[:3, :4].reshape(-1)
-            self.cams[i, 12:] = (focal[i], principal_point[i][0], principal_point[i][1], h[i], w[i])
+        self.cams = camera.rows(camtoworlds, focal, principal_point, h, w)
         self.n_rays = int(sum(int(a) * int(b) for a, b in zip(h, w)))
         flat = lambda xs, c: torch.cat([torch.as_tensor(np.asarray(x, np.float32)).reshape(-1, c) for x in xs]).to(device)
         self.images = flat(images, np.asarray(images[0]).shape[-1]) if images is not None else None
@@ -52,24 +48,18 @@ def generate_batch(ts_data, ray_indices, near, far):
     return utils.BoxRays(o, d, v, r, lm, nr, fr), px, dp, sk
 
 
-def camera_row(c2w, focal, principal_point, h, w):
-    """one camera as the 17 floats of durf_gen_batch's table: c2w [3,4] row-major, focal, principal point x / y, h, w"""
-    row = np.zeros(17, np.float32)
-    row[:12] = np.asarray(c2w, np.float32)[:3, :4].reshape(-1)
-    row[12:] = (focal, principal_point[0], principal_point[1], h, w)
-    return row
+camera_row = camera.row
 
 
 def camera_rays(cam17, near, far, device='cuda'):
     """-> BoxRays of [h, w, .] fields on the device for ONE camera row (camera_row): the pinhole generator of generate_batch
     through k_camera_rays (durf_camera_rays) -- bit-identical to generate_batch(ray_indices=None) on a one-camera timestep,
     with no TimestepData to build.  What render_image_one_call / render_layers take as `rays`."""
-    cam = np.ascontiguousarray(np.asarray(cam17, np.float32).reshape(17))
-    h, w = int(cam[15]), int(cam[16])
+    cam, h, w = camera.as_rows(cam17, 'raygen.camera_rays', frames=1)
     dev = torch.device(device)
     f = lambda c: torch.empty(h, w, c, device=dev)
     o, d, v, r, nr, fr = f(3), f(3), f(3), f(1), f(1), f(1)
-    _lib.check(_lib.lib().durf_camera_rays(_stream(), (C.c_float * 17)(*cam.tolist()), 0, h * w, float(near), float(far), _p(o),
+    _lib.check(_lib.lib().durf_camera_rays(_stream(), (C.c_float * camera.CAM_FLOATS)(*cam[0].tolist()), 0, h * w, float(near), float(far), _p(o),
                                            _p(d), _p(v), _p(r), _p(nr), _p(fr)), 'durf_camera_rays')
     return utils.BoxRays(o, d, v, r, torch.ones(h, w, 1, device=dev), nr, fr)
 

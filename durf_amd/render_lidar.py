@@ -20,6 +20,7 @@ import math
 import os
 import sys
 
+from . import camera
 from .render_traj import add_scene_arguments, open_scene, restore_model
 
 
@@ -60,7 +61,7 @@ def main(argv=None):
             pose_end = np.asarray(z['pose_end'], np.float64).reshape(-1, 3, 4) if 'pose_end' in z.files else None
             times = np.asarray(z['times'], np.float32).reshape(-1)
     else:
-        c2w = np.asarray(dataset.ts_data[0].cams[0, :12], np.float64).reshape(3, 4)
+        c2w = camera.c2w(dataset.ts_data[0].cams[0]).astype(np.float64)
         p0 = np.concatenate([c2w[:, :3] @ np.asarray(CAM_FROM_SENSOR), c2w[:, 3:]], 1)
         p1 = p0.copy()
         p1[:, :3] = p0[:, :3] @ lidar.rodrigues([0.0, 0.0, 0.1])

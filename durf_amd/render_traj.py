@@ -131,24 +131,12 @@ def write_flow(eval_dir, out, cams, ext, near, far, enable, chunk):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     import numpy as np
-    from . import trajectory
+    from . import camera, trajectory
     if not args.synthetic and (args.data_dir is None or args.train_dir is None or args.traj is None):
         raise SystemExit('render_traj: --data_dir, --train_dir and --traj are required (or --synthetic)')
     dev, config, dataset = open_scene(args)
-    if args.synthetic:
-        cam_rows = dataset.ts_data[0].cams
-        ext = dataset.ext
-        key_c2w = [dataset.ts_data[0].cams[0, :12].reshape(3, 4), dataset.ts_data[-1].cams[-1, :12].reshape(3, 4)]
-        key_t = [0.0, float(dataset.T - 1)]
-    else:
-        cam_rows = np.concatenate([np.asarray(dataset.camtoworlds, np.float32).reshape(-1, 12),
-                                   np.stack([dataset.focal, dataset.principal_point[:, 0], dataset.principal_point[:, 1],
-                                             dataset.h, dataset.w], -1).astype(np.float32)], -1)
-        ext = dataset.peek()['ext']             # ONE set of half extents for every frame (the first test image's timestep), as the
-                                                # notebook renders with timestep 1's: the boxes move between timesteps, they do not resize
-    if not 0 <= args.cam < len(cam_rows):
-        raise SystemExit('render_traj: --cam %d of %d cameras' % (args.cam, len(cam_rows)))
-    focal, ppx, ppy, h, w = [float(x) for x in cam_rows[args.cam][12:]]
+    cam_rows, ext, key_c2w, key_t = camera.scene_cameras(args, dataset, 'render_traj')
+    focal, ppx, ppy, h, w = camera.intrinsics(cam_rows[args.cam])
     model, variables, alpha = restore_model(args, config, dataset, dev)
     if args.traj is not None:
         c2w, times = trajectory.load_trajectory(args.traj)

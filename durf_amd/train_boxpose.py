@@ -15,6 +15,7 @@ from typing import Any
 
 import torch
 
+from . import camera
 from . import math as dmath
 from . import obbpose_model as om
 from . import ops
@@ -842,7 +843,7 @@ def evaluate_set(model, config, variables, dataset, alpha, chunk=8192, obj_mask=
         raise ValueError('obj_mask: %d planes for %d frames' % (len(obj_mask), F))
     groups = {}
     for f in range(F):
-        groups.setdefault((int(cams[f][15]), int(cams[f][16]), ts[f]), []).append(f)
+        groups.setdefault(camera.size(cams[f]) + (ts[f],), []).append(f)
     per_frame = torch.empty(F, ops.EVAL_FLOATS, device=dev)
     rgb8, pics = [None] * F, [None] * F
     rays = 0
@@ -1044,7 +1045,7 @@ class SyntheticTimestepDataset:
 
     def eval_set(self):
         """The scene as an evaluation set (datasets.Waymo.eval_set's layout): every camera of every timestep, timestep-major
-        -- next() draws one timestep at random and yields its first camera, frame ts * n_cams of this set -> dict(cams [F,17],
+        -- next() draws one timestep at random and yields its first camera, frame ts * n_cams of this set -> dict(cams [F,CAM_FLOATS],
         ts [F] ints, pixels / depth / sky lists of [H,W,.] views of the resident data, ext per frame, init).  No rays are made
         and the generator of next() is not advanced."""
         import numpy as np
@@ -1053,9 +1054,8 @@ class SyntheticTimestepDataset:
         cams, ts, pixels, depth, sky = [], [], [], [], []
         for t, td in enumerate(self.ts_data):
             for c in range(self.n_cams):
-                row = td.cams[c]
                 img = lambda x: x[c * n:(c + 1) * n].reshape(self.H, self.W, -1)
-                cams.append(raygen.camera_row(row[:12].reshape(3, 4), row[12], row[13:15], row[15], row[16]))
+                cams.append(td.cams[c].copy())
                 ts.append(t)
                 pixels.append(img(td.images))
                 depth.append(img(td.depth))

@@ -3,6 +3,8 @@ notebooks/durf_render_traj.ipynb, and binary PPM frames.  numpy only -- the rend
 (one library call for the whole list); this module prepares its `cams` / `times` and stores what it returns."""
 import numpy as np
 
+from . import camera
+
 
 def _quat_from_rot(R):
     """rotation matrix -> unit quaternion (w, x, y, z), the branch with the largest pivot (no division by a small number)"""
@@ -101,14 +103,7 @@ def load_trajectory(path):
     return c2w, times
 
 
-def camera_rows(c2w, focal, principal_point, h, w):
-    """[F,3,4] camera-to-world matrices with shared intrinsics -> the [F,17] float32 camera table render_trajectory takes
-    (raygen.camera_row per frame)"""
-    c2w = np.asarray(c2w, np.float32)
-    rows = np.zeros((c2w.shape[0], 17), np.float32)
-    rows[:, :12] = c2w[:, :3, :4].reshape(-1, 12)
-    rows[:, 12:] = (focal, principal_point[0], principal_point[1], h, w)
-    return rows
+camera_rows = camera.rows          # [F,3,4] camera-to-world matrices with shared intrinsics -> the table render_trajectory takes
 
 
 def write_ppm(path, rgb8):

@@ -15,6 +15,8 @@ moves through, from the pixels the instance map gives it.  The known artefact is
 false surface at the back of the truncation band where another camera sees free space."""
 import numpy as np
 
+from . import camera
+
 
 def _host(a):
     return a.detach().cpu().numpy() if hasattr(a, 'detach') else np.asarray(a)
@@ -63,8 +65,7 @@ def check_frames(cams, depth, acc=None, rgb=None, label=None, select=None, carve
                  max_weight=64.0, znear=1e-2, entry='tsdf.integrate'):
     """every refusal of integrate that needs no device, from shapes alone -> (F, h, w)"""
     cs, ds = tuple(cams.shape), tuple(depth.shape)
-    if len(cs) != 2 or cs[1] != 17:
-        raise ValueError('%s: cams of shape %s, expected [F,17] camera rows (trajectory.camera_rows)' % (entry, cs))
+    camera.check_shape(cs, entry)
     if len(ds) != 3 or ds[0] != cs[0]:
         raise ValueError('%s: depth of shape %s for %d cameras, expected [F,h,w]' % (entry, ds, cs[0]))
     F, h, w = ds
@@ -91,7 +92,7 @@ def check_frames(cams, depth, acc=None, rgb=None, label=None, select=None, carve
 
 def integrate(vol, cams, depth, acc=None, rgb=None, label=None, select=None, carve=False, xform=None, frame_weight=None, min_acc=0.5,
               max_weight=64.0, znear=1e-2):
-    """F frames into vol, IN PLACE, one launch (durf_tsdf_integrate; the header states the rule).  cams [F,17] camera rows; depth
+    """F frames into vol, IN PLACE, one launch (durf_tsdf_integrate; the header states the rule).  cams [F,CAM_FLOATS] camera rows; depth
     [F,h,w] camera depth (the renderer's `distance`, raster's depth; 0, NaN, inf and negative values are holes); acc [F,h,w]: a
     pixel below min_acc is no observation; rgb [F,h,w,3]; label int32 [F,h,w] with select: only pixels of that label are
     observations of this volume's surface -- with carve=True a pixel of another label whose depth lies beyond the voxel by at
@@ -177,7 +178,7 @@ def box_xforms(poses_fk6, k):
 def fuse_scene(model, variables, cams, times, ext, white_bkgd, alpha, origin, shape, step, trunc, obj_step=None, obj_trunc=None, pad=0.05,
                carve=False, near=None, far=None, chunk=8192, batch=8, min_acc=0.5, max_weight=64.0, znear=1e-2, min_weight=1.0,
                min_points=0, largest=None, objects=True):
-    """The whole scene fused from rendered depth: cams [F,17] host camera rows and times [F] (render_trajectory's).  The poses
+    """The whole scene fused from rendered depth: cams [F,CAM_FLOATS] host camera rows and times [F] (render_trajectory's).  The poses
     [F,K,6] come from render_trajectory(outputs=()); per frame ONE render_layers call with layers=('instance', 'background') at
     ts = floor(t_f) and pose = poses[f].  The background volume (origin, shape, step, trunc) integrates bg_distance, bg_acc and
     bg_rgb: the street with every box switched off.  Object k's volume is mesh.object_lattice's lattice in the box's own frame
@@ -189,10 +190,10 @@ def fuse_scene(model, variables, cams, times, ext, white_bkgd, alpha, origin, sh
     background=, objects=[...])."""
     import torch
     from . import mesh, raygen
-    cams = np.ascontiguousarray(np.asarray(_host(cams), np.float32).reshape(-1, 17))
+    cams = camera.as_rows(cams, 'tsdf.fuse_scene', one_size=False)[0]
     times = [float(t) for t in np.asarray(_host(times), np.float64).reshape(-1)]
     F = cams.shape[0]
-    if F < 1 or len(times) != F:
+    if len(times) != F:
         raise ValueError('tsdf.fuse_scene: %d cameras and %d times' % (F, len(times)))
     if near is None or far is None:
         raise ValueError('tsdf.fuse_scene: near and far are the ray bounds of the render (config.near, config.far)')

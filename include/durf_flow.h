@@ -16,13 +16,12 @@ extern "C" {
 #endif
 
 /* ---- where a pixel goes (csrc/flow.hip k_flow_poses, k_flow_points) -------------------------------------------------------
- * n pixels [first, first + n) of source frame a, row-major in its w-wide image (w = cam_a_host[16]); pixel p = first + i is
+ * n pixels [first, first + n) of source frame a, row-major in its w-wide image (w = cam_a_host[DURF_CAM_W]); pixel p = first + i is
  * (x, y) = (p mod w, p div w).  origins_s, dirs_s [n,3] and hit [n,K] int32 are durf_ray_setup_masked's outputs for that
  * frame's rays at pose_a; t [n] is the renderer's `distance` and acc [n] its `acc`.  distance is sum_j w_j t_mid_j -- NOT
  * divided by acc -- measured along dirs_s, which on a ray that hit a box is the UNIT direction in that box's frame and
  * elsewhere the un-normalised world direction of the pixel (-z component 1 in the camera: t is then depth along the axis).
- * cam_a_host, cam_b_host: 17 HOST floats each in durf_camera_rays' layout (c2w [3,4] row-major: R_c[a][j] = cam[4 a + j],
- * o_c[a] = cam[4 a + 3]; focal = cam[12], ppx = cam[13], ppy = cam[14], h = cam[15], w = cam[16]).  pose_a, pose_b [K,6]
+ * cam_a_host, cam_b_host: one camera row of HOST floats each (durf_hip.h, THE CAMERA ROW).  pose_a, pose_b [K,6]
  * (centre, rotation vector) and ext [K,3] (half extents) on the device.  Per pixel:
  *   tt = normalise ? t / acc : t,   P_j = origins_s_j + tt dirs_s_j            (a point in the frame the ray was marched in)
  *   nh = the number of k with hit[k] != 0, k = the largest such
@@ -33,7 +32,7 @@ extern "C" {
  *             inside:  X_b = c_b + R_b^T P likewise, moving = k           (the point rides the box)
  *             else:    X_b = X_a (the same bits), moving = -1             (scenery seen through the box)
  *   nh >= 2:  invalid (the model's sum of several boxes' frames is no geometry anyone can reproject)
- *   camera c of a world point X (include/durf_overlay.h's convention): d = X - o_c, pc_j = (R_c[0][j] d_0 + R_c[1][j] d_1) +
+ *   camera c of a world point X, in csrc/camera.h's order: d = X - o_c, pc_j = (R_c[0][j] d_0 + R_c[1][j] d_1) +
  *     R_c[2][j] d_2, z = -pc_2, x' = ppx + (focal pc_0) / z, y' = ppy - (focal pc_1) / z
  *   target = (x', y', z_b) of X_b in camera b,  flow = (x' - (float) x, y' - (float) y),  zcam = z of X_a in camera a
  *   scene_flow = X_b - X_a (world frame; exactly 0 where nothing moved),  xyz = X_a
@@ -50,7 +49,7 @@ extern "C" {
 #define DURF_FLOW_POSE_FLOATS(K) (2 * (K) * 12)
 int durf_flow_points(void* stream, int n, int first, int K, const float* origins_s, const float* dirs_s,
                      const int32_t* hit /* nullable when K == 0 */, const float* t, const float* acc,
-                     const float* cam_a_host /* 17 */, const float* cam_b_host /* 17 */, const float* pose_a, const float* pose_b,
+                     const float* cam_a_host, const float* cam_b_host, const float* pose_a, const float* pose_b,
                      const float* ext, int normalise, float min_acc, float znear, float inside_tol, float* pose_scratch,
                      float* flow /* nullable */, float* scene_flow /* nullable */, float* xyz /* nullable */,
                      float* target /* nullable */, float* zcam /* nullable */, int32_t* moving /* nullable */,
@@ -104,7 +103,7 @@ int durf_flow_consistency(void* stream, int P, int m, int C, const float* warped
 int durf_flow_color(void* stream, int n, const float* flow, float max_mag, float* rgb /* nullable */, uint8_t* rgb8 /* nullable */);
 
 /* ---- P pairs of frames in one call -----------------------------------------------------------------------------------------
- * F frames of one size h x w (n = h w) seen from cams_host [F,17] with the boxes at poses [F,K,6] on the DEVICE
+ * F frames of one size h x w (n = h w) seen from cams_host [F,DURF_CAM_FLOATS] with the boxes at poses [F,K,6] on the DEVICE
  * (durf_render_trajectory's poses_out), their distance and acc planes [F,n] (durf_render_trajectory's), and P pairs
  * pairs_host [P,2] HOST ints (source frame, target frame; source == target is legal and is how a frame's own zcam is had).
  * Per pair and per chunk of `chunk` pixels (the last one the remainder): durf_camera_rays of the source camera, then
@@ -116,7 +115,7 @@ int durf_flow_color(void* stream, int n, const float* flow, float max_mag, float
  * without a device: F <= 0, P <= 0, a pair index outside [0, F), frames of different sizes, K > DURF_MAX_OBJ, znear <= 0,
  * inside_tol < 0, chunk <= 0, no output, a workspace smaller than that (both sizes named). */
 size_t durf_render_flow_workspace_bytes(int chunk, int K);
-int durf_render_flow(void* stream, int F, int K, const float* cams_host /* F x 17 */, const float* poses /* device [F,K,6] */,
+int durf_render_flow(void* stream, int F, int K, const float* cams_host /* F rows */, const float* poses /* device [F,K,6] */,
                      const float* ext, const int32_t* box_enable /* nullable */, const float* distance, const float* acc, int P,
                      const int* pairs_host /* P x 2 */, float near, float far, int chunk, int normalise, float min_acc,
                      float znear, float inside_tol, float* flow /* nullable */, float* scene_flow /* nullable */,

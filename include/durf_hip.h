@@ -524,13 +524,29 @@ int durf_render_layers(void* stream, const durf_forward_args* args, const int32_
  * The loop of the reference's notebooks/durf_render_traj.ipynb -- a list of (c2w, ts) pairs, rays built on the host and
  * render_image frame by frame -- with cameras and times in and frames out.
  *
- * durf_camera_rays: the six ray fields of pixels [first, first + count) of ONE camera row (17 host floats in
- * durf_gen_batch's layout: c2w [3,4] row-major, focal, principal point x / y, height, width), through the device function
- * durf_gen_batch's pinhole path runs: bit-identical to what durf_gen_batch writes for ray_idx = NULL on a one-camera
+ * THE CAMERA ROW.  Every entry point of this library and of its satellites (durf_overlay.h, durf_flow.h, durf_raster.h,
+ * durf_tsdf.h) takes a camera as one row of DURF_CAM_FLOATS floats:
+ *   cam[0 .. 11]  c2w [3,4] row-major: R_c[a][j] = cam[4 a + j] (camera axes as world columns), o[a] = cam[4 a + 3] (its centre)
+ *   cam[DURF_CAM_FOCAL]  the focal length in pixels;  cam[DURF_CAM_PPX], cam[DURF_CAM_PPY]  the principal point
+ *   cam[DURF_CAM_H], cam[DURF_CAM_W]  the picture's height and width, whole numbers held as floats
+ * The camera looks down its -z; picture y points down; pixel centres are at integer coordinates.  Pixel (x, y) has the ray
+ * direction sum_j cd_j R_c[:, j], cd = ((x - ppx) / focal, -(y - ppy) / focal, -1) (pinhole_ray), and a world point P is seen at
+ *   d = P - o;  pc_j = (R_c[0][j] d_0 + R_c[1][j] d_1) + R_c[2][j] d_2;  z = -pc_2;
+ *   x = ppx + (focal pc_0) / z;  y = ppy - (focal pc_1) / z
+ * in fp32, unfused, in that order: csrc/camera.h is the one place either formula is written, and z is the renderer's
+ * `distance` on a ray that hit no box. */
+#define DURF_CAM_FLOATS 17
+#define DURF_CAM_FOCAL 12
+#define DURF_CAM_PPX 13
+#define DURF_CAM_PPY 14
+#define DURF_CAM_H 15
+#define DURF_CAM_W 16
+/* durf_camera_rays: the six ray fields of pixels [first, first + count) of ONE camera row (host floats), through the device
+ * function durf_gen_batch's pinhole path runs: bit-identical to what durf_gen_batch writes for ray_idx = NULL on a one-camera
  * timestep.  origins / directions / viewdirs [count,3], radii / near_out / far_out [count]. */
-int durf_camera_rays(void* stream, const float* cams_host /* 17 */, int first, int count, float near, float far,
+int durf_camera_rays(void* stream, const float* cams_host /* DURF_CAM_FLOATS */, int first, int count, float near, float far,
                      float* origins, float* directions, float* viewdirs, float* radii, float* near_out, float* far_out);
-/* durf_render_trajectory: F frames; frame f is seen from camera row f of cams_host [F,17] (all of one height h and width w;
+/* durf_render_trajectory: F frames; frame f is seen from camera row f of cams_host [F,DURF_CAM_FLOATS] (all of one height h and width w;
  * n = h * w) at time times_host[f] in [0, T - 1].  `args` as for durf_render_image with the ray fields AND args->pose ignored:
  * the frame's rays are generated chunk by chunk into the workspace (no image-sized ray buffer exists), and its box poses are
  * interpolated on the device from box_centers [T,K,6] -- a DEVICE pointer, the head of the flat parameter buffer, so a
@@ -550,7 +566,7 @@ int durf_camera_rays(void* stream, const float* cams_host /* 17 */, int first, i
  * image and grows with F by the poses only (F * K * 24 bytes) -- checked before the first launch, both sizes named. */
 size_t durf_render_trajectory_workspace_bytes(int F, int chunk, int N, int K, int num_levels);
 int durf_render_trajectory(void* stream, const durf_forward_args* args, const int32_t* box_enable /* nullable */,
-                           const float* box_centers /* device [T,K,6] */, int T, int F, const float* cams_host /* F x 17 */,
+                           const float* box_centers /* device [T,K,6] */, int T, int F, const float* cams_host /* F rows */,
                            const float* times_host /* F */, float near, float far, int chunk, uint8_t* rgb8 /* nullable */,
                            float* rgb /* nullable */, float* distance /* nullable */, float* acc /* nullable */,
                            float* poses_out /* nullable */, void* workspace, size_t workspace_bytes);
@@ -875,7 +891,7 @@ int durf_weight_decay(void* stream, size_t n, const float* params, float* grad, 
 /* ---- callers / data either side of the hot path ---------------------------------
  * Rays of a 'timestep' batch generated on the device (obbpose_dataset.py:1868-1916 pinhole rays with
  * un-normalised directions and row-neighbour radii; :1551-1583 gather from the timestep's concatenated
- * cameras).  cams_host: n_cams x 17 HOST floats {camtoworld 3x4 row-major, focal, cx, cy, h, w};
+ * cameras).  cams_host: n_cams camera rows of HOST floats (THE CAMERA ROW, at durf_camera_rays);
  * ray_idx [B] device indices into the concatenation (NULL: 0..B-1); images [P,img_channels] / depth [P] /
  * sky [P] device arrays of the same concatenation (nullable, with their outputs). */
 int durf_gen_batch(void* stream, int B, int n_cams, const float* cams_host, const int32_t* ray_idx, float near,

@@ -13,12 +13,11 @@ extern "C" {
 
 /* ---- the scene's boxes on rendered frames (csrc/overlay.hip -> libdurf_overlay.so; by hand in the reference: notebooks/waymo_labels.ipynb
  * project_point / show_camera_image) ----------------------------------------------------------------
- * durf_project_boxes: the twelve edges of box k of frame f as the camera of row f of cams_dev ([F,17] DEVICE floats, the
- * layout of durf_gen_batch / durf_camera_rays, durf_hip.h) sees them.  World corner c in 0..7 (bit 0 / 1 / 2: the sign on the box's
+ * durf_project_boxes: the twelve edges of box k of frame f as the camera of row f of cams_dev ([F,DURF_CAM_FLOATS] DEVICE floats:
+ * durf_hip.h, THE CAMERA ROW) sees them.  World corner c in 0..7 (bit 0 / 1 / 2: the sign on the box's
  * x / y / z half extent, 0 = -, 1 = +): P_c = centre + R^T (s_c * ext[k]), (centre, rotvec) = poses[f,k], R = aa2matrix(rotvec)
  * the world->object matrix of the box test (durf_ray_setup, durf_hip.h).  Camera space pc = R_c^T (P - o), depth z = -pc_z; picture
- * x = ppx + focal pc_x / z, y = ppy - focal pc_y / z: the inverse of the ray generator (pixel centres at integer
- * coordinates).  Edge e = 4 axis + j joins the two corners that differ in bit `axis`, j counting the four such pairs by
+ * x = ppx + (focal pc_x) / z, y = ppy - (focal pc_y) / z, in csrc/camera.h's order: the inverse of the ray generator.  Edge e = 4 axis + j joins the two corners that differ in bit `axis`, j counting the four such pairs by
  * increasing corner index, from the corner with the bit clear to the corner with it set.  Edges are clipped in camera space
  * against z >= znear (znear > 0): both ends nearer -- the edge is culled, its four floats are NaN; one end nearer -- it is cut
  * at z = znear.
@@ -40,7 +39,7 @@ extern "C" {
  * nothing of the frames.  K == 0 with a label fills it with -1. */
 #define DURF_BOX_EDGES 12
 #define DURF_BOX_RECT_FLOATS 6
-int durf_project_boxes(void* stream, int F, int K, const float* cams_dev /* [F,17] device */, const float* poses /* [F,K,6] */,
+int durf_project_boxes(void* stream, int F, int K, const float* cams_dev /* [F,DURF_CAM_FLOATS] device */, const float* poses /* [F,K,6] */,
                        const float* ext /* [K,3] */, const int32_t* box_enable /* nullable */, float znear,
                        float* segments /* [F,K,12,4] */, float* rect /* [F,K,6] */);
 int durf_draw_boxes(void* stream, int F, int h, int w, int K, const float* segments /* [F,K,12,4] */,

@@ -8,10 +8,9 @@
  * in durf_last_error(), every argument checked before anything is launched, no stream synchronisation and no device-to-host
  * copy anywhere.  All float arithmetic is fp32, unfused, in the order written here, with IEEE division; coverage is integer.
  *
- * Inputs.  cams_dev [F,17] floats ON THE DEVICE: c2w [3,4] row-major (R_c = its 3 x 3 block, o = its last column), focal,
- *   ppx, ppy, height, width -- the frame size is the h and w of the call, shared by all F cameras; the last two floats of a
- *   row are not read.  vertices [V,3] float, triangles [T,3] int32.  A PAIR is a (frame f, triangle t).
- * Projection (durf_overlay.h's rule).  d = P - o;  pc_j = (R_c[0][j] d_0 + R_c[1][j] d_1) + R_c[2][j] d_2;  z = -pc_2;
+ * Inputs.  cams_dev [F,DURF_CAM_FLOATS] floats ON THE DEVICE (durf_hip.h, THE CAMERA ROW) -- the frame size is the h and w of
+ *   the call, shared by all F cameras; the last two floats of a row are not read.  vertices [V,3] float, triangles [T,3] int32.  A PAIR is a (frame f, triangle t).
+ * Projection (csrc/camera.h's order).  d = P - o;  pc_j = (R_c[0][j] d_0 + R_c[1][j] d_1) + R_c[2][j] d_2;  z = -pc_2;
  *   x = ppx + (focal pc_0) / z;  y = ppy - (focal pc_1) / z.  Pixel centres are at integer coordinates.
  * Cull.  A pair is counted once, under the first rule that applies, in this order:
  *   1 INVALID     a vertex id outside 0 .. V-1, a vertex coordinate that is not finite, or a pc_j that is not finite
@@ -89,7 +88,7 @@ size_t durf_raster_workspace_bytes(int F, int T, int h, int w);
  * Refused: the shape as above (every value named), V < 0, !(znear >= FLT_MIN) (znear > 0, and 1 / znear finite), cull outside
  * 0 .. 2, a NULL cams_dev with F > 0, NULL vertices with V > 0, NULL triangles with T > 0, a NULL counts or workspace, a workspace
  * not aligned to 256 bytes or smaller than durf_raster_workspace_bytes (both sizes named). */
-int durf_raster_setup(void* stream, int F, int h, int w, const float* cams_dev /* [F,17] device */, int V, int T,
+int durf_raster_setup(void* stream, int F, int h, int w, const float* cams_dev /* [F,DURF_CAM_FLOATS] device */, int V, int T,
                       const float* vertices /* [V,3] */, const int32_t* triangles /* [T,3] */, float znear, int cull, void* workspace,
                       size_t workspace_bytes, int32_t* counts /* [DURF_RASTER_COUNTS] */);
 

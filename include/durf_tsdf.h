@@ -17,9 +17,8 @@
  *   weight [n] float    W
  *   colour [n,4] float  NULLABLE: r, g, b and the colour's own weight Wc; ALIGNED TO 16 BYTES (a row is one 16-byte access)
  *
- * Integration.  cams_dev [F,17] floats ON THE DEVICE, the rows of durf_camera_rays as durf_raster.h reads them: c2w [3,4]
- *   row-major (R_c its 3 x 3 block, o its last column), focal, ppx, ppy; the last two floats of a row are not read, the frame
- *   size is the h and w of the call.  depth [F,h,w] float: camera depth.  acc [F,h,w] float NULLABLE.  rgb [F,h,w,3] float
+ * Integration.  cams_dev [F,DURF_CAM_FLOATS] floats ON THE DEVICE (durf_hip.h, THE CAMERA ROW), projected in csrc/camera.h's
+ *   order; the last two floats of a row are not read, the frame size is the h and w of the call.  depth [F,h,w] float: camera depth.  acc [F,h,w] float NULLABLE.  rgb [F,h,w,3] float
  *   NULLABLE.  label [F,h,w] int32 NULLABLE.  xform [F,3,4] float ON THE DEVICE, NULLABLE: M maps the volume's coordinates to
  *   frame f's world, X_c = ((M[c][0] P_0 + M[c][1] P_1) + M[c][2] P_2) + M[c][3]; NULL: X = P.  (A volume in a box's frame follows
  *   the box: X = c_f + R_f^T P.)  frame_weight [F] float ON THE DEVICE, NULLABLE: NULL means 1.
@@ -84,7 +83,7 @@ extern "C" {
  * colour not aligned to 16 bytes.  rgb without colour is allowed: the colour is simply not kept. */
 int durf_tsdf_integrate(void* stream, int nu, int nv, int nw, const float* origin_host /* 3 */, const float* du_host /* 3 */,
                         const float* dv_host /* 3 */, const float* dw_host /* 3 */, int F, int h, int w,
-                        const float* cams_dev /* [F,17] device */, const float* depth /* [F,h,w] */, const float* acc /* nullable */,
+                        const float* cams_dev /* [F,DURF_CAM_FLOATS] device */, const float* depth /* [F,h,w] */, const float* acc /* nullable */,
                         float min_acc, const float* rgb /* [F,h,w,3], nullable */, const int32_t* label /* nullable */, int select,
                         int other_mode, const float* xform /* [F,3,4] device, nullable */, const float* frame_weight /* [F], nullable */,
                         float trunc, float max_weight, float znear, float* tsdf /* [n] */, float* weight /* [n] */,

@@ -8,6 +8,9 @@ tests/test_flow_host.py -- a wall at a fixed depth in front of the camera and bo
 inside them, acc = 1 -- which stands in for the renderer where no GPU is to hand."""
 import numpy as np
 
+from tests import camera_ref
+from tests.camera_ref import row as camera_row  # noqa: F401
+
 F32, F64 = np.float32, np.float64
 POSE_ROW = 12
 CONS_SPAN = 4096
@@ -44,13 +47,10 @@ def _to_world(R, c, P):
 
 
 def project(cam, X, dt=F64):
-    """(x', y', z) of world points X [m,3] in camera row `cam` (17 floats), the overlay's convention"""
-    cam = _a(cam, dt)
+    """(x', y', z) of world points X [m,3] in camera row `cam` (camera_ref's projection)"""
     with np.errstate(all='ignore'):                # (a point at infinity: an invalid pixel's, replaced by NaN afterwards)
-        d = [X[:, 0] - cam[3], X[:, 1] - cam[7], X[:, 2] - cam[11]]
-        pc = [(cam[j] * d[0] + cam[4 + j] * d[1]) + cam[8 + j] * d[2] for j in range(3)]
-        z = -pc[2]
-        return cam[13] + (cam[12] * pc[0]) / z, cam[14] - (cam[12] * pc[1]) / z, z
+        xy, z = camera_ref.project(_a(cam, dt)[None], X[None], dt)
+    return xy[0, :, 0], xy[0, :, 1], z[0]
 
 
 # ---- (a) durf_flow_points ---------------------------------------------------------------------------------------------------
@@ -82,7 +82,7 @@ def points(origins_s, dirs_s, hit, t, acc, cam_a, cam_b, pose_a, pose_b, ext, fi
         Xb[h] = np.where(inside[:, None], B, A)
         moving[h] = np.where(inside, k, -1)
     cam_a32 = np.asarray(cam_a, F32)
-    w = int(cam_a32[16])
+    w = int(cam_a32[camera_ref.W])
     p = first + np.arange(n)
     x, y = (p % w).astype(dt), (p // w).astype(dt)
     xb, yb, zb = project(cam_b, Xb, dt)
@@ -176,18 +176,13 @@ def color(flow, max_mag, dt=F64, dimmed=None):
 
 
 # ---- an analytic scene for the closed-form checks -----------------------------------------------------------------------------
-def camera_row(c2w, focal, ppx, ppy, h, w):
-    return np.concatenate([np.asarray(c2w, F64).reshape(3, 4).reshape(-1), [focal, ppx, ppy, h, w]]).astype(F32)
-
-
 def camera_rays(cam):
-    """origins, directions [h w,3] float64 of a camera row: the pinhole rays of csrc/pinhole.h (direction's -z camera component 1)"""
+    """origins, directions [h w,3] float64 of a camera row: the pinhole rays of csrc/camera.h (direction's -z camera component 1)"""
     cam = np.asarray(cam, F32).astype(F64)
-    h, w = int(cam[15]), int(cam[16])
+    h, w = int(cam[camera_ref.H]), int(cam[camera_ref.W])
     y, x = np.divmod(np.arange(h * w), w)
-    cd = np.stack([(x - cam[13]) / cam[12], -(y - cam[14]) / cam[12], -np.ones(h * w)], 1)
-    R = cam[:12].reshape(3, 4)[:, :3]
-    return np.tile(cam[:12].reshape(3, 4)[:, 3], (h * w, 1)), cd @ R.T
+    o, d = camera_ref.rays(cam, x, y)
+    return np.tile(o, (h * w, 1)), d
 
 
 def ray_setup(origins, dirs, pose, ext):

@@ -2,7 +2,7 @@
 """Records tests/golden/gen_batch_rig0.npz: what raygen.generate_batch (durf_gen_batch) returns, bit for bit, on the seeded
 three-camera rig of tests/test_gpu_data.py -- the full images in order (ray_idx = None) and a random batch of 777 pixel
 indices.  Recorded ONCE on an MI355X from the commit BEFORE the pinhole body of k_gen_batch was factored out into
-csrc/pinhole.h (the device function k_camera_rays shares with it): tests/test_gpu_trajectory.py holds every later build
+csrc/pinhole.h (now csrc/camera.h; the device function k_camera_rays shares with it): tests/test_gpu_trajectory.py holds every later build
 to these bits, so "durf_gen_batch stays bit-identical" is checked against the old kernel and not against itself.
 
     python tests/golden/make_gen_batch_fixture.py [OUT.npz]        (needs the GPU; do not re-record to make a test pass)"""

@@ -4,6 +4,8 @@ cases the overlay tests share.  Every function takes the dtype it computes in: n
 makes on those inputs, and so the measure the device is held to."""
 import numpy as np
 
+from tests.camera_ref import FLOATS, project as project_points, row as camera_row, to_camera  # noqa: F401  (the oracle's camera)
+
 EDGES = 12
 
 
@@ -47,23 +49,6 @@ def world_corners(poses, ext, ft):
         for a in range(3):
             P[:, :, q, a] = poses[:, :, a] + ((R[:, :, 0, a] * v[0] + R[:, :, 1, a] * v[1]) + R[:, :, 2, a] * v[2])
     return P
-
-
-def to_camera(cams, P, ft):
-    """cams [F,17], P [F,...,3] -> pc [F,...,3] = R_c^T (P - o)"""
-    cams, P = np.asarray(cams, ft), np.asarray(P, ft)
-    c = cams.reshape((cams.shape[0],) + (1,) * (P.ndim - 2) + (17,))
-    d0, d1, d2 = P[..., 0] - c[..., 3], P[..., 1] - c[..., 7], P[..., 2] - c[..., 11]
-    return np.stack([(c[..., j] * d0 + c[..., 4 + j] * d1) + c[..., 8 + j] * d2 for j in range(3)], -1)
-
-
-def project_points(cams, P, ft):
-    """picture coordinates [F,...,2] and camera depth [F,...] of world points (no clipping)"""
-    cams = np.asarray(cams, ft)
-    pc = to_camera(cams, P, ft)
-    c = cams.reshape((cams.shape[0],) + (1,) * (pc.ndim - 2) + (17,))
-    z = -pc[..., 2]
-    return np.stack([c[..., 13] + (c[..., 12] * pc[..., 0]) / z, c[..., 14] - (c[..., 12] * pc[..., 1]) / z], -1), z
 
 
 def project_boxes(cams, poses, ext, box_enable, znear, ft):
@@ -175,13 +160,6 @@ def look_at(eye, target, up=(0.0, 0.0, 1.0)):
     return np.concatenate([np.stack([right, true_up, -fwd], 1), eye[:, None]], 1)
 
 
-def camera_row(c2w, focal, ppx, ppy, h, w):
-    row = np.zeros(17, np.float32)
-    row[:12] = np.asarray(c2w, np.float32).reshape(-1)
-    row[12:] = (focal, ppx, ppy, h, w)
-    return row
-
-
 SPECIAL = ('zero_rot', 'near_pi', 'straddle', 'behind', 'offscreen', 'edge_on', 'disabled')
 
 
@@ -192,7 +170,7 @@ def make_case(F, h, w, K, seed):
     rng = np.random.default_rng(seed)
     focal = 0.9 * w
     ppx, ppy = (w - 1) / 2.0 + 0.25, (h - 1) / 2.0 - 0.25
-    cams = np.zeros((F, 17), np.float32)
+    cams = np.zeros((F, FLOATS), np.float32)
     for f in range(F):
         eye = np.zeros(3) if f == 0 else rng.uniform(-0.3, 0.3, 3)
         target = np.array([6.0, 0.0, 0.0]) if f == 0 else np.array([6.0, 0.0, 0.0]) + rng.uniform(-0.5, 0.5, 3)

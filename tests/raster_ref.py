@@ -9,6 +9,9 @@
 Scenes shared by the host and the device tests: camera(), random_scene(), fan() and grid() (tilings of a rectangle)."""
 import numpy as np
 
+from tests import camera_ref
+from tests.camera_ref import look_at  # noqa: F401
+
 SUB = 256
 MAX_COORD = 1 << 29
 TILE = 16
@@ -17,53 +20,34 @@ F32 = np.float32
 
 
 def camera(h, w, focal, c2w=None, pp=None):
-    """one row of the [F,17] camera table: c2w [3,4] row-major, focal, ppx, ppy, h, w (identity pose: looking down -z, y up)"""
-    row = np.zeros(17, np.float32)
-    row[:12] = (np.eye(4)[:3] if c2w is None else np.asarray(c2w, np.float64)[:3, :4]).reshape(12)
-    row[12] = focal
-    row[13], row[14] = ((w - 1) / 2.0, (h - 1) / 2.0) if pp is None else pp
-    row[15], row[16] = h, w
-    return row
-
-
-def look_at(eye, target, up=(0.0, 1.0, 0.0)):
-    """c2w [3,4] of a camera at `eye` looking at `target` (camera -z is the view direction)"""
-    eye, target, up = (np.asarray(a, np.float64) for a in (eye, target, up))
-    zc = eye - target
-    zc /= np.linalg.norm(zc)
-    xc = np.cross(up, zc)
-    xc /= np.linalg.norm(xc)
-    yc = np.cross(zc, xc)
-    return np.concatenate([np.stack([xc, yc, zc], 1), eye[:, None]], 1)
+    """one camera row (identity pose: looking down -z, y up; the principal point at the picture's centre)"""
+    ppx, ppy = ((w - 1) / 2.0, (h - 1) / 2.0) if pp is None else pp
+    return camera_ref.row(np.eye(4) if c2w is None else c2w, focal, ppx, ppy, h, w)
 
 
 def _setup(cam, vertices, triangles, znear, cull, dtype):
     """project, cull, snap: rules 1-6 of the header for one camera -> why [T] (1 drawn, 2 .. 7 the culls), X, Y int64 [T,3]
     (float32 route whatever `dtype`: the snap is part of the definition), z [T,3] in `dtype`"""
-    cam = np.asarray(cam, np.float32).reshape(17)
+    cam = np.asarray(cam, np.float32).reshape(1, -1)
     vertices = np.asarray(vertices, np.float32).reshape(-1, 3)
     tri = np.asarray(triangles, np.int64).reshape(-1, 3)
     V, T = vertices.shape[0], tri.shape[0]
     ok_id = ((tri >= 0) & (tri < V)).all(1) if T else np.zeros(0, bool)
     P32 = vertices[np.clip(tri, 0, max(V - 1, 0))] if V else np.zeros((T, 3, 3), np.float32)
-
-    def project(P, c):
-        d0, d1, d2 = P[..., 0] - c[3], P[..., 1] - c[7], P[..., 2] - c[11]
-        return [(c[j] * d0 + c[4 + j] * d1) + c[8 + j] * d2 for j in range(3)]
     with np.errstate(all='ignore'):
-        pc = project(P32, cam)
-        finite = np.isfinite(P32).all(2) & np.isfinite(pc[0]) & np.isfinite(pc[1]) & np.isfinite(pc[2])
+        pc = camera_ref.to_camera(cam, P32[None], np.float32)
+        finite = np.isfinite(P32).all(2) & np.isfinite(pc[0]).all(2)
         valid = ok_id & finite.all(1)
-        z = -pc[2]
-        x = cam[13] + (cam[12] * pc[0]) / z
-        y = cam[14] - (cam[12] * pc[1]) / z
+        z = -pc[0, ..., 2]
+        xy = camera_ref.pixel(cam, pc, z[None], np.float32)[0]
+        x, y = xy[..., 0], xy[..., 1]
         near = (z < F32(znear)).sum(1)
         sx, sy = F32(SUB) * x, F32(SUB) * y
         rng = (~(np.abs(sx) <= F32(MAX_COORD)) | ~(np.abs(sy) <= F32(MAX_COORD))).any(1)
         snap = valid[:, None] & ~rng[:, None] & np.isfinite(sx) & np.isfinite(sy)
         X = np.where(snap, np.rint(np.where(snap, sx, 0)), 0).astype(np.int64)
         Y = np.where(snap, np.rint(np.where(snap, sy, 0)), 0).astype(np.int64)
-        z_out = z if dtype == np.float32 else -project(P32.astype(np.float64), cam.astype(np.float64))[2]
+        z_out = z if dtype == np.float32 else -camera_ref.to_camera(cam, P32[None], np.float64)[0, ..., 2]
     A2 = (X[:, 1] - X[:, 0]) * (Y[:, 2] - Y[:, 0]) - (Y[:, 1] - Y[:, 0]) * (X[:, 2] - X[:, 0])
     why = np.full(T, 1)
     why[(cull == 1) & (A2 > 0) | (cull == 2) & (A2 < 0)] = 7
@@ -98,7 +82,7 @@ def _coverage(X, Y, A2, x0, x1, y0, y1):
 
 
 def _draw(cams, h, w, vertices, triangles, znear, cull, dtype):
-    cams = np.asarray(cams, np.float32).reshape(-1, 17)
+    cams = np.asarray(cams, np.float32).reshape(-1, camera_ref.FLOATS)
     triangles = np.asarray(triangles, np.int64).reshape(-1, 3)
     F, T = cams.shape[0], triangles.shape[0]
     tri = np.full((F, h, w), -1, np.int32)
@@ -167,7 +151,7 @@ def draw64(cams, h, w, vertices, triangles, znear, cull=0):
 def gamma(cams, vertices, triangles):
     """max over frames and referenced vertices with z > 0 of sum_j |R_c[j][2] d_j| / z in float64: how much the projection's
     cancellation magnifies its roundings in z"""
-    cams = np.asarray(cams, np.float64).reshape(-1, 17)
+    cams = np.asarray(cams, np.float64).reshape(-1, camera_ref.FLOATS)
     P = np.asarray(vertices, np.float64)[np.unique(np.asarray(triangles).reshape(-1))]
     g = 0.0
     for c in cams:
@@ -182,7 +166,7 @@ def gamma(cams, vertices, triangles):
 # ---- scenes ----------------------------------------------------------------------------------------------------------------------
 def random_scene(seed=0, n=2000, stacked=600, h=48, w=64):
     """n small random triangles in front of three cameras of h x w, `stacked` of them over the pixels of tile (1, 1) of the first
-    camera at different depths -> (cams [3,17], vertices [3n,3], triangles [n,3])"""
+    camera at different depths -> (cams: 3 rows, vertices [3n,3], triangles [n,3])"""
     rng = np.random.default_rng(seed)
     focal = 64.0
     cams = np.stack([camera(h, w, focal),
@@ -231,4 +215,5 @@ def to_world(cam, pts, z):
     cam = np.asarray(cam, np.float64)
     pts = np.asarray(pts, np.float64)
     z = np.broadcast_to(np.asarray(z, np.float64), pts.shape[:1])
-    return np.stack([(pts[:, 0] - cam[13]) / cam[12] * z + cam[3], -(pts[:, 1] - cam[14]) / cam[12] * z + cam[7], -z + cam[11]], 1).astype(np.float32)
+    focal, ppx, ppy = cam[camera_ref.FOCAL], cam[camera_ref.PPX], cam[camera_ref.PPY]
+    return np.stack([(pts[:, 0] - ppx) / focal * z + cam[3], -(pts[:, 1] - ppy) / focal * z + cam[7], -z + cam[11]], 1).astype(np.float32)

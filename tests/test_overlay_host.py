@@ -12,33 +12,6 @@ from tests import overlay_ref as O
 F64 = np.float64
 
 
-def pinhole_ray(cam, x, y):
-    """csrc/pinhole.h in float64: origin and (un-normalised) direction of pixel (x, y)"""
-    cd = np.array([(x - cam[13]) / cam[12], -(y - cam[14]) / cam[12], -1.0])
-    Rm = cam[:12].reshape(3, 4)
-    return Rm[:, 3].copy(), Rm[:, :3] @ cd
-
-
-def random_camera(rng, h=48, w=64):
-    eye = rng.uniform(-2, 2, 3)
-    c2w = O.look_at(eye, eye + rng.normal(size=3), up=rng.normal(size=3))
-    # (a float64 row: rounded to fp32 the rotation block is orthonormal to 1e-7 only, and its transpose no inverse to 1e-9)
-    return np.concatenate([c2w.reshape(-1), [rng.uniform(30, 90), rng.uniform(20, 40), rng.uniform(15, 30), h, w]])
-
-
-def test_projection_inverts_the_ray_generator():
-    rng = np.random.default_rng(0)
-    for _ in range(20):
-        cam = random_camera(rng)
-        for _ in range(10):
-            x, y = float(rng.integers(0, 64)), float(rng.integers(0, 48))
-            o, d = pinhole_ray(cam, x, y)
-            t = rng.uniform(0.1, 30.0)
-            xy, z = O.project_points(cam[None], (o + t * d)[None], F64)
-            assert abs(xy[0, 0] - x) < 1e-9 and abs(xy[0, 1] - y) < 1e-9, (xy, x, y)
-            assert abs(z[0] - t) < 1e-9              # the camera-space direction has z = -1: depth is t
-
-
 def test_corners_satisfy_the_oracles_box_test():
     rng = np.random.default_rng(1)
     K = 5

@@ -147,17 +147,6 @@ def test_write_ppm_bytes(tmp_path):
         trajectory.write_ppm(path, img.astype(np.float32))
 
 
-def test_camera_rows_layout():
-    from durf_amd import raygen
-    keys, _ = _keys(5, 2)
-    rows = trajectory.camera_rows(keys, 51.5, (17.25, 11.5), 24, 32)
-    assert rows.shape == (2, 17) and rows.dtype == np.float32
-    for i in range(2):
-        assert np.array_equal(rows[i], raygen.camera_row(keys[i], 51.5, (17.25, 11.5), 24, 32))
-    td = raygen.TimestepData(keys, [51.5] * 2, [(17.25, 11.5)] * 2, [24] * 2, [32] * 2, device='cpu')
-    assert np.array_equal(rows, td.cams), 'the table durf_gen_batch takes'
-
-
 # ---- the surface ----------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_bound_and_exported():
     hdr = open(os.path.join(ROOT, 'include', 'durf_hip.h')).read()

@@ -12,6 +12,8 @@ Scenes shared by the host and the device tests: ring_cameras(), sphere_depth() (
 depth), holes(), random_extras() and random_scene()."""
 import numpy as np
 
+from tests import camera_ref
+
 from tests.raster_ref import camera, look_at  # noqa: F401  (the camera rows are the rasteriser's)
 
 F32 = np.float32
@@ -41,7 +43,7 @@ def voxels(frame, shape, dtype):
 
 def _integrate(dtype, state, frame, shape, cams, depth, trunc, acc, min_acc, rgb, label, select, other_mode, xform, frame_weight,
                max_weight, znear, margins):
-    cams = np.asarray(cams, F32).reshape(-1, 17)
+    cams = np.asarray(cams, F32).reshape(-1, camera_ref.FLOATS)
     depth = np.asarray(depth, F32)
     F, h, w = depth.shape
     T = dtype
@@ -61,8 +63,8 @@ def _integrate(dtype, state, frame, shape, cams, depth, trunc, acc, min_acc, rgb
                 X = np.stack([((M[r, 0] * P[:, 0] + M[r, 1] * P[:, 1]) + M[r, 2] * P[:, 2]) + M[r, 3] for r in range(3)], 1)
             else:
                 X = P
-            d0, d1, d2 = X[:, 0] - c[3], X[:, 1] - c[7], X[:, 2] - c[11]
-            pc = [(c[j] * d0 + c[4 + j] * d1) + c[8 + j] * d2 for j in range(3)]
+            pcs = camera_ref.to_camera(c[None], X[None], T)
+            pc = [pcs[0, :, j] for j in range(3)]
             y_ = np.zeros(n, np.int8)                                        # the rule that stopped the pair; 0: none yet
             live = np.ones(n, bool)
 
@@ -76,8 +78,7 @@ def _integrate(dtype, state, frame, shape, cams, depth, trunc, acc, min_acc, rgb
             if margins:
                 margin[f, live, 2] = np.abs(z - zn)[live]
             stop(~(z >= zn), 2)
-            x = c[13] + (c[12] * pc[0]) / z
-            y = c[14] - (c[12] * pc[1]) / z
+            x, y = np.moveaxis(camera_ref.pixel(c[None], pcs, z[None], T)[0], -1, 0)
             stop(~(np.abs(x) <= T(MAX_COORD)) | ~(np.abs(y) <= T(MAX_COORD)), 3)
             xs, ys = np.where(live, x, T(0)), np.where(live, y, T(0))
             if margins:
@@ -191,7 +192,7 @@ def sample32(state, frame, shape, trunc, points, min_weight=1.0):
 
 # ---- scenes ---------------------------------------------------------------------------------------------------------------------
 def ring_cameras(F, h, w, focal, radius=4.0, height=1.0, target=(0.0, 0.0, 0.0), phase=0.1):
-    """F cameras on a ring around `target`, looking at it -> [F,17]"""
+    """F cameras on a ring around `target`, looking at it -> [F] camera rows"""
     rows = []
     for f in range(F):
         a = phase + 2.0 * np.pi * f / F
@@ -204,14 +205,12 @@ def sphere_depth(cams, h, w, radius=1.0, centre=(0.0, 0.0, 0.0), plane=True):
     """the analytic camera depth [F,h,w] float32 of a sphere standing on the plane y = centre_y - radius (0 where a ray meets
     neither).  The rays are durf_camera_rays': direction ((px - ppx) / focal, -(py - ppy) / focal, -1) in the camera, so the
     ray parameter IS the camera depth."""
-    cams = np.asarray(cams, np.float64).reshape(-1, 17)
+    cams = np.asarray(cams, np.float64).reshape(-1, camera_ref.FLOATS)
     ctr = np.asarray(centre, np.float64)
     out = np.zeros((cams.shape[0], h, w))
     py, px = np.mgrid[0:h, 0:w].astype(np.float64)
     for f, c in enumerate(cams):
-        R, o = c[:12].reshape(3, 4)[:, :3], c[:12].reshape(3, 4)[:, 3]
-        dc = np.stack([(px - c[13]) / c[12], -(py - c[14]) / c[12], -np.ones_like(px)], -1)
-        d = dc @ R.T
+        o, d = camera_ref.rays(c, px, py)
         oc = o - ctr
         A, B, C = (d * d).sum(-1), 2.0 * (d @ oc), oc @ oc - radius * radius
         disc = B * B - 4.0 * A * C
@@ -266,7 +265,7 @@ def random_scene(seed, F=6, h=48, w=64, shape=(14, 12, 13), step=0.25, focal=52.
 
 
 def six_cameras(h, w, focal, dist, target=(0.0, 0.0, 0.0)):
-    """one camera on each half axis at `dist`, looking at `target` -> [6,17]"""
+    """one camera on each half axis at `dist`, looking at `target` -> 6 camera rows"""
     rows = []
     for ax in range(3):
         for s in (1.0, -1.0):

@@ -33,7 +33,7 @@ def main():
     import numpy as np
     import torch
     import bench
-    from durf_amd import raygen, synthetic, trajectory
+    from durf_amd import camera, raygen, synthetic, trajectory
     dev = torch.device('cuda', 0)
     torch.cuda.set_device(dev)
     w = bench.setup_workload('cfg3', dev)
@@ -49,9 +49,9 @@ def main():
     keys[1, :, 3] = [0.3, 0.0, 0.0]
     c2w, _ = trajectory.make_trajectory(keys, [0.0, 1.0], F)
     times = [(0.5 * f) % (lay.T - 1.0) if lay.T > 1 else 0.0 for f in range(F)]      # every second one fractional
-    cams = trajectory.camera_rows(c2w, 515.0, (W / 2.0, H / 2.0), H, W)          # synthetic.make_batch's camera
+    cams = camera.rows(c2w, 515.0, (W / 2.0, H / 2.0), H, W)          # synthetic.make_batch's camera
     near, far, alpha, white = 0.0, float(w['far']), w['alpha'], config.white_bkgd
-    tables = [raygen.TimestepData([c[:12].reshape(3, 4)], [c[12]], [(c[13], c[14])], [H], [W], device=dev) for c in cams]
+    tables = [raygen.TimestepData([camera.c2w(c)], [515.0], [(W / 2.0, H / 2.0)], [H], [W], device=dev) for c in cams]
     poses = model.render_trajectory(variables, cams, times, ext, white, alpha, near=near, far=far, chunk=args.chunk, outputs=())['poses']
 
     def loop():                                   # A: what a user had before

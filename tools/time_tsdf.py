@@ -34,6 +34,7 @@ def torch_integrate(vol, P, cams, depth, acc, rgb, min_acc=0.5, max_weight=64.0,
     """include/durf_tsdf.h's rule without label, xform and frame weights, one frame at a time over all voxels P [n,3], every
     operation written out in the header's order (no matrix product: its order of summation is the library's own)"""
     import torch
+    from durf_amd import ops
     D, W, C = vol['tsdf'].reshape(-1), vol['weight'].reshape(-1), vol['colour'].reshape(-1, 4)
     F, h, w = depth.shape
     trunc = vol['trunc']
@@ -42,7 +43,7 @@ def torch_integrate(vol, P, cams, depth, acc, rgb, min_acc=0.5, max_weight=64.0,
         d0, d1, d2 = P[:, 0] - c[3], P[:, 1] - c[7], P[:, 2] - c[11]
         pc = [(c[j] * d0 + c[4 + j] * d1) + c[8 + j] * d2 for j in range(3)]
         z = -pc[2]
-        x, y = c[13] + (c[12] * pc[0]) / z, c[14] - (c[12] * pc[1]) / z
+        x, y = c[ops.CAM_PPX] + (c[ops.CAM_FOCAL] * pc[0]) / z, c[ops.CAM_PPY] - (c[ops.CAM_FOCAL] * pc[1]) / z
         px, py = torch.round(x), torch.round(y)                              # ties to even, as rintf
         ok = torch.isfinite(pc[0]) & torch.isfinite(pc[1]) & torch.isfinite(pc[2]) & (z >= znear) & (x.abs() <= 2 ** 20) & (y.abs() <= 2 ** 20)
         ok &= (px >= 0) & (px < w) & (py >= 0) & (py < h)
