@@ -1,0 +1,523 @@
+// The nearest triangle of a mesh along arbitrary rays (include/durf_cast.h; libdurf_cast.so): Morton keys, an implicit complete
+// binary tree of boxes over the caller's sorted order built level by level, and a per-ray walk with a short stack in LDS.  The
+// header defines the result as a minimum over all triangles and proves that no tree can change it; the kernels follow it.  No
+// atomics, nothing synchronises or copies to the host, no workgroup waits for another.
+#include <climits>
+#include "workspace.h"
+#include "camera.h"
+#include "../../include/durf_cast.h"
+
+#define CB DURF_CAST_BLOCK
+#define CLEAF DURF_CAST_LEAF
+#define CREC DURF_CAST_RECORD_FLOATS
+#define CNODE DURF_CAST_NODE_FLOATS
+#define CSTACK DURF_CAST_STACK
+static_assert(CB == 256 && CLEAF == 4 && CREC == 10 && CNODE == 8 && CSTACK == 32 && DURF_CAST_TOP == CB, "the layouts the header states");
+static_assert(DURF_CAST_KEY_BITS == 21, "three axes in 63 bits");
+
+// the implicit tree of T triangles: n(k) nodes on level k (0: the leaves), stored from node off[k]; the root is level K
+struct CastTree {
+    int T, K, n0;
+    int off[CSTACK];
+    int nodes;                         // off[K] + 1, 0 for T == 0
+    __host__ __device__ int n(int k) const { return (int)(((long long)n0 + ((1ll << k) - 1)) >> k); }      // ceil halved k times
+};
+
+// the level offsets in LDS, where a thread indexes them by its own level (a by-value argument indexed so would go to scratch)
+__device__ __forceinline__ void cast_offsets_to_lds(const CastTree& R, int* s_off) {
+    if (threadIdx.x < CSTACK) s_off[threadIdx.x] = R.off[threadIdx.x];
+    __syncthreads();
+}
+
+struct CastBox { float lo[3], hi[3]; };
+
+__device__ __forceinline__ CastBox cast_empty_box() {
+    const float inf = __builtin_inff();
+    return CastBox{{inf, inf, inf}, {-inf, -inf, -inf}};
+}
+
+__device__ __forceinline__ CastBox cast_load_box(const float* nodes, int i) {
+    const float4 a = *(const float4*)(nodes + (size_t)i * CNODE), b = *(const float4*)(nodes + (size_t)i * CNODE + 4);
+    return CastBox{{a.x, a.y, a.z}, {b.x, b.y, b.z}};
+}
+
+__device__ __forceinline__ void cast_store_box(float* nodes, int i, const CastBox& B) {
+    *(float4*)(nodes + (size_t)i * CNODE) = make_float4(B.lo[0], B.lo[1], B.lo[2], 0.0f);
+    *(float4*)(nodes + (size_t)i * CNODE + 4) = make_float4(B.hi[0], B.hi[1], B.hi[2], 0.0f);
+}
+
+__device__ __forceinline__ void cast_union(CastBox& B, const CastBox& C) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        B.lo[a] = fminf(B.lo[a], C.lo[a]);
+        B.hi[a] = fmaxf(B.hi[a], C.hi[a]);
+    }
+}
+
+// the box of a triangle: min and max per axis, one ulp outward
+__device__ __forceinline__ CastBox cast_tri_box(const float* A, const float* B, const float* C) {
+    CastBox X;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        X.lo[a] = nextafterf(fminf(fminf(A[a], B[a]), C[a]), -__builtin_inff());
+        X.hi[a] = nextafterf(fmaxf(fmaxf(A[a], B[a]), C[a]), __builtin_inff());
+    }
+    return X;
+}
+
+// a valid triangle's vertices; false for an id outside 0 .. T-1, an index outside 0 .. V-1 or a coordinate that is not finite
+__device__ __forceinline__ bool cast_fetch(int id, int V, int T, const float* __restrict__ vertices, const int32_t* __restrict__ triangles,
+                                           float* P /* [9] */) {
+    if (id < 0 || id >= T) return false;
+    bool ok = true;
+    int v[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        v[c] = triangles[(size_t)id * 3 + c];
+        ok = ok && v[c] >= 0 && v[c] < V;
+    }
+    if (!ok) return false;
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            P[3 * c + a] = vertices[(size_t)v[c] * 3 + a];
+            ok = ok && cam_finite(P[3 * c + a]);
+        }
+    return ok;
+}
+
+// ---- keys ---------------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(CB)
+k_cast_keys(int V, int T, const float* __restrict__ vertices, const int32_t* __restrict__ triangles, const float* __restrict__ bounds,
+            long long* __restrict__ keys) {
+    const int i = blockIdx.x * CB + threadIdx.x;
+    if (i >= T) return;
+    float P[9];
+    if (!cast_fetch(i, V, T, vertices, triangles, P)) {
+        keys[i] = LLONG_MAX;
+        return;
+    }
+    unsigned long long key = 0;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const float lo = bounds[a], ext = bounds[3 + a] - lo;
+        const float c = ((P[a] + P[3 + a]) + P[6 + a]) / 3.0f;
+        const float x = ((c - lo) / ext) * 2097152.0f;
+        const unsigned g = (!(ext > 0.0f) || !(x >= 0.0f)) ? 0u : x >= 2097151.0f ? 2097151u : (unsigned)(int)x;
+        for (int b = 0; b < DURF_CAST_KEY_BITS; b++) key |= (unsigned long long)(g >> b & 1u) << (3 * b + (2 - a));
+    }
+    keys[i] = (long long)key;
+}
+
+// ---- build --------------------------------------------------------------------------------------------------------------------------
+// one thread per leaf: its records and its box
+__global__ void __launch_bounds__(CB)
+k_cast_leaves(int V, int T, int n0, const float* __restrict__ vertices, const int32_t* __restrict__ triangles,
+              const int32_t* __restrict__ order, float* __restrict__ records, float* __restrict__ nodes) {
+    const int l = blockIdx.x * CB + threadIdx.x;
+    if (l >= n0) return;
+    CastBox B = cast_empty_box();
+#pragma unroll
+    for (int j = 0; j < CLEAF; j++) {
+        const size_t s = (size_t)l * CLEAF + j;
+        float P[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        int id = s < (size_t)T ? order[s] : -1;
+        if (cast_fetch(id, V, T, vertices, triangles, P)) {
+            cast_union(B, cast_tri_box(P, P + 3, P + 6));
+        } else {
+            id = -1;
+#pragma unroll
+            for (int c = 0; c < 9; c++) P[c] = 0.0f;
+        }
+        float* r = records + s * CREC;
+#pragma unroll
+        for (int c = 0; c < 9; c++) r[c] = P[c];
+        r[9] = __int_as_float(id);
+    }
+    cast_store_box(nodes, l, B);
+}
+
+// one thread per node of a level: the union of its two children on the level below (a missing sibling is empty)
+__global__ void __launch_bounds__(CB)
+k_cast_level(int n_below, int off_below, int n_here, int off_here, float* nodes) {
+    const int j = blockIdx.x * CB + threadIdx.x;
+    if (j >= n_here) return;
+    CastBox B = cast_load_box(nodes, off_below + 2 * j);
+    if (2 * j + 1 < n_below) cast_union(B, cast_load_box(nodes, off_below + 2 * j + 1));
+    cast_store_box(nodes, off_here + j, B);
+}
+
+// one workgroup: every level from `first` (whose level below has at most 2 DURF_CAST_TOP nodes) up to the root
+__global__ void __launch_bounds__(CB)
+k_cast_top(const CastTree R, int first, float* nodes) {
+    for (int k = first; k <= R.K; k++) {                                     // (uniform; at most DURF_CAST_STACK levels)
+        const int j = threadIdx.x;
+        if (j < R.n(k)) {
+            CastBox B = cast_load_box(nodes, R.off[k - 1] + 2 * j);
+            if (2 * j + 1 < R.n(k - 1)) cast_union(B, cast_load_box(nodes, R.off[k - 1] + 2 * j + 1));
+            cast_store_box(nodes, R.off[k] + j, B);
+        }
+        __threadfence_block();
+        __syncthreads();                                                     // the next level reads what this one wrote
+    }
+}
+
+// ---- the walk -----------------------------------------------------------------------------------------------------------------------
+struct CastRay {
+    float o[3], d[3], inv[3];
+    bool zero[3];
+    float tmin, tmax;
+};
+
+// false for an unusable ray
+__device__ __forceinline__ bool cast_ray_setup(CastRay& r) {
+    bool ok = r.tmin >= 0.0f && r.tmax == r.tmax;
+    bool all_zero = true;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        ok = ok && cam_finite(r.o[a]) && cam_finite(r.d[a]);
+        all_zero = all_zero && r.d[a] == 0.0f;
+        r.inv[a] = 1.0f / r.d[a];
+        r.zero[a] = r.d[a] == 0.0f || !cam_finite(r.inv[a]);
+    }
+    return ok && !all_zero;
+}
+
+// the box rule; bn and bf are written whenever rule 1 lets the box through
+__device__ __forceinline__ bool cast_box_rule(const CastRay& r, const CastBox& B, float& bn, float& bf) {
+    bn = -__builtin_inff();
+    bf = __builtin_inff();
+    bool pass = true;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        if (B.lo[a] > B.hi[a]) return false;
+        if (r.zero[a]) {
+            pass = pass && B.lo[a] <= r.o[a] && r.o[a] <= B.hi[a];
+        } else {
+            const float x1 = (B.lo[a] - r.o[a]) * r.inv[a], x2 = (B.hi[a] - r.o[a]) * r.inv[a];
+            bn = fmaxf(bn, fminf(x1, x2));
+            bf = fminf(bf, fmaxf(x1, x2));
+        }
+    }
+    return pass && bn <= bf && bf >= r.tmin && bn <= r.tmax;
+}
+
+// the triangle rule on a valid triangle's vertices: true when it counts, with t and (u, v, w)
+__device__ __forceinline__ bool cast_triangle(const CastRay& r, int cull, const float* P, float& t, float& u, float& v, float& w) {
+    float bn, bf;
+    if (!cast_box_rule(r, cast_tri_box(P, P + 3, P + 6), bn, bf)) return false;
+    const float* d = r.d;
+    const float e1[3] = {P[3] - P[0], P[4] - P[1], P[5] - P[2]}, e2[3] = {P[6] - P[0], P[7] - P[1], P[8] - P[2]};
+    const float p[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
+    const float det = (e1[0] * p[0] + e1[1] * p[1]) + e1[2] * p[2];
+    if (!(det != 0.0f)) return false;                                        // (a NaN det is refused by inv below)
+    const float inv = 1.0f / det;
+    if (!cam_finite(inv)) return false;
+    if ((cull == 1 && det < 0.0f) || (cull == 2 && det > 0.0f)) return false;
+    const float s[3] = {r.o[0] - P[0], r.o[1] - P[1], r.o[2] - P[2]};
+    u = ((s[0] * p[0] + s[1] * p[1]) + s[2] * p[2]) * inv;
+    const float q[3] = {s[1] * e1[2] - s[2] * e1[1], s[2] * e1[0] - s[0] * e1[2], s[0] * e1[1] - s[1] * e1[0]};
+    v = ((d[0] * q[0] + d[1] * q[1]) + d[2] * q[2]) * inv;
+    w = (1.0f - u) - v;
+    if (!(u >= 0.0f && v >= 0.0f && w >= 0.0f)) return false;
+    const float t0 = ((e2[0] * q[0] + e2[1] * q[1]) + e2[2] * q[2]) * inv;
+    if (t0 != t0) return false;
+    t = fminf(fmaxf(t0, bn), bf) + 0.0f;
+    return r.tmin <= t && t <= r.tmax;
+}
+
+struct CastHit {
+    int tri;
+    float t, u, v, w;
+};
+
+// Nodes are numbered as a heap: the root is 1, the children of h are 2 h and 2 h + 1, so a node of depth D = floor(log2 h) is
+// node h - 2^D of level K - D.  `stack` is this thread's column of the workgroup's LDS array, CB ints apart.
+template <bool ANY>
+__device__ __forceinline__ CastHit cast_walk(const CastTree& R, const float* __restrict__ records, const float* __restrict__ nodes,
+                                             const CastRay& r, int cull, int* stack, const int* s_off) {
+    CastHit best{-1, __builtin_inff(), 0.0f, 0.0f, 0.0f};
+    if (R.nodes == 0) return best;
+    int sp = 0, cur = 0;
+    float bn, bf;
+    if (cast_box_rule(r, cast_load_box(nodes, s_off[R.K]), bn, bf)) cur = 1;
+    const long long max_steps = 4ll * R.nodes + 4;                           // every node is entered at most once, popped at most once
+    for (long long step = 0; step < max_steps && cur != 0; step++) {
+        const int depth = 31 - __clz(cur), k = R.K - depth;
+        if (k == 0) {
+            const int l = cur - (1 << depth);
+            const float* rec = records + (size_t)l * (CLEAF * CREC);
+#pragma unroll
+            for (int j = 0; j < CLEAF; j++) {
+                float P[10];
+#pragma unroll
+                for (int c = 0; c < CREC; c += 2) {
+                    const float2 x = *(const float2*)(rec + j * CREC + c);
+                    P[c] = x.x;
+                    P[c + 1] = x.y;
+                }
+                const int id = __float_as_int(P[9]);
+                float t, u, v, w;
+                if (id >= 0 && cast_triangle(r, cull, P, t, u, v, w) && (t < best.t || (t == best.t && id < best.tri) || best.tri < 0))
+                    best = CastHit{id, t, u, v, w};
+            }
+            if (ANY && best.tri >= 0) return best;
+            cur = 0;
+        } else {
+            const int c0 = 2 * cur, j0 = c0 - (2 << depth), nb = R.n(k - 1), base = s_off[k - 1];
+            float bn0 = 0.0f, bn1 = 0.0f;
+            bool p0 = false, p1 = false;
+            if (j0 < nb) p0 = cast_box_rule(r, cast_load_box(nodes, base + j0), bn0, bf) && (ANY || !(bn0 > best.t));
+            if (j0 + 1 < nb) p1 = cast_box_rule(r, cast_load_box(nodes, base + j0 + 1), bn1, bf) && (ANY || !(bn1 > best.t));
+            if (p0 && p1) {
+                const bool swap = bn1 < bn0;
+                if (sp < CSTACK) stack[(sp++) * CB] = swap ? c0 : c0 + 1;    // (one entry per level: sp <= K < CSTACK)
+                cur = swap ? c0 + 1 : c0;
+            } else {
+                cur = p0 ? c0 : p1 ? c0 + 1 : 0;
+            }
+        }
+        while (cur == 0 && sp > 0) {                                         // (bounded by sp)
+            const int h = stack[(--sp) * CB];
+            const int dh = 31 - __clz(h), kh = R.K - dh;
+            if (cast_box_rule(r, cast_load_box(nodes, s_off[kh] + (h - (1 << dh))), bn, bf) && (ANY || !(bn > best.t))) cur = h;
+        }
+    }
+    return best;
+}
+
+__device__ __forceinline__ void cast_write(const CastHit& hit, bool usable, size_t i, int32_t* __restrict__ tri, float* __restrict__ t,
+                                           float* __restrict__ bary) {
+    const float nan = __builtin_nanf("");
+    const bool found = usable && hit.tri >= 0;
+    tri[i] = !usable ? -2 : found ? hit.tri : -1;
+    t[i] = !usable ? nan : found ? hit.t : 0.0f;
+    if (bary) {
+        bary[i * 3] = !usable ? nan : found ? hit.w : 0.0f;
+        bary[i * 3 + 1] = !usable ? nan : found ? hit.u : 0.0f;
+        bary[i * 3 + 2] = !usable ? nan : found ? hit.v : 0.0f;
+    }
+}
+
+template <bool ANY>
+__global__ void __launch_bounds__(CB)
+k_cast_rays(const CastTree R, int n, const float* __restrict__ origins, const float* __restrict__ directions,
+            const float* __restrict__ tmin_rays, const float* __restrict__ tmax_rays, float tmin, float tmax, int cull,
+            const float* __restrict__ records, const float* __restrict__ nodes, int32_t* __restrict__ tri, float* __restrict__ t,
+            float* __restrict__ bary) {
+    __shared__ int s_stack[CSTACK * CB];
+    __shared__ int s_off[CSTACK];
+    cast_offsets_to_lds(R, s_off);
+    const int i = blockIdx.x * CB + threadIdx.x;
+    if (i >= n) return;                                                      // (no barrier below)
+    CastRay r;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        r.o[a] = origins[(size_t)i * 3 + a];
+        r.d[a] = directions[(size_t)i * 3 + a];
+    }
+    r.tmin = tmin_rays ? tmin_rays[i] : tmin;
+    r.tmax = tmax_rays ? tmax_rays[i] : tmax;
+    const bool usable = cast_ray_setup(r);
+    CastHit hit{-1, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (usable) hit = cast_walk<ANY>(R, records, nodes, r, cull, s_stack + threadIdx.x, s_off);
+    if (ANY) tri[i] = !usable ? -2 : hit.tri >= 0 ? 1 : 0;
+    else cast_write(hit, usable, (size_t)i, tri, t, bary);
+}
+
+__global__ void __launch_bounds__(CB)
+k_cast_cameras(const CastTree R, int F, int h, int w, const float* __restrict__ cams, float tmin, float tmax, int cull,
+               const float* __restrict__ records, const float* __restrict__ nodes, int32_t* __restrict__ tri, float* __restrict__ depth,
+               float* __restrict__ bary) {
+    __shared__ int s_stack[CSTACK * CB];
+    __shared__ int s_off[CSTACK];
+    cast_offsets_to_lds(R, s_off);
+    const unsigned i = blockIdx.x * (unsigned)CB + threadIdx.x;              // F h w < 2^31
+    const unsigned hw = (unsigned)h * (unsigned)w;
+    if (i >= (unsigned)F * hw) return;
+    const int f = i / hw, p = i - (unsigned)f * hw;
+    const float* cam = cams + (size_t)f * DURF_CAM_FLOATS;
+    CastRay r;
+    r.tmin = tmin;
+    r.tmax = tmax;
+    bool usable = (int)cam[DURF_CAM_H] == h && (int)cam[DURF_CAM_W] == w;    // (a NaN converts to some int: the row is not finite then)
+    if (usable) {
+        float view[3], radius, nr, fr;
+        pinhole_ray(cam, p, tmin, tmax, 0, r.o, r.d, view, &radius, &nr, &fr);
+        usable = cast_ray_setup(r);
+    }
+    CastHit hit{-1, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (usable) hit = cast_walk<false>(R, records, nodes, r, cull, s_stack + threadIdx.x, s_off);
+    cast_write(hit, usable, (size_t)i, tri, depth, bary);
+}
+
+// ---- launchers ----------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct CastWs {
+    float *records, *nodes;
+    size_t total;
+};
+
+bool cast_t_ok(int T) { return T >= 0 && T < DURF_CAST_MAX_TRIANGLES; }
+
+CastTree cast_tree(int T) {
+    CastTree R{};
+    R.T = T;
+    if (T == 0) return R;
+    int n = (int)durf_cdiv((size_t)T, CLEAF), off = 0, k = 0;
+    R.n0 = n;
+    for (;; k++) {                                                           // n_0 <= 2^28: at most 29 levels
+        R.off[k] = off;
+        off += n;
+        if (n == 1) break;
+        n = (n + 1) / 2;
+    }
+    R.K = k;
+    R.nodes = off;
+    return R;
+}
+
+CastWs carve_cast(void* base, const CastTree& R) {
+    durf::Carver c{(char*)base, 0};
+    CastWs w{};
+    const size_t slots = R.T == 0 ? 0 : (size_t)R.n0 * CLEAF;
+    w.records = (float*)c.take(slots * CREC * 4);
+    w.nodes = (float*)c.take((size_t)R.nodes * CNODE * 4);
+    w.total = c.total() > 256 ? c.total() : 256;
+    return w;
+}
+
+int check_cast_t(const char* who, int T) {
+    if (!cast_t_ok(T)) {
+        durf_set_error("%s: requirement failed: 0 <= T < %d, T = %d", who, DURF_CAST_MAX_TRIANGLES, T);
+        return -1;
+    }
+    return 0;
+}
+
+int check_cast_ws(const char* who, const void* workspace, size_t workspace_bytes, const CastTree& R, CastWs* ws) {
+    if (workspace == nullptr || ((size_t)workspace & 255) != 0) {
+        durf_set_error("%s: requirement failed: workspace aligned to 256 bytes", who);
+        return -1;
+    }
+    *ws = carve_cast((void*)workspace, R);
+    return durf::check_workspace(who, workspace_bytes, ws->total, "durf_cast_workspace_bytes(%d)", R.T);
+}
+
+int check_cast_mesh(const char* who, int V, int T, const float* vertices, const int32_t* triangles) {
+    if (!(V >= 0)) { durf_set_error("%s: requirement failed: V >= 0, V = %d", who, V); return -1; }
+    if (check_cast_t(who, T) != 0) return -1;
+    if (!(vertices || V == 0)) { durf_set_error("%s: requirement failed: vertices for V = %d", who, V); return -1; }
+    if (!(triangles || T == 0)) { durf_set_error("%s: requirement failed: triangles for T = %d", who, T); return -1; }
+    return 0;
+}
+
+int check_cast_bounds(const char* who, bool scalar_tmin, bool scalar_tmax, float tmin, float tmax, int cull) {
+    if (!(cull >= 0 && cull <= 2)) { durf_set_error("%s: requirement failed: cull in 0 .. 2, cull = %d", who, cull); return -1; }
+    if (scalar_tmin && !(tmin >= 0.0f)) { durf_set_error("%s: requirement failed: tmin >= 0, tmin = %g", who, (double)tmin); return -1; }
+    if (scalar_tmax && tmax != tmax) { durf_set_error("%s: requirement failed: tmax is a number, tmax = %g", who, (double)tmax); return -1; }
+    return 0;
+}
+
+template <bool ANY>
+int cast_rays(const char* who, void* stream, int n, const float* origins, const float* directions, const float* tmin_rays,
+              const float* tmax_rays, float tmin, float tmax, int cull, int T, const void* workspace, size_t workspace_bytes,
+              int32_t* tri, float* t, float* bary) {
+    if (!(n >= 0)) { durf_set_error("%s: requirement failed: n >= 0, n = %d", who, n); return -1; }
+    if (check_cast_t(who, T) != 0) return -1;
+    if (check_cast_bounds(who, tmin_rays == nullptr, tmax_rays == nullptr, tmin, tmax, cull) != 0) return -1;
+    if (!((origins && directions) || n == 0)) { durf_set_error("%s: requirement failed: origins and directions for n = %d", who, n); return -1; }
+    if (!((tri && (ANY || t)) || n == 0)) { durf_set_error("%s: requirement failed: outputs for n = %d", who, n); return -1; }
+    const CastTree R = cast_tree(T);
+    CastWs ws;
+    if (check_cast_ws(who, workspace, workspace_bytes, R, &ws) != 0) return -1;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_cast_rays<ANY>, dim3(durf_cdiv((size_t)n, CB)), dim3(CB), 0, (hipStream_t)stream, R, n, origins, directions,
+                       tmin_rays, tmax_rays, tmin, tmax, cull, ws.records, ws.nodes, tri, t, bary);
+    DURF_CHECK_LAUNCH(ANY ? "k_cast_rays<any>" : "k_cast_rays<nearest>");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t durf_cast_workspace_bytes(int T) {
+    if (!cast_t_ok(T)) return 0;
+    return carve_cast(nullptr, cast_tree(T)).total;
+}
+
+int durf_cast_keys(void* stream, int V, int T, const float* vertices, const int32_t* triangles, const float* bounds, int64_t* keys) {
+    if (check_cast_mesh(__func__, V, T, vertices, triangles) != 0) return -1;
+    if (!((bounds && keys) || T == 0)) { durf_set_error("%s: requirement failed: bounds and keys for T = %d", __func__, T); return -1; }
+    if (T == 0) return 0;
+    hipLaunchKernelGGL(k_cast_keys, dim3(durf_cdiv((size_t)T, CB)), dim3(CB), 0, (hipStream_t)stream, V, T, vertices, triangles, bounds,
+                       (long long*)keys);
+    DURF_CHECK_LAUNCH("k_cast_keys");
+    return 0;
+}
+
+int durf_cast_build(void* stream, int V, int T, const float* vertices, const int32_t* triangles, const int32_t* order, void* workspace,
+                    size_t workspace_bytes) {
+    if (check_cast_mesh(__func__, V, T, vertices, triangles) != 0) return -1;
+    if (!(order || T == 0)) { durf_set_error("%s: requirement failed: order for T = %d", __func__, T); return -1; }
+    const CastTree R = cast_tree(T);
+    CastWs ws;
+    if (check_cast_ws(__func__, workspace, workspace_bytes, R, &ws) != 0) return -1;
+    if (T == 0) return 0;
+    const hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_cast_leaves, dim3(durf_cdiv((size_t)R.n0, CB)), dim3(CB), 0, s, V, T, R.n0, vertices, triangles, order,
+                       ws.records, ws.nodes);
+    DURF_CHECK_LAUNCH("k_cast_leaves");
+    int k = 1;
+    for (; k <= R.K && R.n(k) > DURF_CAST_TOP; k++) {
+        hipLaunchKernelGGL(k_cast_level, dim3(durf_cdiv((size_t)R.n(k), CB)), dim3(CB), 0, s, R.n(k - 1), R.off[k - 1], R.n(k), R.off[k],
+                           ws.nodes);
+        DURF_CHECK_LAUNCH("k_cast_level");
+    }
+    if (k <= R.K) {
+        hipLaunchKernelGGL(k_cast_top, dim3(1), dim3(CB), 0, s, R, k, ws.nodes);
+        DURF_CHECK_LAUNCH("k_cast_top");
+    }
+    return 0;
+}
+
+int durf_cast_rays(void* stream, int n, const float* origins, const float* directions, const float* tmin_rays, const float* tmax_rays,
+                   float tmin, float tmax, int cull, int T, const void* workspace, size_t workspace_bytes, int32_t* tri, float* t,
+                   float* bary) {
+    return cast_rays<false>(__func__, stream, n, origins, directions, tmin_rays, tmax_rays, tmin, tmax, cull, T, workspace,
+                            workspace_bytes, tri, t, bary);
+}
+
+int durf_cast_any(void* stream, int n, const float* origins, const float* directions, const float* tmin_rays, const float* tmax_rays,
+                  float tmin, float tmax, int cull, int T, const void* workspace, size_t workspace_bytes, int32_t* hit) {
+    return cast_rays<true>(__func__, stream, n, origins, directions, tmin_rays, tmax_rays, tmin, tmax, cull, T, workspace, workspace_bytes,
+                           hit, nullptr, nullptr);
+}
+
+int durf_cast_cameras(void* stream, int F, int h, int w, const float* cams_dev, float tmin, float tmax, int cull, int T,
+                      const void* workspace, size_t workspace_bytes, int32_t* tri, float* depth, float* bary) {
+    if (!(F >= 0 && h >= 1 && w >= 1)) {
+        durf_set_error("%s: requirement failed: F >= 0, h >= 1, w >= 1, F = %d, h = %d, w = %d", __func__, F, h, w);
+        return -1;
+    }
+    if (!((double)F * h * w < 2147483648.0)) {
+        durf_set_error("%s: requirement failed: F h w < 2^31 pixels, F = %d, h = %d, w = %d", __func__, F, h, w);
+        return -1;
+    }
+    if (check_cast_t(__func__, T) != 0) return -1;
+    if (check_cast_bounds(__func__, true, true, tmin, tmax, cull) != 0) return -1;
+    if (!((cams_dev && tri && depth) || F == 0)) { durf_set_error("%s: requirement failed: cams_dev, tri and depth for F = %d", __func__, F); return -1; }
+    const CastTree R = cast_tree(T);
+    CastWs ws;
+    if (check_cast_ws(__func__, workspace, workspace_bytes, R, &ws) != 0) return -1;
+    if (F == 0) return 0;
+    hipLaunchKernelGGL(k_cast_cameras, dim3(durf_cdiv((size_t)F * h * w, CB)), dim3(CB), 0, (hipStream_t)stream, R, F, h, w, cams_dev, tmin,
+                       tmax, cull, ws.records, ws.nodes, tri, depth, bary);
+    DURF_CHECK_LAUNCH("k_cast_cameras");
+    return 0;
+}
+
+}  // extern "C"

@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import _lib, camera
-from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs
+from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs, _cast_sigs
 
 
 
@@ -22,7 +22,7 @@ def _by_prefix(table, prefix):
 # the tables imported above; tests/test_headers_host.py holds the tables to the C compiler).  Every `#define DURF_X <integer>`
 # of include/durf_hip.h and include/durf_<name>.h is ops.X: ENC_DIM, MAX_OBJ, TRAIN_OBJ_FP32, TIMED_STAGES, MESH_BLOCK, PARTS_TILE_K, ...
 # -- all but OVERLAP_MIN_ROWS, launch policy that the library is asked for (__getattr__ below).
-for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs):
+for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs, _cast_sigs):
     globals().update(_by_prefix(_table, 'DURF_'))
 del OVERLAP_MIN_ROWS
 
@@ -2607,3 +2607,87 @@ def tsdf_sample(tsdf, weight, colour, shape, origin, inv, trunc, points, min_wei
                                                     _p(tsdf), _p(weight), _p(colour), float(trunc), float(min_weight), m, _z(points), _z(sdf),
                                                     _z(ok), _z(rgb)), 'durf_tsdf_sample')
     return sdf, ok, rgb
+
+
+# ---------------------------------------------------------------------------
+# rays against a triangle mesh (include/durf_cast.h, csrc/cast.hip, libdurf_cast.so)
+# ---------------------------------------------------------------------------
+def cast_workspace_bytes(T):
+    return int(_lib.cast_lib().durf_cast_workspace_bytes(int(T)))
+
+
+def _cast_mesh(vertices, triangles):
+    V, T = int(vertices.shape[0]), int(triangles.shape[0])
+    assert _f32(vertices).numel() == 3 * V and _i32(triangles, 3 * T, 'triangles') is triangles
+    return V, T
+
+
+def cast_keys(vertices, triangles, bounds):
+    """durf_cast_keys: the Morton key of every triangle's centroid inside bounds [6] ON THE DEVICE (lo, hi) -> int64 [T];
+    INT64_MAX for an invalid triangle"""
+    V, T = _cast_mesh(vertices, triangles)
+    assert _f32(bounds).numel() == 6
+    keys = torch.empty(T, dtype=torch.int64, device=vertices.device)
+    with _Timed('cast_keys'):
+        _lib.check(_lib.cast_lib().durf_cast_keys(_stream(), V, T, _z(vertices), _z(triangles), _p(bounds), _z(keys)), 'durf_cast_keys')
+    return keys
+
+
+def cast_build(vertices, triangles, order, ws=None):
+    """durf_cast_build: the implicit tree over the permutation order [T] int32 -> the workspace (a uint8 tensor the casts read)"""
+    V, T = _cast_mesh(vertices, triangles)
+    _i32(order, T, 'order')
+    if ws is None:
+        ws = torch.empty(cast_workspace_bytes(T), dtype=torch.uint8, device=vertices.device)
+    with _Timed('cast_build'):
+        _lib.check(_lib.cast_lib().durf_cast_build(_stream(), V, T, _z(vertices), _z(triangles), _z(order), _p(ws), ws.numel()), 'durf_cast_build')
+    return ws
+
+
+def _cast_bound(b, n, what):
+    """a bound of the cast: a number -> (None, number); a tensor [n] on the device -> (tensor, 0.0)"""
+    if torch.is_tensor(b):
+        assert _f32(b).numel() == n, (what, tuple(b.shape), n)
+        return b, 0.0
+    return None, float(b)
+
+
+def _cast_rays(origins, directions, tmin, tmax):
+    n = int(origins.numel() // 3)
+    assert _f32(origins).numel() == 3 * n == _f32(directions).numel(), (tuple(origins.shape), tuple(directions.shape))
+    return (n,) + _cast_bound(tmin, n, 'tmin') + _cast_bound(tmax, n, 'tmax')
+
+
+def cast_rays(ws, T, origins, directions, tmin=0.0, tmax=float('inf'), cull=0, want_bary=True):
+    """durf_cast_rays: origins, directions [..., 3] against the tree in ws -> (tri int32 [...], t [...], bary [..., 3] = (w, u, v)
+    or None); tmin, tmax: numbers or tensors [...] on the device.  -1 / 0 where nothing counts, -2 / NaN for an unusable ray."""
+    n, tmin_a, tmin_s, tmax_a, tmax_s = _cast_rays(origins, directions, tmin, tmax)
+    lead, dev = tuple(origins.shape[:-1]), origins.device
+    tri, t = torch.empty(lead, dtype=torch.int32, device=dev), torch.empty(lead, device=dev)
+    bary = torch.empty(lead + (3,), device=dev) if want_bary else None
+    with _Timed('cast_rays'):
+        _lib.check(_lib.cast_lib().durf_cast_rays(_stream(), n, _z(origins), _z(directions), _z(tmin_a), _z(tmax_a), tmin_s, tmax_s, int(cull),
+                                                  int(T), _p(ws), ws.numel(), _z(tri), _z(t), _z(bary)), 'durf_cast_rays')
+    return tri, t, bary
+
+
+def cast_any(ws, T, origins, directions, tmin=0.0, tmax=float('inf'), cull=0):
+    """durf_cast_any -> hit int32 [...]: 1 where a triangle counts, 0 where none does, -2 for an unusable ray"""
+    n, tmin_a, tmin_s, tmax_a, tmax_s = _cast_rays(origins, directions, tmin, tmax)
+    hit = torch.empty(tuple(origins.shape[:-1]), dtype=torch.int32, device=origins.device)
+    with _Timed('cast_any'):
+        _lib.check(_lib.cast_lib().durf_cast_any(_stream(), n, _z(origins), _z(directions), _z(tmin_a), _z(tmax_a), tmin_s, tmax_s, int(cull),
+                                                 int(T), _p(ws), ws.numel(), _z(hit)), 'durf_cast_any')
+    return hit
+
+
+def cast_cameras(ws, T, cams, h, w, tmin=0.0, tmax=float('inf'), cull=0, want_bary=True):
+    """durf_cast_cameras: cams [F,CAM_FLOATS] on the device, all h x w -> (tri int32 [F,h,w], depth [F,h,w], bary [F,h,w,3] or None)"""
+    assert _f32(cams).dim() == 2 and cams.shape[1] == CAM_FLOATS, tuple(cams.shape)
+    F, h, w, dev = int(cams.shape[0]), int(h), int(w), cams.device
+    tri, depth = torch.empty(F, h, w, dtype=torch.int32, device=dev), torch.empty(F, h, w, device=dev)
+    bary = torch.empty(F, h, w, 3, device=dev) if want_bary else None
+    with _Timed('cast_cameras'):
+        _lib.check(_lib.cast_lib().durf_cast_cameras(_stream(), F, h, w, _z(cams), float(tmin), float(tmax), int(cull), int(T), _p(ws),
+                                                     ws.numel(), _z(tri), _z(depth), _z(bary)), 'durf_cast_cameras')
+    return tri, depth, bary
