@@ -109,7 +109,10 @@ def visible(b, a, p):
     return occluded(b, o, e - o, 0.0, 1.0) == 0
 
 
-def _attributes(b, tri, bary, attrs, label, out):
+def attributes_at(b, tri, bary, attrs, label, out):
+    """The per-vertex arrays of build()'s b at (tri, bary), through durf_raster_interp, added to the dict `out`: every key of
+    `attrs` that b holds as [...,C] (uint8 colours as [0, 1] floats) and `label` as [...] int32 (-1 where tri < 0).  cameras()
+    and closest.attributes share it."""
     import torch
     from . import ops
     V = b['V']
@@ -143,7 +146,7 @@ def cameras(b, cams, tmin=0.0, tmax=float('inf'), attrs=('rgb', 'normals'), labe
     import torch
     from . import ops
     tri, depth, bary = ops.cast_cameras(b['ws'], b['T'], torch.as_tensor(cams).to(b['ws'].device).contiguous(), h, w, tmin, tmax, cull)
-    return _attributes(b, tri, bary, attrs, label, dict(tri=tri, depth=depth, bary=bary, mask=tri >= 0))
+    return attributes_at(b, tri, bary, attrs, label, dict(tri=tri, depth=depth, bary=bary, mask=tri >= 0))
 
 
 def lidar(b, sensor, poses, near, far, pose_end=None):

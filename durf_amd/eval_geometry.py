@@ -4,7 +4,7 @@ precision / recall / F-score at thresholds (durf_amd.geometry):
     python -m durf_amd.eval_geometry --gin_file configs/waymo.gin --data_dir DATA --train_dir CKPT --split test --eval_dir OUT
                                      --grid "ox,oy,oz;nu,nv,nw;step" [--iso V] [--source mesh|frames|lidar] [--samples 200000]
                                      [--max_dist 0.5] [--thresholds 0.05,0.1,0.2] [--keep_objects] [--sweeps sweeps.npz]
-                                     [--min_component N] [--largest K]
+                                     [--min_component N] [--largest K] [--exact]
     python -m durf_amd.eval_geometry --synthetic --eval_dir OUT [--source ...]
 
 Truth: the union over the split's frames of geometry.depth_points of the frame's LIDAR depth plane (eval_set()['depth']: its
@@ -16,7 +16,9 @@ switched off unless --keep_objects).  Written: OUT/geometry.json (everything geo
 source and the point counts), OUT/accuracy.ply (the prediction coloured by its distance to the truth) and OUT/completeness.ply
 (the truth coloured by its distance to the prediction), turbo over [0, --max_dist].  --synthetic measures
 train_boxpose.SyntheticTimestepDataset's scene (no data directory; without --train_dir the freshly initialised model), which
-exercises the command end to end."""
+exercises the command end to end.  --exact (--source mesh only) measures completeness against the mesh itself, not its samples
+(geometry.surface_distance: the point-to-triangle distance of durf_amd.closest); geometry.json then holds "exact": true and
+completeness.ply is coloured by the exact distances."""
 import argparse
 import json
 import math
@@ -39,6 +41,7 @@ def build_parser():
     ap.add_argument('--split', choices=('test', 'render'), default='test', help='the frames whose LIDAR depth is the truth')
     ap.add_argument('--source', choices=('mesh', 'frames', 'lidar'), default='mesh', help='what is measured against the truth')
     ap.add_argument('--samples', type=int, default=200000, help='--source mesh: surface samples')
+    ap.add_argument('--exact', action='store_true', help='--source mesh: completeness against the mesh itself (point-to-triangle), not its samples')
     ap.add_argument('--max_dist', type=float, default=0.5, help='distances are looked for up to here (scene units)')
     ap.add_argument('--thresholds', default=None, help='comma-separated, at most 8, each <= --max_dist (default: 0.05,0.1,0.2,0.5 up to it)')
     ap.add_argument('--keep_objects', action='store_true', help='keep the truth points inside boxes (and the boxes in a lidar prediction)')
@@ -144,6 +147,8 @@ def main(argv=None):
         raise SystemExit('eval_geometry: --source mesh needs --grid')
     if args.source == 'lidar' and not args.synthetic and args.sweeps is None:
         raise SystemExit('eval_geometry: --source lidar needs --sweeps')
+    if args.exact and args.source != 'mesh':
+        raise SystemExit('eval_geometry: --exact needs --source mesh')
     try:
         thresholds = (geometry.DEFAULT_THRESHOLDS if args.thresholds is None else
                       tuple(float(t) for t in args.thresholds.split(',') if t.strip()))
@@ -162,7 +167,7 @@ def main(argv=None):
         ckw = dict(min_points=args.min_component, largest=args.largest) if cleaning else {}
         bg = mesh.extract(model, variables, origin, shape, step=step, iso=args.iso, colour=None, ts=args.ts, ext=ext if K else None,
                           box_enable=[0] * K if K else None, sigma=args.sigma, alpha=alpha, chunk=max(args.chunk, 1), **ckw)
-        pred = geometry.sample_mesh(bg, args.samples)[0]
+        pred = None if args.exact else geometry.sample_mesh(bg, args.samples)[0]
         source = dict(kind='mesh', vertices=int(bg['vertices'].shape[0]), triangles=int(bg['triangles'].shape[0]), iso=args.iso,
                       samples=args.samples, frame=bg['frame'])
         if cleaning:
@@ -174,13 +179,19 @@ def main(argv=None):
         pred = lidar_cloud(args, model, config, variables, dataset, alpha, ext)
         source = dict(kind='lidar', sweeps=args.sweeps)
     try:
-        res = geometry.cloud_distance(pred, truth, args.max_dist, thresholds=thresholds, keep=True)
+        if args.exact:
+            res = geometry.surface_distance(bg, truth, args.max_dist, thresholds=thresholds, samples=args.samples, keep=True)
+            pred = res['pred']
+        else:
+            res = geometry.cloud_distance(pred, truth, args.max_dist, thresholds=thresholds, keep=True)
     except ValueError as e:
         raise SystemExit('eval_geometry: %s' % e)
     os.makedirs(args.eval_dir, exist_ok=True)
     geometry.write_error_ply(os.path.join(args.eval_dir, 'accuracy.ply'), pred, res['pred_dist'], args.max_dist)
     geometry.write_error_ply(os.path.join(args.eval_dir, 'completeness.ply'), truth, res['truth_dist'], args.max_dist)
-    doc = {k: v for k, v in res.items() if k not in ('pred_dist', 'pred_index', 'truth_dist', 'truth_index')}
+    doc = {k: v for k, v in res.items() if k not in ('pred', 'pred_dist', 'pred_index', 'truth_dist', 'truth_index', 'truth_bary')}
+    if args.exact:
+        doc['exact'] = True
     doc.update(source=source, pred_points=int(pred.shape[0]), truth_points=int(truth.shape[0]), frames=len(es['ts']), split=args.split,
                keep_objects=bool(args.keep_objects))
     with open(os.path.join(args.eval_dir, 'geometry.json'), 'w') as fh:

@@ -174,6 +174,40 @@ def cloud_distance(pred, truth, max_dist, thresholds=DEFAULT_THRESHOLDS, sort_qu
     return res
 
 
+def surface_distance(m, truth, max_dist, thresholds=DEFAULT_THRESHOLDS, samples=200000, sort_queries=None, keep=False):
+    """cloud_distance for a MESH m (dict vertices, triangles) against the measured cloud truth, without a sample spacing on the
+    completeness side: accuracy is `samples` area-uniform samples of m (sample_mesh) against the truth cloud by nearest(), as
+    cloud_distance does; completeness is every truth point against the surface itself by closest.points (the exact
+    point-to-triangle distance, include/durf_closest.h).  -> cloud_distance's keys (`grids` holds the one grid there is);
+    keep=True adds pred (the samples), pred_dist, pred_index, truth_dist, truth_index (the triangle each truth point lands on)
+    and truth_bary."""
+    import torch
+    from . import cast, closest, ops
+    entry = 'geometry.surface_distance'
+    md = _max_dist(max_dist, entry)
+    if thresholds is DEFAULT_THRESHOLDS:
+        thresholds = tuple(t for t in DEFAULT_THRESHOLDS if t <= md)
+    th = _thresholds(thresholds, md, entry)
+    if int(samples) < 1:
+        raise ValueError('%s: samples = %r, expected at least one sample of the mesh (the accuracy side)' % (entry, samples))
+    truth = _cloud(truth, 'truth', entry)
+    b = m if (isinstance(m, dict) and m.get('ws') is not None) else cast.build(m)
+    pred = sample_mesh(b, int(samples))[0]
+    rows = torch.empty(2, ops.GEOM_STAT_DOUBLES, dtype=torch.float64, device=pred.device)
+    g = make_grid(truth, md, entry)
+    d, i = nearest(pred, truth, md, sort_queries=sort_queries, grid=g)
+    far = (i == -2) & torch.isfinite(pred).all(1)                       # (as cloud_distance: beyond the grid is `found nothing`)
+    d, i = torch.where(far, torch.full_like(d, md), d), torch.where(far, torch.full_like(i, -1), i)
+    ops.geom_stats(d, i, th, out=rows[0])
+    r = closest.points(b, truth, md, sort_queries=sort_queries)
+    ops.geom_stats(r['dist'], r['tri'], th, out=rows[1])
+    res = summarise(rows.cpu().numpy(), th, md)
+    res['grids'] = dict(pred_to_truth=dict(origin=g['origin'].tolist(), dims=list(g['dims']), cell=g['cell']))
+    if keep:
+        res.update(pred=pred, pred_dist=d, pred_index=i, truth_dist=r['dist'], truth_index=r['tri'], truth_bary=r['bary'])
+    return res
+
+
 def sample_mesh(m, n):
     """n area-uniform samples of a triangle mesh: what mesh.surface / mesh.extract / mesh.read_ply return (dict vertices
     [V,3], triangles [T,3]; host arrays are uploaded) -> (points [n,3], tri [n] int32: the triangle each sample lies on, so the

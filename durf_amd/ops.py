@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import _lib, camera
-from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs, _cast_sigs
+from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs, _cast_sigs, _closest_sigs
 
 
 
@@ -22,7 +22,7 @@ def _by_prefix(table, prefix):
 # the tables imported above; tests/test_headers_host.py holds the tables to the C compiler).  Every `#define DURF_X <integer>`
 # of include/durf_hip.h and include/durf_<name>.h is ops.X: ENC_DIM, MAX_OBJ, TRAIN_OBJ_FP32, TIMED_STAGES, MESH_BLOCK, PARTS_TILE_K, ...
 # -- all but OVERLAP_MIN_ROWS, launch policy that the library is asked for (__getattr__ below).
-for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs, _cast_sigs):
+for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs, _cast_sigs, _closest_sigs):
     globals().update(_by_prefix(_table, 'DURF_'))
 del OVERLAP_MIN_ROWS
 
@@ -2691,3 +2691,35 @@ def cast_cameras(ws, T, cams, h, w, tmin=0.0, tmax=float('inf'), cull=0, want_ba
         _lib.check(_lib.cast_lib().durf_cast_cameras(_stream(), F, h, w, _z(cams), float(tmin), float(tmax), int(cull), int(T), _p(ws),
                                                      ws.numel(), _z(tri), _z(depth), _z(bary)), 'durf_cast_cameras')
     return tri, depth, bary
+
+
+# ---------------------------------------------------------------------------
+# the closest point of a triangle mesh (include/durf_closest.h, csrc/closest.hip, libdurf_closest.so)
+# ---------------------------------------------------------------------------
+def closest_points(ws, T, points, max_dist=float('inf'), want_bary=True, want_point=True):
+    """durf_closest_points: points [..., 3] against the tree cast_build left in ws -> (tri int32 [...], dist [...], bary [..., 3] =
+    (w, u, v) or None, point [..., 3] or None).  -1 / max_dist where nothing lies within max_dist, -2 / NaN for an unusable point."""
+    n = int(points.numel() // 3)
+    assert _f32(points).numel() == 3 * n and points.dim() >= 1 and points.shape[-1] == 3, tuple(points.shape)
+    lead, dev = tuple(points.shape[:-1]), points.device
+    tri, dist = torch.empty(lead, dtype=torch.int32, device=dev), torch.empty(lead, device=dev)
+    bary = torch.empty(lead + (3,), device=dev) if want_bary else None
+    point = torch.empty(lead + (3,), device=dev) if want_point else None
+    with _Timed('closest_points'):
+        _lib.check(_lib.closest_lib().durf_closest_points(_stream(), n, _z(points), float(max_dist), int(T), _p(ws), ws.numel(), _z(tri),
+                                                          _z(dist), _z(bary), _z(point)), 'durf_closest_points')
+    return tri, dist, bary, point
+
+
+def closest_grid(ws, T, shape, origin, du, dv, dw, max_dist=float('inf'), want_tri=True):
+    """durf_closest_grid: the lattice of shape (nu, nv, nw) at origin + i du + j dv + k dw (host floats), its points generated in
+    the kernel -> (dist [nu,nv,nw], tri int32 [nu,nv,nw] or None)"""
+    nu, nv, nw = (int(s) for s in shape)
+    dev = ws.device
+    dist = torch.empty(max(nu, 0), max(nv, 0), max(nw, 0), device=dev)
+    tri = torch.empty(max(nu, 0), max(nv, 0), max(nw, 0), dtype=torch.int32, device=dev) if want_tri else None
+    with _Timed('closest_grid'):
+        _lib.check(_lib.closest_lib().durf_closest_grid(_stream(), nu, nv, nw, _host_floats(origin, 3, 'origin'), _host_floats(du, 3, 'du'),
+                                                        _host_floats(dv, 3, 'dv'), _host_floats(dw, 3, 'dw'), float(max_dist), int(T),
+                                                        _p(ws), ws.numel(), _p(dist), _p(tri)), 'durf_closest_grid')
+    return dist, tri
