@@ -3,67 +3,10 @@
 // header defines the result as a minimum over all triangles and proves that no tree can change it; the kernels follow it.  No
 // atomics, nothing synchronises or copies to the host, no workgroup waits for another.
 #include <climits>
-#include "workspace.h"
+#include "cast_tree.h"
 #include "camera.h"
-#include "../../include/durf_cast.h"
 
-#define CB DURF_CAST_BLOCK
-#define CLEAF DURF_CAST_LEAF
-#define CREC DURF_CAST_RECORD_FLOATS
-#define CNODE DURF_CAST_NODE_FLOATS
-#define CSTACK DURF_CAST_STACK
-static_assert(CB == 256 && CLEAF == 4 && CREC == 10 && CNODE == 8 && CSTACK == 32 && DURF_CAST_TOP == CB, "the layouts the header states");
 static_assert(DURF_CAST_KEY_BITS == 21, "three axes in 63 bits");
-
-// the implicit tree of T triangles: n(k) nodes on level k (0: the leaves), stored from node off[k]; the root is level K
-struct CastTree {
-    int T, K, n0;
-    int off[CSTACK];
-    int nodes;                         // off[K] + 1, 0 for T == 0
-    __host__ __device__ int n(int k) const { return (int)(((long long)n0 + ((1ll << k) - 1)) >> k); }      // ceil halved k times
-};
-
-// the level offsets in LDS, where a thread indexes them by its own level (a by-value argument indexed so would go to scratch)
-__device__ __forceinline__ void cast_offsets_to_lds(const CastTree& R, int* s_off) {
-    if (threadIdx.x < CSTACK) s_off[threadIdx.x] = R.off[threadIdx.x];
-    __syncthreads();
-}
-
-struct CastBox { float lo[3], hi[3]; };
-
-__device__ __forceinline__ CastBox cast_empty_box() {
-    const float inf = __builtin_inff();
-    return CastBox{{inf, inf, inf}, {-inf, -inf, -inf}};
-}
-
-__device__ __forceinline__ CastBox cast_load_box(const float* nodes, int i) {
-    const float4 a = *(const float4*)(nodes + (size_t)i * CNODE), b = *(const float4*)(nodes + (size_t)i * CNODE + 4);
-    return CastBox{{a.x, a.y, a.z}, {b.x, b.y, b.z}};
-}
-
-__device__ __forceinline__ void cast_store_box(float* nodes, int i, const CastBox& B) {
-    *(float4*)(nodes + (size_t)i * CNODE) = make_float4(B.lo[0], B.lo[1], B.lo[2], 0.0f);
-    *(float4*)(nodes + (size_t)i * CNODE + 4) = make_float4(B.hi[0], B.hi[1], B.hi[2], 0.0f);
-}
-
-__device__ __forceinline__ void cast_union(CastBox& B, const CastBox& C) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        B.lo[a] = fminf(B.lo[a], C.lo[a]);
-        B.hi[a] = fmaxf(B.hi[a], C.hi[a]);
-    }
-}
-
-// the box of a triangle: min and max per axis, one ulp outward
-__device__ __forceinline__ CastBox cast_tri_box(const float* A, const float* B, const float* C) {
-    CastBox X;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        X.lo[a] = nextafterf(fminf(fminf(A[a], B[a]), C[a]), -__builtin_inff());
-        X.hi[a] = nextafterf(fmaxf(fmaxf(A[a], B[a]), C[a]), __builtin_inff());
-    }
-    return X;
-}
 
 // a valid triangle's vertices; false for an id outside 0 .. T-1, an index outside 0 .. V-1 or a coordinate that is not finite
 __device__ __forceinline__ bool cast_fetch(int id, int V, int T, const float* __restrict__ vertices, const int32_t* __restrict__ triangles,
@@ -232,59 +175,29 @@ struct CastHit {
     float t, u, v, w;
 };
 
-// Nodes are numbered as a heap: the root is 1, the children of h are 2 h and 2 h + 1, so a node of depth D = floor(log2 h) is
-// node h - 2^D of level K - D.  `stack` is this thread's column of the workgroup's LDS array, CB ints apart.
+// the two queries of a ray: the nearest counting triangle by (t, id), or whether any counts (ANY: no prune by t, done at the first)
+template <bool ANY>
+struct CastQuery {
+    const CastRay& r;
+    int cull;
+    CastHit best;
+    __device__ __forceinline__ bool enter(const CastBox& B, float& bn) {
+        float bf;
+        return cast_box_rule(r, B, bn, bf) && (ANY || !(bn > best.t));
+    }
+    __device__ __forceinline__ bool leaf(const float* P, int id) {
+        float t, u, v, w;
+        if (cast_triangle(r, cull, P, t, u, v, w) && (t < best.t || (t == best.t && id < best.tri) || best.tri < 0)) best = CastHit{id, t, u, v, w};
+        return ANY && best.tri >= 0;
+    }
+};
+
 template <bool ANY>
 __device__ __forceinline__ CastHit cast_walk(const CastTree& R, const float* __restrict__ records, const float* __restrict__ nodes,
                                              const CastRay& r, int cull, int* stack, const int* s_off) {
-    CastHit best{-1, __builtin_inff(), 0.0f, 0.0f, 0.0f};
-    if (R.nodes == 0) return best;
-    int sp = 0, cur = 0;
-    float bn, bf;
-    if (cast_box_rule(r, cast_load_box(nodes, s_off[R.K]), bn, bf)) cur = 1;
-    const long long max_steps = 4ll * R.nodes + 4;                           // every node is entered at most once, popped at most once
-    for (long long step = 0; step < max_steps && cur != 0; step++) {
-        const int depth = 31 - __clz(cur), k = R.K - depth;
-        if (k == 0) {
-            const int l = cur - (1 << depth);
-            const float* rec = records + (size_t)l * (CLEAF * CREC);
-#pragma unroll
-            for (int j = 0; j < CLEAF; j++) {
-                float P[10];
-#pragma unroll
-                for (int c = 0; c < CREC; c += 2) {
-                    const float2 x = *(const float2*)(rec + j * CREC + c);
-                    P[c] = x.x;
-                    P[c + 1] = x.y;
-                }
-                const int id = __float_as_int(P[9]);
-                float t, u, v, w;
-                if (id >= 0 && cast_triangle(r, cull, P, t, u, v, w) && (t < best.t || (t == best.t && id < best.tri) || best.tri < 0))
-                    best = CastHit{id, t, u, v, w};
-            }
-            if (ANY && best.tri >= 0) return best;
-            cur = 0;
-        } else {
-            const int c0 = 2 * cur, j0 = c0 - (2 << depth), nb = R.n(k - 1), base = s_off[k - 1];
-            float bn0 = 0.0f, bn1 = 0.0f;
-            bool p0 = false, p1 = false;
-            if (j0 < nb) p0 = cast_box_rule(r, cast_load_box(nodes, base + j0), bn0, bf) && (ANY || !(bn0 > best.t));
-            if (j0 + 1 < nb) p1 = cast_box_rule(r, cast_load_box(nodes, base + j0 + 1), bn1, bf) && (ANY || !(bn1 > best.t));
-            if (p0 && p1) {
-                const bool swap = bn1 < bn0;
-                if (sp < CSTACK) stack[(sp++) * CB] = swap ? c0 : c0 + 1;    // (one entry per level: sp <= K < CSTACK)
-                cur = swap ? c0 + 1 : c0;
-            } else {
-                cur = p0 ? c0 : p1 ? c0 + 1 : 0;
-            }
-        }
-        while (cur == 0 && sp > 0) {                                         // (bounded by sp)
-            const int h = stack[(--sp) * CB];
-            const int dh = 31 - __clz(h), kh = R.K - dh;
-            if (cast_box_rule(r, cast_load_box(nodes, s_off[kh] + (h - (1 << dh))), bn, bf) && (ANY || !(bn > best.t))) cur = h;
-        }
-    }
-    return best;
+    CastQuery<ANY> q{r, cull, CastHit{-1, __builtin_inff(), 0.0f, 0.0f, 0.0f}};
+    cast_tree_walk(R, records, nodes, q, stack, s_off);
+    return q.best;
 }
 
 __device__ __forceinline__ void cast_write(const CastHit& hit, bool usable, size_t i, int32_t* __restrict__ tri, float* __restrict__ t,
@@ -355,57 +268,6 @@ k_cast_cameras(const CastTree R, int F, int h, int w, const float* __restrict__ 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------------
 namespace {
 
-struct CastWs {
-    float *records, *nodes;
-    size_t total;
-};
-
-bool cast_t_ok(int T) { return T >= 0 && T < DURF_CAST_MAX_TRIANGLES; }
-
-CastTree cast_tree(int T) {
-    CastTree R{};
-    R.T = T;
-    if (T == 0) return R;
-    int n = (int)durf_cdiv((size_t)T, CLEAF), off = 0, k = 0;
-    R.n0 = n;
-    for (;; k++) {                                                           // n_0 <= 2^28: at most 29 levels
-        R.off[k] = off;
-        off += n;
-        if (n == 1) break;
-        n = (n + 1) / 2;
-    }
-    R.K = k;
-    R.nodes = off;
-    return R;
-}
-
-CastWs carve_cast(void* base, const CastTree& R) {
-    durf::Carver c{(char*)base, 0};
-    CastWs w{};
-    const size_t slots = R.T == 0 ? 0 : (size_t)R.n0 * CLEAF;
-    w.records = (float*)c.take(slots * CREC * 4);
-    w.nodes = (float*)c.take((size_t)R.nodes * CNODE * 4);
-    w.total = c.total() > 256 ? c.total() : 256;
-    return w;
-}
-
-int check_cast_t(const char* who, int T) {
-    if (!cast_t_ok(T)) {
-        durf_set_error("%s: requirement failed: 0 <= T < %d, T = %d", who, DURF_CAST_MAX_TRIANGLES, T);
-        return -1;
-    }
-    return 0;
-}
-
-int check_cast_ws(const char* who, const void* workspace, size_t workspace_bytes, const CastTree& R, CastWs* ws) {
-    if (workspace == nullptr || ((size_t)workspace & 255) != 0) {
-        durf_set_error("%s: requirement failed: workspace aligned to 256 bytes", who);
-        return -1;
-    }
-    *ws = carve_cast((void*)workspace, R);
-    return durf::check_workspace(who, workspace_bytes, ws->total, "durf_cast_workspace_bytes(%d)", R.T);
-}
-
 int check_cast_mesh(const char* who, int V, int T, const float* vertices, const int32_t* triangles) {
     if (!(V >= 0)) { durf_set_error("%s: requirement failed: V >= 0, V = %d", who, V); return -1; }
     if (check_cast_t(who, T) != 0) return -1;
@@ -446,7 +308,7 @@ extern "C" {
 
 size_t durf_cast_workspace_bytes(int T) {
     if (!cast_t_ok(T)) return 0;
-    return carve_cast(nullptr, cast_tree(T)).total;
+    return cast_carve(nullptr, cast_tree(T)).total;
 }
 
 int durf_cast_keys(void* stream, int V, int T, const float* vertices, const int32_t* triangles, const float* bounds, int64_t* keys) {

@@ -1,42 +1,20 @@
-// The closest point of a triangle mesh to arbitrary points (include/durf_closest.h; libdurf_closest.so): the second walk over the
-// implicit box tree that durf_cast_build leaves (include/durf_cast.h documents the workspace; csrc/cast.hip writes it) -- nearest
-// by distance to a point instead of nearest along a ray.  The header defines the result as a minimum over all triangles and
-// proves that no tree can change it; the kernels follow it.  This file reads the workspace and writes its outputs, nothing
-// else: no atomics, nothing synchronises or copies to the host, no workgroup waits for another.
+// The closest point of a triangle mesh to arbitrary points (include/durf_closest.h; libdurf_closest.so): the second query of the
+// implicit box tree that durf_cast_build leaves (cast_tree.h holds the tree, its workspace and the walk; csrc/cast.hip writes it)
+// -- nearest by distance to a point instead of nearest along a ray.  The header defines the result as a minimum over all
+// triangles and proves that no tree can change it; the kernels follow it.  This file reads the workspace and writes its outputs,
+// nothing else: no atomics, nothing synchronises or copies to the host, no workgroup waits for another.
 #include <cmath>
-#include "workspace.h"
+#include "cast_tree.h"
 #include "camera.h"
 #include "../../include/durf_closest.h"
 
-#define QB DURF_CLOSEST_BLOCK
-#define QSTACK DURF_CLOSEST_STACK
-#define QLEAF DURF_CAST_LEAF
-#define QREC DURF_CAST_RECORD_FLOATS
-#define QNODE DURF_CAST_NODE_FLOATS
-#define QBRICK DURF_CLOSEST_BRICK
-static_assert(QB == DURF_CAST_BLOCK && QSTACK == DURF_CAST_STACK, "one entry per level of durf_cast.h's tree");
-static_assert(QB == 256 && QLEAF == 4 && QREC == 10 && QNODE == 8 && QSTACK == 32, "the layouts durf_cast.h states");
-static_assert(QBRICK * QBRICK * QBRICK == 64 && QB % 64 == 0, "a brick per wave");
-
-// durf_cast.h's implicit tree of T triangles: n(k) nodes on level k (0: the leaves), stored from node off[k]; the root is level K
-struct ClosestTree {
-    int T, K, n0;
-    int off[QSTACK];
-    int nodes;                         // off[K] + 1, 0 for T == 0
-    __host__ __device__ int n(int k) const { return (int)(((long long)n0 + ((1ll << k) - 1)) >> k); }      // ceil halved k times
-};
-
-struct ClosestBox { float lo[3], hi[3]; };
-
-__device__ __forceinline__ ClosestBox closest_load_box(const float* nodes, int i) {
-    const float4 a = *(const float4*)(nodes + (size_t)i * QNODE), b = *(const float4*)(nodes + (size_t)i * QNODE + 4);
-    return ClosestBox{{a.x, a.y, a.z}, {b.x, b.y, b.z}};
-}
+static_assert(DURF_CLOSEST_BLOCK == CB && DURF_CLOSEST_STACK == CSTACK, "the walk's workgroup and its one stack entry per level");
+static_assert(DURF_CLOSEST_BRICK * DURF_CLOSEST_BRICK * DURF_CLOSEST_BRICK == 64 && CB % 64 == 0, "a brick per wave");
 
 __device__ __forceinline__ float closest_dot(const float* x, const float* y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
 
 // the box bound: +inf for the empty box by the formula itself
-__device__ __forceinline__ float closest_bound(const float* P, const ClosestBox& B) {
+__device__ __forceinline__ float closest_bound(const float* P, const CastBox& B) {
     float e[3];
 #pragma unroll
     for (int a = 0; a < 3; a++) e[a] = fmaxf(fmaxf(B.lo[a] - P[a], P[a] - B.hi[a]), 0.0f);
@@ -67,7 +45,6 @@ __device__ __forceinline__ float closest_clamped(float num, float den) { return 
 __device__ __forceinline__ ClosestBest closest_triangle(const float* P, const float* V) {
     const float *A = V, *B = V + 3, *C = V + 6;
     float e1[3], e2[3], s[3], f[3], r[3];
-    ClosestBox X;
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         e1[k] = B[k] - A[k];
@@ -75,8 +52,6 @@ __device__ __forceinline__ ClosestBest closest_triangle(const float* P, const fl
         s[k] = P[k] - A[k];
         f[k] = C[k] - B[k];
         r[k] = P[k] - B[k];
-        X.lo[k] = nextafterf(fminf(fminf(A[k], B[k]), C[k]), -__builtin_inff());
-        X.hi[k] = nextafterf(fmaxf(fmaxf(A[k], B[k]), C[k]), __builtin_inff());
     }
     const float a = closest_dot(e1, e1), b = closest_dot(e1, e2), c = closest_dot(e2, e2), d = closest_dot(e1, s), e = closest_dot(e2, s);
     const float l = closest_dot(f, f), g = closest_dot(f, r);
@@ -92,82 +67,38 @@ __device__ __forceinline__ ClosestBest closest_triangle(const float* P, const fl
     closest_candidate(P, A, e1, e2, 1.0f - x, 0.0f, x, best);
     x = closest_clamped(g, l);
     closest_candidate(P, A, e1, e2, 0.0f, 1.0f - x, x, best);
-    best.d2 = fmaxf(best.d2, closest_bound(P, X)) + 0.0f;
+    best.d2 = fmaxf(best.d2, closest_bound(P, cast_tri_box(A, B, C))) + 0.0f;
     return best;
 }
 
-// Nodes are numbered as a heap (csrc/cast.hip): the root is 1, the children of h are 2 h and 2 h + 1, so a node of depth D =
-// floor(log2 h) is node h - 2^D of level K - D.  `stack` is this thread's column of the workgroup's LDS array, QB ints apart.
-// A node is skipped for lb > cap2 or lb > best.d2, strictly.
-__device__ __forceinline__ ClosestBest closest_walk(const ClosestTree& R, const float* __restrict__ records, const float* __restrict__ nodes,
-                                                    const float* P, float cap2, int* stack, const int* s_off) {
-    ClosestBest best{-1, __builtin_inff(), 0.0f, 0.0f, 0.0f, {0.0f, 0.0f, 0.0f}};
-    if (R.nodes == 0) return best;
-    int sp = 0, cur = 0;
-    if (!(closest_bound(P, closest_load_box(nodes, s_off[R.K])) > cap2)) cur = 1;
-    const long long max_steps = 4ll * R.nodes + 4;                           // every node is entered at most once, popped at most once
-    for (long long step = 0; step < max_steps && cur != 0; step++) {
-        const int depth = 31 - __clz(cur), k = R.K - depth;
-        if (k == 0) {
-            const int l = cur - (1 << depth);
-            const float* rec = records + (size_t)l * (QLEAF * QREC);
-#pragma unroll
-            for (int j = 0; j < QLEAF; j++) {
-                float V[10];
-#pragma unroll
-                for (int c = 0; c < QREC; c += 2) {
-                    const float2 x = *(const float2*)(rec + j * QREC + c);
-                    V[c] = x.x;
-                    V[c + 1] = x.y;
-                }
-                const int id = __float_as_int(V[9]);
-                if (id >= 0) {
-                    ClosestBest t = closest_triangle(P, V);
-                    if (t.d2 <= cap2 && (t.d2 < best.d2 || (t.d2 == best.d2 && id < best.tri) || best.tri < 0)) {
-                        best = t;
-                        best.tri = id;
-                    }
-                }
-            }
-            cur = 0;
-        } else {
-            const int c0 = 2 * cur, j0 = c0 - (2 << depth), nb = R.n(k - 1), base = s_off[k - 1];
-            float lb0 = 0.0f, lb1 = 0.0f;
-            bool p0 = false, p1 = false;
-            if (j0 < nb) {
-                lb0 = closest_bound(P, closest_load_box(nodes, base + j0));
-                p0 = !(lb0 > cap2) && !(lb0 > best.d2);
-            }
-            if (j0 + 1 < nb) {
-                lb1 = closest_bound(P, closest_load_box(nodes, base + j0 + 1));
-                p1 = !(lb1 > cap2) && !(lb1 > best.d2);
-            }
-            if (p0 && p1) {
-                const bool swap = lb1 < lb0;
-                if (sp < QSTACK) stack[(sp++) * QB] = swap ? c0 : c0 + 1;    // (one entry per level: sp <= K < QSTACK)
-                cur = swap ? c0 + 1 : c0;
-            } else {
-                cur = p0 ? c0 : p1 ? c0 + 1 : 0;
-            }
-        }
-        while (cur == 0 && sp > 0) {                                         // (bounded by sp)
-            const int h = stack[(--sp) * QB];
-            const int dh = 31 - __clz(h), kh = R.K - dh;
-            const float lb = closest_bound(P, closest_load_box(nodes, s_off[kh] + (h - (1 << dh))));
-            if (!(lb > cap2) && !(lb > best.d2)) cur = h;
-        }
+// the query of a point: the nearest triangle within cap2 by (d2, id).  A node is skipped for lb > cap2 or lb > best.d2, strictly.
+struct ClosestQuery {
+    const float* P;
+    float cap2;
+    ClosestBest best;
+    __device__ __forceinline__ bool enter(const CastBox& B, float& lb) {
+        lb = closest_bound(P, B);
+        return !(lb > cap2) && !(lb > best.d2);
     }
-    return best;
-}
+    __device__ __forceinline__ bool leaf(const float* V, int id) {
+        ClosestBest t = closest_triangle(P, V);
+        if (t.d2 <= cap2 && (t.d2 < best.d2 || (t.d2 == best.d2 && id < best.tri) || best.tri < 0)) {
+            best = t;
+            best.tri = id;
+        }
+        return false;
+    }
+};
 
 // the query of one thread, from the point to its outputs at index i (tri, bary, point: nullable)
-__device__ __forceinline__ void closest_query(const ClosestTree& R, const float* __restrict__ records, const float* __restrict__ nodes,
+__device__ __forceinline__ void closest_query(const CastTree& R, const float* __restrict__ records, const float* __restrict__ nodes,
                                               const float* P, float max_dist, int* stack, const int* s_off, size_t i,
                                               int32_t* __restrict__ tri, float* __restrict__ dist, float* __restrict__ bary,
                                               float* __restrict__ point) {
     const bool usable = cam_finite(P[0]) && cam_finite(P[1]) && cam_finite(P[2]);
-    ClosestBest hit{-1, 0.0f, 0.0f, 0.0f, 0.0f, {0.0f, 0.0f, 0.0f}};
-    if (usable) hit = closest_walk(R, records, nodes, P, max_dist * max_dist, stack, s_off);
+    ClosestQuery q{P, max_dist * max_dist, ClosestBest{-1, __builtin_inff(), 0.0f, 0.0f, 0.0f, {0.0f, 0.0f, 0.0f}}};
+    if (usable) cast_tree_walk(R, records, nodes, q, stack, s_off);
+    const ClosestBest& hit = q.best;
     const float nan = __builtin_nanf("");
     const bool found = usable && hit.tri >= 0;
     if (tri) tri[i] = !usable ? -2 : found ? hit.tri : -1;
@@ -183,20 +114,14 @@ __device__ __forceinline__ void closest_query(const ClosestTree& R, const float*
     }
 }
 
-// the level offsets in LDS, where a thread indexes them by its own level (a by-value argument indexed so would go to scratch)
-__device__ __forceinline__ void closest_offsets_to_lds(const ClosestTree& R, int* s_off) {
-    if (threadIdx.x < QSTACK) s_off[threadIdx.x] = R.off[threadIdx.x];
-    __syncthreads();
-}
-
-__global__ void __launch_bounds__(QB)
-k_closest_points(const ClosestTree R, int n, const float* __restrict__ points, float max_dist, const float* __restrict__ records,
+__global__ void __launch_bounds__(CB)
+k_closest_points(const CastTree R, int n, const float* __restrict__ points, float max_dist, const float* __restrict__ records,
                  const float* __restrict__ nodes, int32_t* __restrict__ tri, float* __restrict__ dist, float* __restrict__ bary,
                  float* __restrict__ point) {
-    __shared__ int s_stack[QSTACK * QB];
-    __shared__ int s_off[QSTACK];
-    closest_offsets_to_lds(R, s_off);
-    const int i = blockIdx.x * QB + threadIdx.x;
+    __shared__ int s_stack[CSTACK * CB];
+    __shared__ int s_off[CSTACK];
+    cast_offsets_to_lds(R, s_off);
+    const int i = blockIdx.x * CB + threadIdx.x;
     if (i >= n) return;                                                      // (no barrier below)
     const float P[3] = {points[(size_t)i * 3], points[(size_t)i * 3 + 1], points[(size_t)i * 3 + 2]};
     closest_query(R, records, nodes, P, max_dist, s_stack + threadIdx.x, s_off, (size_t)i, tri, dist, bary, point);
@@ -209,18 +134,18 @@ struct ClosestLattice {
 };
 
 // a wave per brick of 4 x 4 x 4 lattice points: lane = (di 4 + dj) 4 + dk
-__global__ void __launch_bounds__(QB)
-k_closest_grid(const ClosestTree R, const ClosestLattice G, float max_dist, const float* __restrict__ records, const float* __restrict__ nodes,
+__global__ void __launch_bounds__(CB)
+k_closest_grid(const CastTree R, const ClosestLattice G, float max_dist, const float* __restrict__ records, const float* __restrict__ nodes,
                float* __restrict__ dist, int32_t* __restrict__ tri) {
-    __shared__ int s_stack[QSTACK * QB];
-    __shared__ int s_off[QSTACK];
-    closest_offsets_to_lds(R, s_off);
-    const long long brick = (long long)blockIdx.x * (QB / 64) + threadIdx.x / 64;
+    __shared__ int s_stack[CSTACK * CB];
+    __shared__ int s_off[CSTACK];
+    cast_offsets_to_lds(R, s_off);
+    const long long brick = (long long)blockIdx.x * (CB / 64) + threadIdx.x / 64;
     if (brick >= G.bricks) return;                                           // (no barrier below)
     const int lane = threadIdx.x % 64;
     const long long bu = brick / ((long long)G.bv * G.bw);
     const int rest = (int)(brick - bu * ((long long)G.bv * G.bw));
-    const int i = (int)bu * QBRICK + lane / 16, j = (rest / G.bw) * QBRICK + lane / 4 % 4, k = (rest % G.bw) * QBRICK + lane % 4;
+    const int i = (int)bu * DURF_CLOSEST_BRICK + lane / 16, j = (rest / G.bw) * DURF_CLOSEST_BRICK + lane / 4 % 4, k = (rest % G.bw) * DURF_CLOSEST_BRICK + lane % 4;
     if (i >= G.nu || j >= G.nv || k >= G.nw) return;
     float P[3];
 #pragma unroll
@@ -232,57 +157,15 @@ k_closest_grid(const ClosestTree R, const ClosestLattice G, float max_dist, cons
 // ---- launchers ----------------------------------------------------------------------------------------------------------------------
 namespace {
 
-struct ClosestWs {
-    const float *records, *nodes;
-    size_t total;
-};
-
-// durf_cast.h: n_0 = ceil(T / L) leaves, n_{k+1} = ceil(n_k / 2) until a level has one node, level 0 first
-ClosestTree closest_tree(int T) {
-    ClosestTree R{};
-    R.T = T;
-    if (T == 0) return R;
-    int n = (int)durf_cdiv((size_t)T, QLEAF), off = 0, k = 0;
-    R.n0 = n;
-    for (;; k++) {                                                           // n_0 <= 2^28: at most 29 levels
-        R.off[k] = off;
-        off += n;
-        if (n == 1) break;
-        n = (n + 1) / 2;
-    }
-    R.K = k;
-    R.nodes = off;
-    return R;
-}
-
-// durf_cast.h: the records, then the nodes, each on a 256-byte boundary; 256 bytes for T == 0
-ClosestWs closest_carve(const void* base, const ClosestTree& R) {
-    durf::Carver c{(char*)base, 0};
-    ClosestWs w{};
-    const size_t slots = R.T == 0 ? 0 : (size_t)R.n0 * QLEAF;
-    w.records = (const float*)c.take(slots * QREC * 4);
-    w.nodes = (const float*)c.take((size_t)R.nodes * QNODE * 4);
-    w.total = c.total() > 256 ? c.total() : 256;
-    return w;
-}
-
 // T, max_dist and the workspace, in this order
-int closest_check(const char* who, float max_dist, int T, const void* workspace, size_t workspace_bytes, ClosestTree* R, ClosestWs* ws) {
-    if (!(T >= 0 && T < DURF_CAST_MAX_TRIANGLES)) {
-        durf_set_error("%s: requirement failed: 0 <= T < %d, T = %d", who, DURF_CAST_MAX_TRIANGLES, T);
-        return -1;
-    }
+int closest_check(const char* who, float max_dist, int T, const void* workspace, size_t workspace_bytes, CastTree* R, CastWs* ws) {
+    if (check_cast_t(who, T) != 0) return -1;
     if (!(max_dist == __builtin_inff() || (max_dist >= 1e-18f && max_dist <= 1e18f))) {
         durf_set_error("%s: requirement failed: max_dist is +inf or in [1e-18, 1e18], max_dist = %g", who, (double)max_dist);
         return -1;
     }
-    if (workspace == nullptr || ((size_t)workspace & 255) != 0) {
-        durf_set_error("%s: requirement failed: workspace aligned to 256 bytes", who);
-        return -1;
-    }
-    *R = closest_tree(T);
-    *ws = closest_carve(workspace, *R);
-    return durf::check_workspace(who, workspace_bytes, ws->total, "durf_cast_workspace_bytes(%d)", T);
+    *R = cast_tree(T);
+    return check_cast_ws(who, workspace, workspace_bytes, *R, ws);
 }
 
 }  // namespace
@@ -292,13 +175,13 @@ extern "C" {
 int durf_closest_points(void* stream, int n, const float* points, float max_dist, int T, const void* workspace, size_t workspace_bytes,
                         int32_t* tri, float* dist, float* bary, float* point) {
     if (!(n >= 0)) { durf_set_error("%s: requirement failed: n >= 0, n = %d", __func__, n); return -1; }
-    ClosestTree R;
-    ClosestWs ws;
+    CastTree R;
+    CastWs ws;
     if (closest_check(__func__, max_dist, T, workspace, workspace_bytes, &R, &ws) != 0) return -1;
     if (!(points || n == 0)) { durf_set_error("%s: requirement failed: points for n = %d", __func__, n); return -1; }
     if (!((tri && dist) || n == 0)) { durf_set_error("%s: requirement failed: tri and dist for n = %d", __func__, n); return -1; }
     if (n == 0) return 0;
-    hipLaunchKernelGGL(k_closest_points, dim3(durf_cdiv((size_t)n, QB)), dim3(QB), 0, (hipStream_t)stream, R, n, points, max_dist, ws.records,
+    hipLaunchKernelGGL(k_closest_points, dim3(durf_cdiv((size_t)n, CB)), dim3(CB), 0, (hipStream_t)stream, R, n, points, max_dist, ws.records,
                        ws.nodes, tri, dist, bary, point);
     DURF_CHECK_LAUNCH("k_closest_points");
     return 0;
@@ -322,14 +205,14 @@ int durf_closest_grid(void* stream, int nu, int nv, int nw, const float* origin,
         finite = finite && std::isfinite(origin[c]) && std::isfinite(du[c]) && std::isfinite(dv[c]) && std::isfinite(dw[c]);
     }
     if (!finite) { durf_set_error("%s: requirement failed: origin, du, dv and dw are finite", __func__); return -1; }
-    ClosestTree R;
-    ClosestWs ws;
+    CastTree R;
+    CastWs ws;
     if (closest_check(__func__, max_dist, T, workspace, workspace_bytes, &R, &ws) != 0) return -1;
     if (!dist) { durf_set_error("%s: requirement failed: dist for %d x %d x %d points", __func__, nu, nv, nw); return -1; }
     G.nu = nu, G.nv = nv, G.nw = nw;
-    G.bv = (int)durf_cdiv((size_t)nv, QBRICK), G.bw = (int)durf_cdiv((size_t)nw, QBRICK);
-    G.bricks = (long long)durf_cdiv((size_t)nu, QBRICK) * G.bv * G.bw;       // at most 16 nu nv nw / 64 < 2^29
-    hipLaunchKernelGGL(k_closest_grid, dim3(durf_cdiv((size_t)G.bricks, QB / 64)), dim3(QB), 0, (hipStream_t)stream, R, G, max_dist, ws.records,
+    G.bv = (int)durf_cdiv((size_t)nv, DURF_CLOSEST_BRICK), G.bw = (int)durf_cdiv((size_t)nw, DURF_CLOSEST_BRICK);
+    G.bricks = (long long)durf_cdiv((size_t)nu, DURF_CLOSEST_BRICK) * G.bv * G.bw;       // at most 16 nu nv nw / 64 < 2^29
+    hipLaunchKernelGGL(k_closest_grid, dim3(durf_cdiv((size_t)G.bricks, CB / 64)), dim3(CB), 0, (hipStream_t)stream, R, G, max_dist, ws.records,
                        ws.nodes, dist, tri);
     DURF_CHECK_LAUNCH("k_closest_grid");
     return 0;

@@ -1,7 +1,8 @@
 """The oracle of include/durf_cast.h in numpy.  cast32: brute force over rays x triangles in float32, every operation in the
 header's order (numpy's float32 ufuncs round each operation once and fuse nothing).  cast64: the float64 twin without box rule
-or clamp.  bvh32: the same implicit tree as csrc/cast.hip with the same walk, vectorised over rays -- by the header's proof it
-equals cast32 in every bit, which tests/test_cast_host.py exercises.  keys: the Morton key rule.  Scenes shared by the tests."""
+or clamp.  tree_walk32: csrc/cast_tree.h's implicit tree and its one walk, vectorised over queries; bvh32: the rays' box and
+triangle rules on it -- by the header's proof it equals cast32 in every bit, which tests/test_cast_host.py exercises.  keys: the
+Morton key rule.  Scenes shared by the tests."""
 import functools
 
 import numpy as np
@@ -225,27 +226,24 @@ def _depth(h):
     return np.frexp(h.astype(np.float64))[1].astype(np.int64) - 1
 
 
-def bvh32(vertices, triangles, order, o, d, tmin=0.0, tmax=np.inf, cull=0, any_hit=False, stats=None):
-    """csrc/cast.hip's walk of the implicit tree over `order`, every ray at its own pace -> cast32's outputs (any_hit: hit int32
-    [n]).  stats: a dict that receives nodes and leaves [n], the node boxes tested and the leaves entered per ray."""
-    tree = build_tree(vertices, triangles, order)
-    R = ray_setup(o, d, tmin, tmax)
-    n = R['o'].shape[0]
-    best_id, best_t, best_b = np.full(n, -1, np.int64), np.full(n, INF), np.zeros((n, 3), F32)
+def tree_walk32(tree, usable, node_test, leaf_test, any_hit=False, stats=None):
+    """csrc/cast_tree.h's walk of build_tree's tree, every usable query at its own pace; the caller keeps each query's best.
+    node_test(q, node) -> (enter bool [m], key [m]): the box rule with the prune against the best of queries q at their nodes;
+    leaf_test(q, slot) -> found bool [m]: the triangle rule on the records `slot`, after which it says which of q hold a winner.
+    any_hit: a query that has found something is done with the leaf.  stats: a dict that receives nodes and leaves [n], the node
+    boxes tested and the leaves entered per query."""
+    n = usable.shape[0]
     n_nodes, n_leaves = np.zeros(n, np.int64), np.zeros(n, np.int64)
+
+    def enter(q, node):
+        n_nodes[q] += 1
+        return node_test(q, node)
+
     if tree['T'] > 0:
         K, nk, off = tree['K'], tree['n'], tree['off']
-
-        def node_test(rays, node):
-            n_nodes[rays] += 1
-            ok, bn, _ = box_rule(tree['lo'][node], tree['hi'][node], R['o'][rays], R['inv'][rays], R['zero'][rays], R['tmin'][rays], R['tmax'][rays])
-            if not any_hit:
-                ok = ok & ~(bn > best_t[rays])
-            return ok, bn
-
         cur, sp, stack = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros((n, STACK), np.int64)
-        us = np.nonzero(R['usable'])[0]
-        ok, _ = node_test(us, np.full(len(us), off[K]))
+        us = np.nonzero(usable)[0]
+        ok, _ = enter(us, np.full(len(us), off[K]))
         cur[us[ok]] = 1
         while (cur != 0).any():
             act = np.nonzero(cur != 0)[0]
@@ -254,37 +252,30 @@ def bvh32(vertices, triangles, order, o, d, tmin=0.0, tmax=np.inf, cull=0, any_h
             k = K - depth
             leaf = k == 0
             if leaf.any():
-                rays, l = act[leaf], h[leaf] - (1 << depth[leaf])
-                n_leaves[rays] += 1
+                q, l = act[leaf], h[leaf] - (1 << depth[leaf])
+                n_leaves[q] += 1
                 for j in range(LEAF):
-                    slot = l * LEAF + j
-                    ids = tree['rec_id'][slot]
-                    okt, t, u, v, w, _ = tri_rule(tree['rec_P'][slot], R['o'][rays], R['d'][rays], R['inv'][rays], R['zero'][rays],
-                                                  R['tmin'][rays], R['tmax'][rays], cull)
-                    better = okt & (ids >= 0) & ((t < best_t[rays]) | ((t == best_t[rays]) & (ids < best_id[rays])) | (best_id[rays] < 0))
-                    rb = rays[better]
-                    best_id[rb], best_t[rb], best_b[rb] = ids[better], t[better], np.stack([w, u, v], 1)[better]
-                cur[rays] = 0
+                    found = leaf_test(q, l * LEAF + j)
+                cur[q] = 0
                 if any_hit:
-                    sp[rays[best_id[rays] >= 0]] = 0
+                    sp[q[found]] = 0
             inner = ~leaf
             if inner.any():
-                rays, hh, dd, kk = act[inner], h[inner], depth[inner], k[inner]
+                q, hh, dd, kk = act[inner], h[inner], depth[inner], k[inner]
                 c0 = 2 * hh
                 j0 = c0 - (2 << dd)
                 nb, base = nk[kk - 1], off[kk - 1]
-                p, bn = [np.zeros(len(rays), bool), np.zeros(len(rays), bool)], [np.zeros(len(rays), F32), np.zeros(len(rays), F32)]
+                p, key = [np.zeros(len(q), bool), np.zeros(len(q), bool)], [np.zeros(len(q), F32), np.zeros(len(q), F32)]
                 for c in (0, 1):
                     ex = j0 + c < nb
-                    okc, bnc = node_test(rays[ex], (base + j0 + c)[ex])
-                    p[c][ex], bn[c][ex] = okc, bnc
+                    p[c][ex], key[c][ex] = enter(q[ex], (base + j0 + c)[ex])
                 both = p[0] & p[1]
-                swap = bn[1] < bn[0]
-                rb = rays[both]
-                stack[rb, sp[rb]] = np.where(swap, c0, c0 + 1)[both]
-                sp[rb] += 1
+                swap = key[1] < key[0]
+                qb = q[both]
+                stack[qb, sp[qb]] = np.where(swap, c0, c0 + 1)[both]
+                sp[qb] += 1
                 assert (sp <= STACK).all()
-                cur[rays] = np.where(both, np.where(swap, c0 + 1, c0), np.where(p[0], c0, np.where(p[1], c0 + 1, 0)))
+                cur[q] = np.where(both, np.where(swap, c0 + 1, c0), np.where(p[0], c0, np.where(p[1], c0 + 1, 0)))
             while True:
                 pop = np.nonzero((cur == 0) & (sp > 0))[0]
                 if not len(pop):
@@ -292,10 +283,34 @@ def bvh32(vertices, triangles, order, o, d, tmin=0.0, tmax=np.inf, cull=0, any_h
                 sp[pop] -= 1
                 hp = stack[pop, sp[pop]]
                 dp = _depth(hp)
-                ok, _ = node_test(pop, off[K - dp] + hp - (1 << dp))
+                ok, _ = enter(pop, off[K - dp] + hp - (1 << dp))
                 cur[pop[ok]] = hp[ok]
     if stats is not None:
         stats.update(nodes=n_nodes, leaves=n_leaves)
+
+
+def bvh32(vertices, triangles, order, o, d, tmin=0.0, tmax=np.inf, cull=0, any_hit=False, stats=None):
+    """csrc/cast.hip's queries of the implicit tree over `order` -> cast32's outputs (any_hit: hit int32 [n]).  stats: tree_walk32's."""
+    tree = build_tree(vertices, triangles, order)
+    R = ray_setup(o, d, tmin, tmax)
+    n = R['o'].shape[0]
+    best_id, best_t, best_b = np.full(n, -1, np.int64), np.full(n, INF), np.zeros((n, 3), F32)
+    ray = lambda rays: (R['o'][rays], R['inv'][rays], R['zero'][rays], R['tmin'][rays], R['tmax'][rays])
+
+    def node_test(rays, node):
+        ok, bn, _ = box_rule(tree['lo'][node], tree['hi'][node], *ray(rays))
+        return (ok if any_hit else ok & ~(bn > best_t[rays])), bn
+
+    def leaf_test(rays, slot):
+        ids = tree['rec_id'][slot]
+        o_, *rest = ray(rays)
+        okt, t, u, v, w, _ = tri_rule(tree['rec_P'][slot], o_, R['d'][rays], *rest, cull)
+        better = okt & (ids >= 0) & ((t < best_t[rays]) | ((t == best_t[rays]) & (ids < best_id[rays])) | (best_id[rays] < 0))
+        rb = rays[better]
+        best_id[rb], best_t[rb], best_b[rb] = ids[better], t[better], np.stack([w, u, v], 1)[better]
+        return best_id[rays] >= 0
+
+    tree_walk32(tree, R['usable'], node_test, leaf_test, any_hit, stats)
     best_t = np.where(best_id >= 0, best_t, F32(0))
     tri, t, bary = _finish(R, best_id, best_t, best_b)
     if any_hit:

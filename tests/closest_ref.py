@@ -1,7 +1,7 @@
 """The oracle of include/durf_closest.h in numpy.  closest32: brute force over points x triangles in float32, every operation
 in the header's order (numpy's float32 ufuncs round each operation once and fuse nothing).  closest64: the float64 twin without
-box bound or clamp, with the first-order error bound of the float32 formula.  walk32: csrc/closest.hip's walk of
-cast_ref.build_tree's implicit tree, vectorised over points -- by the header's proof it equals closest32 in every bit, which
+box bound or clamp, with the first-order error bound of the float32 formula.  walk32: csrc/closest.hip's box bound and
+triangle rule on cast_ref.tree_walk32's walk -- by the header's proof it equals closest32 in every bit, which
 tests/test_closest_host.py exercises.  Scenes shared by the tests."""
 import functools
 
@@ -193,8 +193,7 @@ def closest64(vertices, triangles, points, max_dist=np.inf):
 
 
 def walk32(vertices, triangles, order, points, max_dist=np.inf, stats=None):
-    """csrc/closest.hip's walk of the implicit tree over `order`, every point at its own pace -> closest32's outputs.  stats: a
-    dict that receives nodes and leaves [n], the node boxes tested and the leaves entered per point."""
+    """csrc/closest.hip's query of the implicit tree over `order` -> closest32's outputs.  stats: cast_ref.tree_walk32's."""
     tree = C.build_tree(vertices, triangles, order)
     P = _f(points).reshape(-1, 3)
     n = P.shape[0]
@@ -202,66 +201,21 @@ def walk32(vertices, triangles, order, points, max_dist=np.inf, stats=None):
     Pz = np.where(usable[:, None], P, F32(0))
     cap2 = cap2_of(max_dist)
     best_id, best_d2, best_w, best_c = np.full(n, -1, np.int64), np.full(n, INF), np.zeros((n, 3), F32), np.zeros((n, 3), F32)
-    n_nodes, n_leaves = np.zeros(n, np.int64), np.zeros(n, np.int64)
-    if tree['T'] > 0:
-        K, nk, off = tree['K'], tree['n'], tree['off']
 
-        def node_test(q, node):
-            n_nodes[q] += 1
-            lb = box_bound(tree['lo'][node], tree['hi'][node], Pz[q])
-            with np.errstate(invalid='ignore'):
-                return ~(lb > cap2) & ~(lb > best_d2[q]), lb
+    def node_test(q, node):
+        lb = box_bound(tree['lo'][node], tree['hi'][node], Pz[q])
+        with np.errstate(invalid='ignore'):
+            return ~(lb > cap2) & ~(lb > best_d2[q]), lb
 
-        cur, sp, stack = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros((n, C.STACK), np.int64)
-        us = np.nonzero(usable)[0]
-        ok, _ = node_test(us, np.full(len(us), off[K]))
-        cur[us[ok]] = 1
-        while (cur != 0).any():
-            act = np.nonzero(cur != 0)[0]
-            h = cur[act]
-            depth = C._depth(h)
-            k = K - depth
-            leaf = k == 0
-            if leaf.any():
-                q, l = act[leaf], h[leaf] - (1 << depth[leaf])
-                n_leaves[q] += 1
-                for j in range(C.LEAF):
-                    slot = l * C.LEAF + j
-                    ids = tree['rec_id'][slot]
-                    d2, w, c, _, _ = tri_rule(tree['rec_P'][slot], Pz[q])
-                    better = (ids >= 0) & (d2 <= cap2) & ((d2 < best_d2[q]) | ((d2 == best_d2[q]) & (ids < best_id[q])) | (best_id[q] < 0))
-                    qb = q[better]
-                    best_id[qb], best_d2[qb], best_w[qb], best_c[qb] = ids[better], d2[better], w[better], c[better]
-                cur[q] = 0
-            inner = ~leaf
-            if inner.any():
-                q, hh, dd, kk = act[inner], h[inner], depth[inner], k[inner]
-                c0 = 2 * hh
-                j0 = c0 - (2 << dd)
-                nb, base = nk[kk - 1], off[kk - 1]
-                p, lb = [np.zeros(len(q), bool), np.zeros(len(q), bool)], [np.zeros(len(q), F32), np.zeros(len(q), F32)]
-                for ch in (0, 1):
-                    ex = j0 + ch < nb
-                    okc, lbc = node_test(q[ex], (base + j0 + ch)[ex])
-                    p[ch][ex], lb[ch][ex] = okc, lbc
-                both = p[0] & p[1]
-                swap = lb[1] < lb[0]
-                qb = q[both]
-                stack[qb, sp[qb]] = np.where(swap, c0, c0 + 1)[both]
-                sp[qb] += 1
-                assert (sp <= C.STACK).all()
-                cur[q] = np.where(both, np.where(swap, c0 + 1, c0), np.where(p[0], c0, np.where(p[1], c0 + 1, 0)))
-            while True:
-                pop = np.nonzero((cur == 0) & (sp > 0))[0]
-                if not len(pop):
-                    break
-                sp[pop] -= 1
-                hp = stack[pop, sp[pop]]
-                dp = C._depth(hp)
-                ok, _ = node_test(pop, off[K - dp] + hp - (1 << dp))
-                cur[pop[ok]] = hp[ok]
-    if stats is not None:
-        stats.update(nodes=n_nodes, leaves=n_leaves)
+    def leaf_test(q, slot):
+        ids = tree['rec_id'][slot]
+        d2, w, c, _, _ = tri_rule(tree['rec_P'][slot], Pz[q])
+        better = (ids >= 0) & (d2 <= cap2) & ((d2 < best_d2[q]) | ((d2 == best_d2[q]) & (ids < best_id[q])) | (best_id[q] < 0))
+        qb = q[better]
+        best_id[qb], best_d2[qb], best_w[qb], best_c[qb] = ids[better], d2[better], w[better], c[better]
+        return best_id[q] >= 0
+
+    C.tree_walk32(tree, usable, node_test, leaf_test, stats=stats)
     return _finish(P, usable, max_dist, best_id, best_d2, best_w, best_c)
 
 

@@ -2,6 +2,8 @@
 the box rule's monotonicity, the float32 definition against its float64 twin, watertightness measured, the key rule, and the
 library's refusals (every argument is checked before anything is launched, so they need no device)."""
 import ctypes as C
+import json
+import os
 
 import numpy as np
 import pytest
@@ -25,6 +27,25 @@ def test_the_walk_of_any_tree_equals_brute_force_in_every_bit(name):
             assert np.array_equal(R.bits(a), R.bits(b)), (name, what, k)
     hit = R.bvh32(s['v'], s['t'], R.morton_order(s['v'], s['t']), s['o'], s['d'], s['tmin'], s['tmax'], s['cull'], any_hit=True)
     assert np.array_equal(hit, np.where(want[0] >= 0, 1, np.where(want[0] == -2, -2, 0)))
+
+
+def walk_counts():
+    """per scene and query, over the Morton order: [node boxes tested, leaves entered] summed over the scene's rays"""
+    out = {'nearest': {}, 'any': {}}
+    for name, s in sorted(R.scenes().items()):
+        order = R.morton_order(s['v'], s['t'])
+        for what in out:
+            stats = {}
+            R.bvh32(s['v'], s['t'], order, s['o'], s['d'], s['tmin'], s['tmax'], s['cull'], any_hit=what == 'any', stats=stats)
+            out[what][name] = [int(stats['nodes'].sum()), int(stats['leaves'].sum())]
+    return out
+
+
+def test_the_walk_visits_what_it_visited_before_the_walks_were_merged():
+    """the outputs cannot show a changed traversal (the header proves them independent of it); the counts can.
+    tests/golden/tree_walk_stats.json holds walk_counts() of this file and of tests/test_closest_host.py as the two separate
+    walks gave them, before cast_ref.tree_walk32 replaced both loops"""
+    assert walk_counts() == json.load(open(os.path.join(os.path.dirname(__file__), 'golden', 'tree_walk_stats.json')))['cast']
 
 
 def test_the_scenes_reach_what_they_are_for():

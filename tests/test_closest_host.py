@@ -2,6 +2,9 @@
 whatever the order the tree is built over), the box bound's monotonicity, lb_i <= d2_i, the float32 definition against its
 float64 twin, degenerate triangles, and the library's refusals (every argument is checked before anything is launched, so they
 need no device)."""
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -25,6 +28,21 @@ def test_the_walk_of_any_tree_equals_brute_force_in_every_bit(name):
     T = s['t'].shape[0]
     for what, order in (('morton', C.morton_order(s['v'], s['t'])), ('random', np.random.default_rng(3).permutation(T)), ('identity', np.arange(T))):
         _same(R.walk32(s['v'], s['t'], order, s['p'], s['max_dist']), want, (name, what))
+
+
+def walk_counts():
+    """per scene, over the Morton order: [node boxes tested, leaves entered] summed over the scene's points"""
+    out = {}
+    for name, s in sorted(R.scenes().items()):
+        stats = {}
+        R.walk32(s['v'], s['t'], C.morton_order(s['v'], s['t']), s['p'], s['max_dist'], stats=stats)
+        out[name] = [int(stats['nodes'].sum()), int(stats['leaves'].sum())]
+    return out
+
+
+def test_the_walk_visits_what_it_visited_before_the_walks_were_merged():
+    """tests/test_cast_host.py's test of this name says why; tests/golden/tree_walk_stats.json holds the counts"""
+    assert walk_counts() == json.load(open(os.path.join(os.path.dirname(__file__), 'golden', 'tree_walk_stats.json')))['closest']
 
 
 def test_the_scenes_reach_what_they_are_for():
