@@ -12,14 +12,9 @@ max_dist is looked for: such a point reports tri = -1 and dist = max_dist (geome
 takes the two arrays as they are); a point with a NaN or infinite coordinate reports -2 and NaN."""
 import numpy as np
 
+from . import lattice
+
 SORT_QUERIES = True                 # points()'s default: queries in the order of a Morton key of their own
-
-
-def _max_dist(max_dist, entry):
-    md = float(np.float32(max_dist))
-    if not (md == float('inf') or 1e-18 <= md <= 1e18):
-        raise ValueError('%s: max_dist = %r, expected +inf or a number in [1e-18, 1e18]' % (entry, max_dist))
-    return md
 
 
 def _tree(b, entry):
@@ -55,7 +50,7 @@ def points(b, p, max_dist=float('inf'), sort_queries=None):
     bool.  sort_queries (default SORT_QUERIES): hand the points over in the order of morton_keys, so that the lanes of a wave
     walk the same nodes, and scatter the results back -- the outputs are bit-identical either way."""
     entry = 'closest.points'
-    md = _max_dist(max_dist, entry)
+    md = lattice._max_dist(max_dist, entry, inf=True)
     _tree(b, entry)
     import torch
     from . import ops
@@ -99,20 +94,15 @@ def grid(b, origin, dims, step, max_dist=float('inf'), axes=None):
     what mesh.surface(g, iso) accepts -- a point is `in` when its distance is >= iso, so the surface at iso = r is the offset
     surface at distance r with normals towards the mesh."""
     entry = 'closest.grid'
-    md = _max_dist(max_dist, entry)
+    md = lattice._max_dist(max_dist, entry, inf=True)
     _tree(b, entry)
     dims = tuple(int(d) for d in np.asarray(dims).reshape(-1))
     if len(dims) != 3 or min(dims) < 1 or dims[0] * dims[1] * dims[2] >= 2 ** 31:
         raise ValueError('%s: dims = %r, expected three counts >= 1 with fewer than 2^31 points' % (entry, dims))
-    o = np.asarray(origin, np.float32).reshape(-1)
-    A = np.eye(3, dtype=np.float64) if axes is None else np.asarray(axes, np.float64).reshape(3, 3)
-    st = np.broadcast_to(np.asarray(step, np.float64).reshape(-1), (3,)) if np.size(step) in (1, 3) else None
-    if o.size != 3 or st is None or not (np.isfinite(o).all() and np.isfinite(A).all() and np.isfinite(st).all()):
-        raise ValueError('%s: origin = %r, step = %r: three finite floats and one or three finite steps' % (entry, origin, step))
-    du, dv, dw = ((A[i] * st[i]).astype(np.float32) for i in range(3))
+    frame = lattice.frame(origin, step=step, axes=axes, entry=entry, scaled=True)
     from . import ops
-    dist, tri = ops.closest_grid(b['ws'], b['T'], dims, o, du, dv, dw, md)
-    return dict(density=dist, tri=tri, valid=None, frame=dict(origin=o, du=du, dv=dv, dw=dw))
+    dist, tri = ops.closest_grid(b['ws'], b['T'], dims, frame['origin'], frame['du'], frame['dv'], frame['dw'], md)
+    return dict(density=dist, tri=tri, valid=None, frame=frame)
 
 
 def mesh_to_mesh(a, b, n, max_dist, thresholds=None):
@@ -123,7 +113,7 @@ def mesh_to_mesh(a, b, n, max_dist, thresholds=None):
     entry = 'closest.mesh_to_mesh'
     import torch
     from . import cast, geometry, ops
-    md = geometry._max_dist(max_dist, entry)
+    md = lattice._max_dist(max_dist, entry)
     if int(n) < 1:
         raise ValueError('%s: n = %r samples' % (entry, n))
     th = geometry._thresholds(tuple(t for t in geometry.DEFAULT_THRESHOLDS if t <= md) if thresholds is None else thresholds, md, entry)

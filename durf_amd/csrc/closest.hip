@@ -6,6 +6,7 @@
 #include <cmath>
 #include "cast_tree.h"
 #include "camera.h"
+#include "lattice.h"
 #include "../../include/durf_closest.h"
 
 static_assert(DURF_CLOSEST_BLOCK == CB && DURF_CLOSEST_STACK == CSTACK, "the walk's workgroup and its one stack entry per level");
@@ -127,15 +128,11 @@ k_closest_points(const CastTree R, int n, const float* __restrict__ points, floa
     closest_query(R, records, nodes, P, max_dist, s_stack + threadIdx.x, s_off, (size_t)i, tri, dist, bary, point);
 }
 
-struct ClosestLattice {
-    int nu, nv, nw, bv, bw;            // bv, bw: bricks along v and w
-    long long bricks;
-    float origin[3], du[3], dv[3], dw[3];
-};
+struct ClosestBricks { int bv, bw; long long bricks; };        // bricks along v and w, and all of them
 
 // a wave per brick of 4 x 4 x 4 lattice points: lane = (di 4 + dj) 4 + dk
 __global__ void __launch_bounds__(CB)
-k_closest_grid(const CastTree R, const ClosestLattice G, float max_dist, const float* __restrict__ records, const float* __restrict__ nodes,
+k_closest_grid(const CastTree R, const LatticeDims D, const LatticeFrame F, const ClosestBricks G, float max_dist, const float* __restrict__ records, const float* __restrict__ nodes,
                float* __restrict__ dist, int32_t* __restrict__ tri) {
     __shared__ int s_stack[CSTACK * CB];
     __shared__ int s_off[CSTACK];
@@ -146,11 +143,10 @@ k_closest_grid(const CastTree R, const ClosestLattice G, float max_dist, const f
     const long long bu = brick / ((long long)G.bv * G.bw);
     const int rest = (int)(brick - bu * ((long long)G.bv * G.bw));
     const int i = (int)bu * DURF_CLOSEST_BRICK + lane / 16, j = (rest / G.bw) * DURF_CLOSEST_BRICK + lane / 4 % 4, k = (rest % G.bw) * DURF_CLOSEST_BRICK + lane % 4;
-    if (i >= G.nu || j >= G.nv || k >= G.nw) return;
+    if (i >= D.nu || j >= D.nv || k >= D.nw) return;
     float P[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) P[c] = ((G.origin[c] + (float)i * G.du[c]) + (float)j * G.dv[c]) + (float)k * G.dw[c];
-    const size_t g = ((size_t)i * G.nv + j) * G.nw + k;
+    lattice_point(F, (float)i, (float)j, (float)k, P);
+    const size_t g = (size_t)lattice_index(D, i, j, k);                      // nu nv nw < 2^31
     closest_query(R, records, nodes, P, max_dist, s_stack + threadIdx.x, s_off, g, tri, dist, nullptr, nullptr);
 }
 
@@ -198,21 +194,19 @@ int durf_closest_grid(void* stream, int nu, int nv, int nw, const float* origin,
         return -1;
     }
     if (!(origin && du && dv && dw)) { durf_set_error("%s: requirement failed: origin, du, dv and dw (host floats)", __func__); return -1; }
-    ClosestLattice G{};
+    const LatticeFrame F = lattice_frame(origin, du, dv, dw);
     bool finite = true;
-    for (int c = 0; c < 3; c++) {
-        G.origin[c] = origin[c], G.du[c] = du[c], G.dv[c] = dv[c], G.dw[c] = dw[c];
-        finite = finite && std::isfinite(origin[c]) && std::isfinite(du[c]) && std::isfinite(dv[c]) && std::isfinite(dw[c]);
-    }
+    for (int c = 0; c < 3; c++) finite = finite && std::isfinite(F.o[c]) && std::isfinite(F.du[c]) && std::isfinite(F.dv[c]) && std::isfinite(F.dw[c]);
     if (!finite) { durf_set_error("%s: requirement failed: origin, du, dv and dw are finite", __func__); return -1; }
     CastTree R;
     CastWs ws;
     if (closest_check(__func__, max_dist, T, workspace, workspace_bytes, &R, &ws) != 0) return -1;
     if (!dist) { durf_set_error("%s: requirement failed: dist for %d x %d x %d points", __func__, nu, nv, nw); return -1; }
-    G.nu = nu, G.nv = nv, G.nw = nw;
+    const LatticeDims D{nu, nv, nw, nu * nv * nw};
+    ClosestBricks G{};
     G.bv = (int)durf_cdiv((size_t)nv, DURF_CLOSEST_BRICK), G.bw = (int)durf_cdiv((size_t)nw, DURF_CLOSEST_BRICK);
     G.bricks = (long long)durf_cdiv((size_t)nu, DURF_CLOSEST_BRICK) * G.bv * G.bw;       // at most 16 nu nv nw / 64 < 2^29
-    hipLaunchKernelGGL(k_closest_grid, dim3(durf_cdiv((size_t)G.bricks, CB / 64)), dim3(CB), 0, (hipStream_t)stream, R, G, max_dist, ws.records,
+    hipLaunchKernelGGL(k_closest_grid, dim3(durf_cdiv((size_t)G.bricks, CB / 64)), dim3(CB), 0, (hipStream_t)stream, R, D, F, G, max_dist, ws.records,
                        ws.nodes, dist, tri);
     DURF_CHECK_LAUNCH("k_closest_grid");
     return 0;

@@ -6,6 +6,7 @@
 // libdurf_hip.so.  Streaming kernels, plain fp32 in the order the header states; no atomics, nothing synchronises or copies to
 // the host.
 #include "workspace.h"
+#include "lattice.h"
 #include "aa2matrix.h"
 #include "enc_lane.h"
 #include "loss_common.h"
@@ -185,23 +186,20 @@ k_field_activate(int n, int K, const int32_t* __restrict__ idx, const int32_t* _
 }
 
 // ---- grids --------------------------------------------------------------------------------------------------------------------
-struct FieldGrid {
-    float o[3], du[3], dv[3], dw[3];
-    int nv, nw;
-};
 
 __global__ void __launch_bounds__(FIELD_THREADS)
-k_field_grid_points(int m, long long first, FieldGrid G, float* __restrict__ pts, float* __restrict__ points_out) {
+k_field_grid_points(int m, int first, const LatticeDims D, const LatticeFrame F, float* __restrict__ pts, float* __restrict__ points_out) {
     const int t = blockIdx.x * FIELD_THREADS + threadIdx.x;
     if (t >= m) return;
-    const long long g = first + t;
-    const long long ij = g / G.nw;
-    const int k = (int)(g - ij * G.nw), i = (int)(ij / G.nv), j = (int)(ij - (long long)i * G.nv);
+    const int g = first + t;                                                 // nu nv nw < 2^31
+    int i, j, k;
+    lattice_ijk(D, g, i, j, k);
+    float P[3];
+    lattice_point(F, (float)i, (float)j, (float)k, P);
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        const float x = ((G.o[c] + (float)i * G.du[c]) + (float)j * G.dv[c]) + (float)k * G.dw[c];
-        pts[(size_t)t * 3 + c] = x;
-        if (points_out) points_out[(size_t)g * 3 + c] = x;
+        pts[(size_t)t * 3 + c] = P[c];
+        if (points_out) points_out[(size_t)g * 3 + c] = P[c];
     }
 }
 
@@ -417,7 +415,7 @@ int durf_field_query(void* stream, const durf_field_args* a, int n, int chunk, v
     int rc = check_field_args(__func__, a, n, chunk, false);
     if (rc != 0) return rc;
     if (n == 0) return 0;
-    DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    if (durf::check_workspace_aligned(__func__, workspace) != 0) return -1;
     const FieldWs w = carve_field(workspace, chunk, a->K);
     rc = durf::check_workspace("durf_field_query", workspace_bytes, w.total, "durf_field_workspace_bytes(%d, %d)", chunk, a->K);
     if (rc != 0) return rc;
@@ -446,21 +444,19 @@ int durf_field_grid(void* stream, const durf_field_args* a, const float* origin_
     if (rc != 0) return rc;
     DURF_REQUIREF(origin_host && du_host && dv_host && dw_host, "origin, du, dv and dw");
     DURF_REQUIREF(has_view || !a->rgb, "rgb needs a view direction (has_view == 0 is a density-only query)");
-    DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    if (durf::check_workspace_aligned(__func__, workspace) != 0) return -1;
     const FieldWs w = carve_field(workspace, chunk, a->K);
     rc = durf::check_workspace("durf_field_grid", workspace_bytes, w.total, "durf_field_workspace_bytes(%d, %d)", chunk, a->K);
     if (rc != 0) return rc;
-    FieldGrid G;
-    for (int c = 0; c < 3; c++) { G.o[c] = origin_host[c]; G.du[c] = du_host[c]; G.dv[c] = dv_host[c]; G.dw[c] = dw_host[c]; }
-    G.nv = nv; G.nw = nw;
+    const LatticeDims D{nu, nv, nw, (int)total};
+    const LatticeFrame G = lattice_frame(origin_host, du_host, dv_host, dw_host);
     // the grid's one view direction as a chunk of view rows: durf_view_enc of `first` copies of it, once
     const int first = (int)(total < chunk ? total : (long long)chunk);
     if (has_view) {
-        FieldGrid V{};
+        LatticeFrame V{};
         V.o[0] = view_x; V.o[1] = view_y; V.o[2] = view_z;       // steps of 0: every "grid point" is the view direction
-        V.nv = 1; V.nw = 1;
         hipLaunchKernelGGL(k_field_grid_points, dim3(durf_cdiv(first, FIELD_THREADS)), dim3(FIELD_THREADS), 0, (hipStream_t)stream, first,
-                           0ll, V, w.view3, (float*)nullptr);
+                           0, D, V, w.view3, (float*)nullptr);
         DURF_CHECK_LAUNCH("k_field_grid_points(view)");
         if ((rc = durf_view_enc(stream, first, w.view3, nullptr, w.view27)) != 0) return rc;
     } else if (hipMemsetAsync(w.view27, 0, (size_t)first * 27 * 4, (hipStream_t)stream) != hipSuccess) {
@@ -469,8 +465,8 @@ int durf_field_grid(void* stream, const durf_field_args* a, const float* origin_
     }
     for (long long i = 0; i < total; i += chunk) {
         const int B = (int)(total - i < chunk ? total - i : (long long)chunk);
-        hipLaunchKernelGGL(k_field_grid_points, dim3(durf_cdiv(B, FIELD_THREADS)), dim3(FIELD_THREADS), 0, (hipStream_t)stream, B, i, G,
-                           w.pts, points_out);
+        hipLaunchKernelGGL(k_field_grid_points, dim3(durf_cdiv(B, FIELD_THREADS)), dim3(FIELD_THREADS), 0, (hipStream_t)stream, B, (int)i, D,
+                           G, w.pts, points_out);
         DURF_CHECK_LAUNCH("k_field_grid_points");
         rc = field_chunk(stream, a, w, B, w.pts, w.view27, a->density + i, a->rgb ? a->rgb + i * 3 : nullptr,
                          a->raw ? a->raw + i * 4 : nullptr, a->owner ? a->owner + i : nullptr, a->valid ? a->valid + i : nullptr);

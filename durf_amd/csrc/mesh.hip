@@ -5,6 +5,7 @@
 // adjacent lanes along k, plain fp32 in the order the header states; no atomics, nothing synchronises or copies to the host.
 #include "workspace.h"
 #include "scan.h"
+#include "lattice.h"
 #include "../../include/durf_mesh.h"
 
 #define MESH_B DURF_MESH_BLOCK
@@ -107,28 +108,19 @@ static_assert(MESH_TABLES.ntri[0] == 0 && MESH_TABLES.ntri[15] == 0 && MESH_TABL
 static_assert(MESH_TABLES.corner[3][1] == 2 && MESH_TABLES.corner[3][2] == 3, "permutation (1,2,0): +j, then +k");
 __constant__ MeshTables c_mesh = MESH_TABLES;
 
-// ---- the lattice ----------------------------------------------------------------------------------------------------------------
-struct MeshDims {
-    int nu, nv, nw, n;
-};
-
-__device__ __forceinline__ bool mesh_usable(const float* __restrict__ density, const uint8_t* __restrict__ valid, int g, float* d) {
-    const float x = density[g];
-    *d = x;
-    return (valid == nullptr || valid[g] != 0) && x == x;
-}
-
+// ---- the lattice (lattice.h) ----------------------------------------------------------------------------------------------------
 // the eight corners of the cell at (i, j, k): bit c of *exist (the corner is inside the lattice), *usable, *in
-__device__ __forceinline__ void mesh_corners(const MeshDims D, const float* __restrict__ density, const uint8_t* __restrict__ valid,
+__device__ __forceinline__ void mesh_corners(const LatticeDims D, const float* __restrict__ density, const uint8_t* __restrict__ valid,
                                              float iso, int g, int i, int j, int k, unsigned* exist, unsigned* usable, unsigned* in) {
     unsigned X = 0, U = 0, N = 0;
 #pragma unroll
     for (int c = 0; c < 8; c++) {
-        const int di = c >> 2, dj = c >> 1 & 1, dk = c & 1;
+        int di, dj, dk;
+        lattice_corner(c, di, dj, dk);
         if (i + di < D.nu && j + dj < D.nv && k + dk < D.nw) {
             X |= 1u << c;
             float d;
-            if (mesh_usable(density, valid, g + (di * D.nv + dj) * D.nw + dk, &d)) {
+            if (lattice_usable(density, valid, g + lattice_index(D, di, dj, dk), &d)) {
                 U |= 1u << c;
                 if (d >= iso) N |= 1u << c;
             }
@@ -140,14 +132,15 @@ __device__ __forceinline__ void mesh_corners(const MeshDims D, const float* __re
 // pass 1: per lattice point the seven activity bits and the counts of its vertices (into voff) and of its cell's triangles
 // (into toff); per workgroup the two sums
 __global__ void __launch_bounds__(MESH_B)
-k_mesh_classify(const MeshDims D, const float* __restrict__ density, const uint8_t* __restrict__ valid, float iso,
+k_mesh_classify(const LatticeDims D, const float* __restrict__ density, const uint8_t* __restrict__ valid, float iso,
                 int32_t* __restrict__ voff, int32_t* __restrict__ toff, uint8_t* __restrict__ mask, int32_t* __restrict__ sums_v,
                 int32_t* __restrict__ sums_t) {
     __shared__ int s_v[MESH_WAVES], s_t[MESH_WAVES];
     const int t = threadIdx.x, g = blockIdx.x * MESH_B + t;
     int cv = 0, ct = 0;
     if (g < D.n) {
-        const int k = g % D.nw, r = g / D.nw, j = r % D.nv, i = r / D.nv;
+        int i, j, k;
+        lattice_ijk(D, g, i, j, k);
         unsigned X, U, N;
         mesh_corners(D, density, valid, iso, g, i, j, k, &X, &U, &N);
         unsigned m = 0;
@@ -195,31 +188,30 @@ k_mesh_offsets(int n, int32_t* __restrict__ voff, int32_t* __restrict__ toff, co
 }
 
 // ---- emit -------------------------------------------------------------------------------------------------------------------
-struct MeshFrame {
-    float o[3], du[3], dv[3], dw[3], A[9];
-};
+struct MeshNormals { float A[9]; };    // the inverse transpose of [du dv dw]
 
 // the index-space gradient at lattice point (i, j, k), index g, whose density d0 is usable
-__device__ __forceinline__ void mesh_gradient(const MeshDims D, const float* __restrict__ density, const uint8_t* __restrict__ valid,
+__device__ __forceinline__ void mesh_gradient(const LatticeDims D, const float* __restrict__ density, const uint8_t* __restrict__ valid,
                                               int g, int i, int j, int k, float d0, float* gr) {
     const int at[3] = {i, j, k}, dim[3] = {D.nu, D.nv, D.nw}, stride[3] = {D.nv * D.nw, D.nw, 1};
 #pragma unroll
     for (int x = 0; x < 3; x++) {
         float dp = 0.0f, dm = 0.0f;
-        const bool up = at[x] + 1 < dim[x] && mesh_usable(density, valid, g + stride[x], &dp);
-        const bool um = at[x] > 0 && mesh_usable(density, valid, g - stride[x], &dm);
+        const bool up = at[x] + 1 < dim[x] && lattice_usable(density, valid, g + stride[x], &dp);
+        const bool um = at[x] > 0 && lattice_usable(density, valid, g - stride[x], &dm);
         gr[x] = up && um ? 0.5f * (dp - dm) : up ? dp - d0 : um ? d0 - dm : 0.0f;
     }
 }
 
 __global__ void __launch_bounds__(MESH_B)
-k_mesh_emit(const MeshDims D, const float* __restrict__ density, const uint8_t* __restrict__ valid, float iso, const MeshFrame F,
-            int flip, const int32_t* __restrict__ voff, const int32_t* __restrict__ toff, const uint8_t* __restrict__ mask,
+k_mesh_emit(const LatticeDims D, const float* __restrict__ density, const uint8_t* __restrict__ valid, float iso, const LatticeFrame F,
+            const MeshNormals M, int flip, const int32_t* __restrict__ voff, const int32_t* __restrict__ toff, const uint8_t* __restrict__ mask,
             int max_vertices, int max_triangles, float* __restrict__ vertices, float* __restrict__ normals,
             int32_t* __restrict__ vertex_edge, float* __restrict__ vertex_t, int32_t* __restrict__ triangles) {
     const int g = blockIdx.x * MESH_B + threadIdx.x;
     if (g >= D.n) return;
-    const int k = g % D.nw, r = g / D.nw, j = r % D.nv, i = r / D.nv;
+    int i, j, k;
+    lattice_ijk(D, g, i, j, k);
     // the vertices on this point's active edges
     const unsigned m = mask[g];
     if (m) {
@@ -231,17 +223,16 @@ k_mesh_emit(const MeshDims D, const float* __restrict__ density, const uint8_t* 
             if (!(m >> e & 1u)) continue;
             const int v = id++;
             if ((unsigned)v >= (unsigned)max_vertices) continue;
-            const int di = (e + 1) >> 2, dj = (e + 1) >> 1 & 1, dk = (e + 1) & 1;
+            int di, dj, dk;
+            lattice_edge(e, di, dj, dk);
             // an active edge exists: its far end is inside the lattice (bounds: mask comes from k_mesh_classify's own test,
             // and a stale workspace is caught here)
             if (i + di >= D.nu || j + dj >= D.nv || k + dk >= D.nw) continue;
-            const int gb = g + (di * D.nv + dj) * D.nw + dk;
+            const int gb = g + lattice_index(D, di, dj, dk);
             const float db = density[gb];
             float t = (iso - da) / (db - da);
             t = fminf(fmaxf(t, 0.0f), 1.0f);
-            const float q0 = (float)i + t * (float)di, q1 = (float)j + t * (float)dj, q2 = (float)k + t * (float)dk;
-#pragma unroll
-            for (int c = 0; c < 3; c++) vertices[(size_t)v * 3 + c] = ((F.o[c] + q0 * F.du[c]) + q1 * F.dv[c]) + q2 * F.dw[c];
+            lattice_point(F, (float)i + t * (float)di, (float)j + t * (float)dj, (float)k + t * (float)dk, vertices + (size_t)v * 3);
             if (vertex_edge) { vertex_edge[(size_t)v * 2] = g; vertex_edge[(size_t)v * 2 + 1] = e; }
             if (vertex_t) vertex_t[v] = t;
             if (normals) {
@@ -250,7 +241,7 @@ k_mesh_emit(const MeshDims D, const float* __restrict__ density, const uint8_t* 
 #pragma unroll
                 for (int x = 0; x < 3; x++) gr[x] = gra[x] + t * (grb[x] - gra[x]);
 #pragma unroll
-                for (int c = 0; c < 3; c++) mm[c] = (F.A[c * 3] * gr[0] + F.A[c * 3 + 1] * gr[1]) + F.A[c * 3 + 2] * gr[2];
+                for (int c = 0; c < 3; c++) mm[c] = (M.A[c * 3] * gr[0] + M.A[c * 3 + 1] * gr[1]) + M.A[c * 3 + 2] * gr[2];
                 const float len = sqrtf((mm[0] * mm[0] + mm[1] * mm[1]) + mm[2] * mm[2]);
                 float nn[3];
                 bool fine = true;
@@ -283,7 +274,7 @@ k_mesh_emit(const MeshDims D, const float* __restrict__ density, const uint8_t* 
             for (int v = 0; v < 3; v++) {
                 const int E = c_mesh.tri[q][cs][3 * r2 + v];
                 const int c = c_mesh.eown[q][E], e = c_mesh.eedge[q][E];
-                const int gg = g + ((c >> 2) * D.nv + (c >> 1 & 1)) * D.nw + (c & 1);          // a corner of an existing cell
+                const int gg = g + lattice_corner_offset(D, c);                                // a corner of an existing cell
                 ids[v] = voff[gg] + __popc(mask[gg] & ((1u << e) - 1u));
             }
             int32_t* row = triangles + (size_t)at * 3;
@@ -296,7 +287,7 @@ k_mesh_emit(const MeshDims D, const float* __restrict__ density, const uint8_t* 
 
 // ---- lattice attributes at the vertices --------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(MESH_B)
-k_mesh_gather(const MeshDims D, const int32_t* __restrict__ counts, int max_vertices, const int32_t* __restrict__ vertex_edge,
+k_mesh_gather(const LatticeDims D, const int32_t* __restrict__ counts, int max_vertices, const int32_t* __restrict__ vertex_edge,
               const float* __restrict__ vertex_t, int C, const float* __restrict__ attr_f, float* __restrict__ out_f,
               const int32_t* __restrict__ attr_i, const float* __restrict__ density, const uint8_t* __restrict__ valid, float iso,
               int32_t* __restrict__ out_i) {
@@ -304,10 +295,11 @@ k_mesh_gather(const MeshDims D, const int32_t* __restrict__ counts, int max_vert
     if (v >= max_vertices || v >= counts[0]) return;
     const int g = vertex_edge[(size_t)v * 2], e = vertex_edge[(size_t)v * 2 + 1];
     if (g < 0 || g >= D.n || e < 0 || e > 6) return;
-    const int k = g % D.nw, r = g / D.nw, j = r % D.nv, i = r / D.nv;
-    const int di = (e + 1) >> 2, dj = (e + 1) >> 1 & 1, dk = (e + 1) & 1;
+    int i, j, k, di, dj, dk;
+    lattice_ijk(D, g, i, j, k);
+    lattice_edge(e, di, dj, dk);
     if (i + di >= D.nu || j + dj >= D.nv || k + dk >= D.nw) return;
-    const int gb = g + (di * D.nv + dj) * D.nw + dk;
+    const int gb = g + lattice_index(D, di, dj, dk);
     if (attr_f) {
         const float t = vertex_t[v];
         for (int c = 0; c < C; c++) {
@@ -317,7 +309,7 @@ k_mesh_gather(const MeshDims D, const int32_t* __restrict__ counts, int max_vert
     }
     if (attr_i) {
         float da;
-        const bool a_in = mesh_usable(density, valid, g, &da) && da >= iso;
+        const bool a_in = lattice_usable(density, valid, g, &da) && da >= iso;
         out_i[v] = attr_i[a_in ? g : gb];
     }
 }
@@ -346,39 +338,26 @@ MeshWs carve_mesh(void* base, int n) {
     return w;
 }
 
-// -> n, or -1 with the refusal set
-int check_mesh_shape(const char* who, int nu, int nv, int nw) {
-    if (!(nu >= 2 && nv >= 2 && nw >= 2)) {
-        durf_set_error("%s: requirement failed: nu, nv, nw >= 2, nu = %d, nv = %d, nw = %d", who, nu, nv, nw);
-        return -1;
-    }
-    if (!((double)nu * nv * nw < (double)DURF_MESH_MAX_POINTS)) {
-        durf_set_error("%s: requirement failed: nu nv nw < 2^27 lattice points, %d x %d x %d", who, nu, nv, nw);
-        return -1;
-    }
-    return nu * nv * nw;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t durf_mesh_workspace_bytes(int nu, int nv, int nw) {
-    if (!(nu >= 2 && nv >= 2 && nw >= 2) || !((double)nu * nv * nw < (double)DURF_MESH_MAX_POINTS)) return 0;
+    if (!lattice_shape_ok(nu, nv, nw, DURF_MESH_MAX_POINTS)) return 0;
     return carve_mesh(nullptr, nu * nv * nw).total;
 }
 
 int durf_mesh_count(void* stream, int nu, int nv, int nw, const float* density, const uint8_t* valid, float iso, void* workspace,
                     size_t workspace_bytes, int32_t* counts) {
-    const int n = check_mesh_shape(__func__, nu, nv, nw);
+    const int n = check_lattice_shape(__func__, nu, nv, nw, DURF_MESH_MAX_POINTS);
     if (n < 0) return -1;
     DURF_REQUIREF(iso == iso, "iso is a number, iso = %g", (double)iso);
     DURF_REQUIREF(density && counts, "density and counts");
-    DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    if (durf::check_workspace_aligned(__func__, workspace) != 0) return -1;
     const MeshWs w = carve_mesh(workspace, n);
     int rc = durf::check_workspace(__func__, workspace_bytes, w.total, "durf_mesh_workspace_bytes(%d, %d, %d)", nu, nv, nw);
     if (rc != 0) return rc;
-    const MeshDims D{nu, nv, nw, n};
+    const LatticeDims D{nu, nv, nw, n};
     hipLaunchKernelGGL(k_mesh_classify, dim3(w.nb), dim3(MESH_B), 0, (hipStream_t)stream, D, density, valid, iso, w.voff, w.toff, w.mask,
                        w.sums_v, w.sums_t);
     DURF_CHECK_LAUNCH("k_mesh_classify");
@@ -393,7 +372,7 @@ int durf_mesh_emit(void* stream, int nu, int nv, int nw, const float* density, c
                    const float* du_host, const float* dv_host, const float* dw_host, const float* normal_xform_host, int flip,
                    const void* workspace, size_t workspace_bytes, int max_vertices, int max_triangles, float* vertices, float* normals,
                    int32_t* vertex_edge, float* vertex_t, int32_t* triangles) {
-    const int n = check_mesh_shape(__func__, nu, nv, nw);
+    const int n = check_lattice_shape(__func__, nu, nv, nw, DURF_MESH_MAX_POINTS);
     if (n < 0) return -1;
     DURF_REQUIREF(iso == iso, "iso is a number, iso = %g", (double)iso);
     DURF_REQUIREF(density != nullptr, "density");
@@ -403,17 +382,17 @@ int durf_mesh_emit(void* stream, int nu, int nv, int nw, const float* density, c
                  max_triangles);
     DURF_REQUIREF(vertices || max_vertices == 0, "vertices for max_vertices = %d", max_vertices);
     DURF_REQUIREF(triangles || max_triangles == 0, "triangles for max_triangles = %d", max_triangles);
-    DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    if (durf::check_workspace_aligned(__func__, workspace) != 0) return -1;
     const MeshWs w = carve_mesh(const_cast<void*>(workspace), n);
     int rc = durf::check_workspace(__func__, workspace_bytes, w.total, "durf_mesh_workspace_bytes(%d, %d, %d)", nu, nv, nw);
     if (rc != 0) return rc;
     if (max_vertices == 0 && max_triangles == 0) return 0;
-    MeshFrame F{};
-    for (int c = 0; c < 3; c++) { F.o[c] = origin_host[c]; F.du[c] = du_host[c]; F.dv[c] = dv_host[c]; F.dw[c] = dw_host[c]; }
+    const LatticeFrame F = lattice_frame(origin_host, du_host, dv_host, dw_host);
+    MeshNormals M{};
     if (normals)
-        for (int c = 0; c < 9; c++) F.A[c] = normal_xform_host[c];
-    const MeshDims D{nu, nv, nw, n};
-    hipLaunchKernelGGL(k_mesh_emit, dim3(w.nb), dim3(MESH_B), 0, (hipStream_t)stream, D, density, valid, iso, F, flip != 0 ? 1 : 0, w.voff,
+        for (int c = 0; c < 9; c++) M.A[c] = normal_xform_host[c];
+    const LatticeDims D{nu, nv, nw, n};
+    hipLaunchKernelGGL(k_mesh_emit, dim3(w.nb), dim3(MESH_B), 0, (hipStream_t)stream, D, density, valid, iso, F, M, flip != 0 ? 1 : 0, w.voff,
                        w.toff, w.mask, max_vertices, max_triangles, max_vertices ? vertices : nullptr, max_vertices ? normals : nullptr,
                        max_vertices ? vertex_edge : nullptr, max_vertices ? vertex_t : nullptr, triangles);
     DURF_CHECK_LAUNCH("k_mesh_emit");
@@ -423,7 +402,7 @@ int durf_mesh_emit(void* stream, int nu, int nv, int nw, const float* density, c
 int durf_mesh_gather(void* stream, int nu, int nv, int nw, const int32_t* counts, int max_vertices, const int32_t* vertex_edge,
                      const float* vertex_t, int C, const float* attr_f, float* out_f, const int32_t* attr_i, const float* density,
                      const uint8_t* valid, float iso, int32_t* out_i) {
-    const int n = check_mesh_shape(__func__, nu, nv, nw);
+    const int n = check_lattice_shape(__func__, nu, nv, nw, DURF_MESH_MAX_POINTS);
     if (n < 0) return -1;
     DURF_REQUIREF(max_vertices >= 0, "max_vertices >= 0, max_vertices = %d", max_vertices);
     DURF_REQUIREF(counts && vertex_edge && vertex_t, "counts, vertex_edge and vertex_t");
@@ -432,7 +411,7 @@ int durf_mesh_gather(void* stream, int nu, int nv, int nw, const int32_t* counts
     DURF_REQUIREF(!attr_i || (out_i && density), "attr_i needs out_i and density");
     DURF_REQUIREF(!attr_i || iso == iso, "iso is a number, iso = %g", (double)iso);
     if (max_vertices == 0) return 0;
-    const MeshDims D{nu, nv, nw, n};
+    const LatticeDims D{nu, nv, nw, n};
     hipLaunchKernelGGL(k_mesh_gather, dim3(durf_cdiv((size_t)max_vertices, MESH_B)), dim3(MESH_B), 0, (hipStream_t)stream, D, counts,
                        max_vertices, vertex_edge, vertex_t, C, attr_f, out_f, attr_i, density, valid, iso, out_i);
     DURF_CHECK_LAUNCH("k_mesh_gather");

@@ -6,6 +6,7 @@
 #include <climits>
 #include "workspace.h"
 #include "scan.h"
+#include "lattice.h"
 #include "../../include/durf_mesh.h"
 #include "../../include/durf_parts.h"
 
@@ -17,14 +18,11 @@
 #define TPOINTS DURF_PARTS_TILE_POINTS
 static_assert(TPOINTS == 256 && TPOINTS % DURF_WAVE == 0 && DURF_WAVE % TK == 0, "one workgroup of whole waves, lanes along k");
 
-struct PartsDims {
-    int nu, nv, nw, n;
-    int tu, tv, tw;                    // tiles along each axis
-};
+struct PartsTiles { int tu, tv, tw; };  // tiles along each axis
 
 __device__ __forceinline__ bool parts_in(const float* __restrict__ density, const uint8_t* __restrict__ valid, float iso, int g) {
-    const float x = density[g];
-    return (valid == nullptr || valid[g] != 0) && x == x && x >= iso;
+    float d;
+    return lattice_usable(density, valid, g, &d) && d >= iso;
 }
 
 // L is read while other workgroups change it: a relaxed load at agent scope (served past this unit's L1)
@@ -34,16 +32,18 @@ __device__ __forceinline__ int parts_load(const int32_t* p) {
 
 // ---- (a) the tile pass -----------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(TPOINTS)
-k_parts_tile(const PartsDims D, const float* __restrict__ density, const uint8_t* __restrict__ valid, float iso,
+k_parts_tile(const LatticeDims D, const PartsTiles B, const float* __restrict__ density, const uint8_t* __restrict__ valid, float iso,
              int32_t* __restrict__ L) {
     __shared__ int s_lab[TPOINTS];
+    const LatticeDims T{TI, TJ, TK, TPOINTS};                                 // the tile is a lattice of its own, in LDS
     const int l = threadIdx.x;
-    const int lk = l % TK, lj = l / TK % TJ, li = l / (TK * TJ);
+    int li, lj, lk;
+    lattice_ijk(T, l, li, lj, lk);
     const int b = blockIdx.x;
-    const int bk = b % D.tw, bj = b / D.tw % D.tv, bi = b / (D.tw * D.tv);
+    const int bk = b % B.tw, bj = b / B.tw % B.tv, bi = b / (B.tw * B.tv);
     const int i = bi * TI + li, j = bj * TJ + lj, k = bk * TK + lk;
     const bool inside = i < D.nu && j < D.nv && k < D.nw;
-    const int g = inside ? (i * D.nv + j) * D.nw + k : 0;
+    const int g = inside ? lattice_index(D, i, j, k) : 0;
     const bool in = inside && parts_in(density, valid, iso, g);
     int mine = in ? l : -1;
     s_lab[l] = mine;
@@ -53,8 +53,9 @@ k_parts_tile(const PartsDims D, const float* __restrict__ density, const uint8_t
     if (in) {
 #pragma unroll
         for (int e = 0; e < 7; e++) {
-            const int di = (e + 1) >> 2, dj = (e + 1) >> 1 & 1, dk = (e + 1) & 1;
-            const int o = (di * TJ + dj) * TK + dk;
+            int di, dj, dk;
+            lattice_edge(e, di, dj, dk);
+            const int o = lattice_edge_offset(T, e);
             if (li + di < TI && lj + dj < TJ && lk + dk < TK && s_lab[l + o] >= 0) adj |= 1u << e;
             if (li - di >= 0 && lj - dj >= 0 && lk - dk >= 0 && s_lab[l - o] >= 0) adj |= 1u << (7 + e);
         }
@@ -65,7 +66,7 @@ k_parts_tile(const PartsDims D, const float* __restrict__ density, const uint8_t
         if (adj) {
 #pragma unroll
             for (int e = 0; e < 7; e++) {
-                const int o = (((e + 1) >> 2) * TJ + ((e + 1) >> 1 & 1)) * TK + ((e + 1) & 1);
+                const int o = lattice_edge_offset(T, e);
                 if (adj >> e & 1u) m = min(m, s_lab[l + o]);
                 if (adj >> (7 + e) & 1u) m = min(m, s_lab[l - o]);
             }
@@ -82,8 +83,9 @@ k_parts_tile(const PartsDims D, const float* __restrict__ density, const uint8_t
     if (inside) {
         int out = -1;
         if (in) {
-            const int rk = mine % TK, rj = mine / TK % TJ, ri = mine / (TK * TJ);
-            out = ((bi * TI + ri) * D.nv + (bj * TJ + rj)) * D.nw + (bk * TK + rk);
+            int ri, rj, rk;
+            lattice_ijk(T, mine, ri, rj, rk);
+            out = lattice_index(D, bi * TI + ri, bj * TJ + rj, bk * TK + rk);
         }
         L[g] = out;
     }
@@ -110,20 +112,22 @@ __device__ __forceinline__ void parts_unite(int32_t* L, int a, int b) {
 }
 
 __global__ void __launch_bounds__(PARTS_B)
-k_parts_border(const PartsDims D, int32_t* L) {
+k_parts_border(const LatticeDims D, int32_t* L) {
     const int g = blockIdx.x * PARTS_B + threadIdx.x;
     if (g >= D.n) return;
-    const int k = g % D.nw, r = g / D.nw, j = r % D.nv, i = r / D.nv;
+    int i, j, k;
+    lattice_ijk(D, g, i, j, k);
     const bool ei = i % TI == TI - 1 && i + 1 < D.nu, ej = j % TJ == TJ - 1 && j + 1 < D.nv, ek = k % TK == TK - 1 && k + 1 < D.nw;
     if (!(ei || ej || ek)) return;                                            // every owned edge stays inside the tile
     if (parts_load(L + g) < 0) return;                                        // not IN (-1 is never changed)
     int a = -1;
 #pragma unroll
     for (int e = 0; e < 7; e++) {
-        const int di = (e + 1) >> 2, dj = (e + 1) >> 1 & 1, dk = (e + 1) & 1;
+        int di, dj, dk;
+        lattice_edge(e, di, dj, dk);
         if (!((di && ei) || (dj && ej) || (dk && ek))) continue;              // stays inside the tile (or leaves the lattice)
         if (i + di >= D.nu || j + dj >= D.nv || k + dk >= D.nw) continue;
-        const int q = g + (di * D.nv + dj) * D.nw + dk;
+        const int q = g + lattice_index(D, di, dj, dk);
         if (parts_load(L + q) < 0) continue;
         if (a < 0) a = parts_find(L, g);
         parts_unite(L, a, parts_find(L, q));
@@ -215,7 +219,7 @@ __device__ __forceinline__ void parts_stats_add(int32_t* size, int32_t* bbox, in
 // at the end the table's entries are added to global memory.  So one component of millions of points sends a few thousand
 // atomics to its seven addresses, not millions.
 __global__ void __launch_bounds__(PARTS_B)
-k_parts_stats(const PartsDims D, const int32_t* __restrict__ comp, int max_components, int32_t* size, int32_t* bbox) {
+k_parts_stats(const LatticeDims D, const int32_t* __restrict__ comp, int max_components, int32_t* size, int32_t* bbox) {
     __shared__ int s_key[STATS_SLOTS], s_cnt[STATS_SLOTS], s_lo[STATS_SLOTS][3], s_hi[STATS_SLOTS][3];
     const int lane = threadIdx.x & (DURF_WAVE - 1);
     if (threadIdx.x < STATS_SLOTS) {
@@ -230,10 +234,7 @@ k_parts_stats(const PartsDims D, const int32_t* __restrict__ comp, int max_compo
         int c = -1, i = 0, j = 0, k = 0;
         if (g < D.n) {
             c = comp[g];
-            k = g % D.nw;
-            const int r = g / D.nw;
-            j = r % D.nv;
-            i = r / D.nv;
+            lattice_ijk(D, g, i, j, k);
         }
         bool todo = c >= 0 && c < max_components;
         for (int turn = 0; turn < DURF_WAVE; turn++) {
@@ -358,45 +359,29 @@ PartsWs carve_parts(void* base, int n) {
     return w;
 }
 
-// -> n, or -1 with the refusal set
-int check_parts_shape(const char* who, int nu, int nv, int nw) {
-    if (!(nu >= 2 && nv >= 2 && nw >= 2)) {
-        durf_set_error("%s: requirement failed: nu, nv, nw >= 2, nu = %d, nv = %d, nw = %d", who, nu, nv, nw);
-        return -1;
-    }
-    if (!((double)nu * nv * nw < (double)DURF_MESH_MAX_POINTS)) {
-        durf_set_error("%s: requirement failed: nu nv nw < 2^27 lattice points, %d x %d x %d", who, nu, nv, nw);
-        return -1;
-    }
-    return nu * nv * nw;
-}
-
-PartsDims parts_dims(int nu, int nv, int nw, int n) {
-    return PartsDims{nu, nv, nw, n, (int)durf_cdiv(nu, TI), (int)durf_cdiv(nv, TJ), (int)durf_cdiv(nw, TK)};
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t durf_parts_workspace_bytes(int nu, int nv, int nw) {
-    if (!(nu >= 2 && nv >= 2 && nw >= 2) || !((double)nu * nv * nw < (double)DURF_MESH_MAX_POINTS)) return 0;
+    if (!lattice_shape_ok(nu, nv, nw, DURF_MESH_MAX_POINTS)) return 0;
     return carve_parts(nullptr, nu * nv * nw).total;
 }
 
 int durf_parts_label(void* stream, int nu, int nv, int nw, const float* density, const uint8_t* valid, float iso, void* workspace,
                      size_t workspace_bytes, int32_t* labels) {
-    const int n = check_parts_shape(__func__, nu, nv, nw);
+    const int n = check_lattice_shape(__func__, nu, nv, nw, DURF_MESH_MAX_POINTS);
     if (n < 0) return -1;
     DURF_REQUIREF(iso == iso, "iso is a number, iso = %g", (double)iso);
     DURF_REQUIREF(density && labels, "density and labels");
-    DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    if (durf::check_workspace_aligned(__func__, workspace) != 0) return -1;
     const PartsWs w = carve_parts(workspace, n);
     int rc = durf::check_workspace(__func__, workspace_bytes, w.total, "durf_parts_workspace_bytes(%d, %d, %d)", nu, nv, nw);
     if (rc != 0) return rc;
-    const PartsDims D = parts_dims(nu, nv, nw, n);
+    const LatticeDims D{nu, nv, nw, n};
+    const PartsTiles B{(int)durf_cdiv(nu, TI), (int)durf_cdiv(nv, TJ), (int)durf_cdiv(nw, TK)};
     const hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_parts_tile, dim3((unsigned)D.tu * D.tv * D.tw), dim3(TPOINTS), 0, s, D, density, valid, iso, w.link);
+    hipLaunchKernelGGL(k_parts_tile, dim3((unsigned)B.tu * B.tv * B.tw), dim3(TPOINTS), 0, s, D, B, density, valid, iso, w.link);
     DURF_CHECK_LAUNCH("k_parts_tile");
     hipLaunchKernelGGL(k_parts_border, dim3(w.nb), dim3(PARTS_B), 0, s, D, w.link);
     DURF_CHECK_LAUNCH("k_parts_border");
@@ -409,7 +394,7 @@ int durf_parts_number(void* stream, int n, const int32_t* labels, void* workspac
                       int32_t* count) {
     DURF_REQUIREF(n >= 1 && n < DURF_MESH_MAX_POINTS, "1 <= n < 2^27, n = %d", n);
     DURF_REQUIREF(labels && comp && count, "labels, comp and count");
-    DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    if (durf::check_workspace_aligned(__func__, workspace) != 0) return -1;
     const PartsWs w = carve_parts(workspace, n);
     int rc = durf::check_workspace(__func__, workspace_bytes, w.total, "the workspace of n = %d points", n);
     if (rc != 0) return rc;
@@ -426,13 +411,13 @@ int durf_parts_number(void* stream, int n, const int32_t* labels, void* workspac
 }
 
 int durf_parts_stats(void* stream, int nu, int nv, int nw, const int32_t* comp, int max_components, int32_t* size, int32_t* bbox) {
-    const int n = check_parts_shape(__func__, nu, nv, nw);
+    const int n = check_lattice_shape(__func__, nu, nv, nw, DURF_MESH_MAX_POINTS);
     if (n < 0) return -1;
     DURF_REQUIREF(max_components >= 0, "max_components >= 0, max_components = %d", max_components);
     DURF_REQUIREF(comp != nullptr, "comp");
     DURF_REQUIREF((size && bbox) || max_components == 0, "size and bbox for max_components = %d", max_components);
     if (max_components == 0) return 0;
-    const PartsDims D = parts_dims(nu, nv, nw, n);
+    const LatticeDims D{nu, nv, nw, n};
     const hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_parts_stats_init, dim3(durf_cdiv((size_t)max_components, PARTS_B)), dim3(PARTS_B), 0, s, max_components, size, bbox);
     DURF_CHECK_LAUNCH("k_parts_stats_init");
@@ -452,7 +437,7 @@ int durf_parts_select_mesh(void* stream, const int32_t* counts, int max_vertices
                  max_vertices);
     DURF_REQUIREF((triangles && triangles_out) || max_triangles == 0, "triangles and triangles_out for max_triangles = %d", max_triangles);
     DURF_REQUIREF(keep || n_components == 0, "keep for n_components = %d", n_components);
-    DURF_REQUIREF(workspace != nullptr && ((size_t)workspace & 255) == 0, "workspace aligned to 256 bytes");
+    if (durf::check_workspace_aligned(__func__, workspace) != 0) return -1;
     const int nm = (int)durf_cdiv((size_t)(max_vertices > max_triangles ? max_vertices : max_triangles), PARTS_B);
     const size_t need = ((size_t)2 * (nm + 1) * 4 + 255) & ~(size_t)255;
     int rc = durf::check_workspace(__func__, workspace_bytes, need, "the block sums of %d vertices and %d triangles", max_vertices,

@@ -6,17 +6,13 @@
 #include <cmath>
 #include "durf_common.h"
 #include "camera.h"
+#include "lattice.h"
 #include "../../include/durf_mesh.h"
 #include "../../include/durf_tsdf.h"
 
 #define TB DURF_TSDF_BLOCK
 static_assert(TB == 256, "one voxel per thread, 256 per workgroup");
 static_assert(DURF_TSDF_MAX_POINTS == DURF_MESH_MAX_POINTS, "the lattice goes on to durf_mesh_count");
-
-struct TsdfLattice {
-    int nu, nv, nw, n;
-    float origin[3], du[3], dv[3], dw[3];
-};
 
 struct TsdfFrames {
     int F, h, w;
@@ -37,13 +33,13 @@ struct TsdfFrames {
 // finite-and-not-NaN test: it guards depth, weights and lattice coordinates here as well as camera space.  The per-lane state is D, W, the
 // four colour floats and the voxel's position.
 __global__ void __launch_bounds__(TB)
-k_tsdf_integrate(const TsdfLattice L, const TsdfFrames A, float* __restrict__ tsdf, float* __restrict__ weight, float* __restrict__ colour) {
+k_tsdf_integrate(const LatticeDims L, const LatticeFrame G, const TsdfFrames A, float* __restrict__ tsdf, float* __restrict__ weight, float* __restrict__ colour) {
     const int g = blockIdx.x * TB + threadIdx.x;                             // n < 2^27
     if (g >= L.n) return;
-    const int k = g % L.nw, ij = g / L.nw, j = ij % L.nv, i = ij / L.nv;
+    int i, j, k;
+    lattice_ijk(L, g, i, j, k);
     float P[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) P[c] = ((L.origin[c] + (float)i * L.du[c]) + (float)j * L.dv[c]) + (float)k * L.dw[c];
+    lattice_point(G, (float)i, (float)j, (float)k, P);
     float D = tsdf[g], W = weight[g];
     const bool keep_colour = colour != nullptr && A.rgb != nullptr;
     float C0 = 0.0f, C1 = 0.0f, C2 = 0.0f, Wc = 0.0f;
@@ -203,19 +199,6 @@ k_tsdf_sample(int nu, int nv, int nw, const TsdfInverse Q, const float* __restri
 
 namespace {
 
-// -> n, or -1 with the refusal set (durf_mesh.h's lattice)
-int check_tsdf_shape(const char* who, int nu, int nv, int nw) {
-    if (!(nu >= 2 && nv >= 2 && nw >= 2)) {
-        durf_set_error("%s: requirement failed: nu, nv, nw >= 2, nu = %d, nv = %d, nw = %d", who, nu, nv, nw);
-        return -1;
-    }
-    if (!((double)nu * nv * nw < (double)DURF_TSDF_MAX_POINTS)) {
-        durf_set_error("%s: requirement failed: nu nv nw < 2^27 lattice points, %d x %d x %d", who, nu, nv, nw);
-        return -1;
-    }
-    return nu * nv * nw;
-}
-
 // colour is read and written as float4 rows: the header asks for 16-byte alignment
 bool tsdf_aligned16(const void* p) { return ((size_t)p & 15) == 0; }
 
@@ -227,7 +210,7 @@ int durf_tsdf_integrate(void* stream, int nu, int nv, int nw, const float* origi
                         const float* dw_host, int F, int h, int w, const float* cams_dev, const float* depth, const float* acc,
                         float min_acc, const float* rgb, const int32_t* label, int select, int other_mode, const float* xform,
                         const float* frame_weight, float trunc, float max_weight, float znear, float* tsdf, float* weight, float* colour) {
-    const int n = check_tsdf_shape(__func__, nu, nv, nw);
+    const int n = check_lattice_shape(__func__, nu, nv, nw, DURF_TSDF_MAX_POINTS);
     if (n < 0) return -1;
     DURF_REQUIREF(F >= 0, "F >= 0, F = %d", F);
     DURF_REQUIREF(h >= 1 && w >= 1 && h <= DURF_TSDF_MAX_SIZE && w <= DURF_TSDF_MAX_SIZE, "1 <= h, w <= %d, h = %d, w = %d",
@@ -249,22 +232,21 @@ int durf_tsdf_integrate(void* stream, int nu, int nv, int nw, const float* origi
     DURF_REQUIREF(cams_dev || F == 0, "cams_dev for F = %d", F);
     DURF_REQUIREF(depth || F == 0, "depth for F = %d", F);
     if (F == 0) return 0;
-    TsdfLattice L;
-    L.nu = nu, L.nv = nv, L.nw = nw, L.n = n;
-    for (int c = 0; c < 3; c++) L.origin[c] = origin_host[c], L.du[c] = du_host[c], L.dv[c] = dv_host[c], L.dw[c] = dw_host[c];
+    const LatticeDims L{nu, nv, nw, n};
+    const LatticeFrame G = lattice_frame(origin_host, du_host, dv_host, dw_host);
     TsdfFrames A;
     A.F = F, A.h = h, A.w = w;
     A.cams = cams_dev, A.depth = depth, A.acc = acc, A.rgb = rgb, A.label = label, A.xform = xform, A.frame_weight = frame_weight;
     A.min_acc = min_acc, A.trunc = trunc, A.max_weight = max_weight, A.znear = znear;
     A.select = select, A.other_mode = other_mode;
-    hipLaunchKernelGGL(k_tsdf_integrate, dim3(durf_cdiv((size_t)n, TB)), dim3(TB), 0, (hipStream_t)stream, L, A, tsdf, weight, colour);
+    hipLaunchKernelGGL(k_tsdf_integrate, dim3(durf_cdiv((size_t)n, TB)), dim3(TB), 0, (hipStream_t)stream, L, G, A, tsdf, weight, colour);
     DURF_CHECK_LAUNCH("k_tsdf_integrate");
     return 0;
 }
 
 int durf_tsdf_lattice(void* stream, int nu, int nv, int nw, const float* tsdf, const float* weight, const float* colour, float min_weight,
                       float* density, uint8_t* valid, float* rgb_out) {
-    const int n = check_tsdf_shape(__func__, nu, nv, nw);
+    const int n = check_lattice_shape(__func__, nu, nv, nw, DURF_TSDF_MAX_POINTS);
     if (n < 0) return -1;
     DURF_REQUIREF(min_weight == min_weight, "min_weight is a number, min_weight = %g", (double)min_weight);
     DURF_REQUIRE(tsdf, "tsdf");
@@ -282,7 +264,7 @@ int durf_tsdf_lattice(void* stream, int nu, int nv, int nw, const float* tsdf, c
 int durf_tsdf_sample(void* stream, int nu, int nv, int nw, const float* origin_host, const float* inv_host, const float* tsdf,
                      const float* weight, const float* colour, float trunc, float min_weight, int m, const float* points, float* sdf,
                      uint8_t* ok, float* rgb_out) {
-    const int n = check_tsdf_shape(__func__, nu, nv, nw);
+    const int n = check_lattice_shape(__func__, nu, nv, nw, DURF_TSDF_MAX_POINTS);
     if (n < 0) return -1;
     DURF_REQUIREF(m >= 0, "m >= 0, m = %d", m);
     DURF_REQUIREF(trunc > 0.0f && trunc <= FLT_MAX, "trunc > 0 and finite, trunc = %g", (double)trunc);

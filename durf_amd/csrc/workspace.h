@@ -55,4 +55,11 @@ inline int check_workspace(const char* who, size_t have, size_t need, const char
     return -1;
 }
 
+// every workspace starts on 256 bytes, as the carver's sub-buffers do
+inline int check_workspace_aligned(const char* who, const void* p) {
+    if (p != nullptr && ((size_t)p & 255) == 0) return 0;
+    durf_set_error("%s: requirement failed: workspace aligned to 256 bytes", who);
+    return -1;
+}
+
 }  // namespace durf

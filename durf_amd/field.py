@@ -16,6 +16,8 @@ import json
 
 import numpy as np
 
+from . import lattice
+
 
 def _refuse(model, variables, entry):
     if model.use_viewdirs is False or not variables.layout.use_viewdirs:
@@ -98,22 +100,14 @@ def grid(model, variables, origin, shape, step=None, axes=None, view=None, sigma
     [nu,nv,nw,.] tensors, plus `frame` (origin, du, dv, dw, shape: what write_density records) and, with want_points,
     points [nu,nv,nw,3]."""
     from . import ops
-    if (step is None) == (axes is None):
-        raise ValueError('field.grid: give step or axes')
-    if axes is None:
-        s = float(step)
-        axes = ((s, 0.0, 0.0), (0.0, s, 0.0), (0.0, 0.0, s))
-    du, dv, dw = ([float(x) for x in v] for v in axes)
-    origin = [float(x) for x in origin]
-    shape = tuple(int(s) for s in shape)
-    if len(origin) != 3 or len(shape) != 3 or any(len(v) != 3 for v in (du, dv, dw)):
-        raise ValueError('field.grid: origin, the axes and shape have three components each')
+    frame = lattice.frame(origin, shape, step, axes, 'field.grid')
+    shape = tuple(frame['shape'])
     if int(chunk) <= 0:
         raise ValueError('field.grid: chunk = %r' % (chunk,))
     a, keep = _args(model, variables, 'field.grid', ext, sigma, ts, alpha, pose, box_enable, inside_tol)
-    res = ops.field_grid(a, origin, du, dv, dw, shape, view, chunk, variables.flat.device, want_points)
+    res = ops.field_grid(a, frame['origin'], frame['du'], frame['dv'], frame['dw'], shape, view, chunk, variables.flat.device, want_points)
     out = {k: (None if v is None else v.reshape(shape + tuple(v.shape[1:]))) for k, v in res.items()}
-    out['frame'] = dict(origin=origin, du=du, dv=dv, dw=dw, shape=list(shape))
+    out['frame'] = frame
     return out
 
 

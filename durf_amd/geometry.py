@@ -16,17 +16,11 @@ cells per axis) makes the result equal to a brute-force search in the same fp32 
 import numpy as np
 
 from . import camera
+from .lattice import _max_dist
 from ._geom_sigs import DURF_GEOM_MAX_CELLS as MAX_CELLS        # per axis (include/durf_geom.h)
 SLACK = 1.0 + 2.0 ** -10            # a cell is max_dist * SLACK wide
 SORT_QUERIES = True                 # nearest()'s default: queries in the order of their own cell keys (profiles/geometry_time.txt)
 DEFAULT_THRESHOLDS = (0.05, 0.1, 0.2, 0.5)
-
-
-def _max_dist(max_dist, entry):
-    md = float(np.float32(max_dist))
-    if not (1e-18 <= md <= 1e18):
-        raise ValueError('%s: max_dist = %r, expected a number in [1e-18, 1e18]' % (entry, max_dist))
-    return md
 
 
 def grid_rule(lo, hi, max_dist, entry='geometry.nearest'):

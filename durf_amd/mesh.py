@@ -15,6 +15,9 @@ solid.  A vertex next to an unusable lattice point (a cell in several boxes, a N
 documented, not repaired."""
 import numpy as np
 
+from . import lattice
+from .lattice import _host
+
 
 def aa2matrix(rotvec):
     """the world->object matrix of a pose's rotation vector in float64 (csrc/aa2matrix.h: safe_norm's clamp, the +1e-12)"""
@@ -26,19 +29,8 @@ def aa2matrix(rotvec):
 
 
 def host_frame(frame, entry='mesh.surface'):
-    """frame dict(origin, du, dv, dw) -> (origin, du, dv, dw float32 [3], A float32 [9]: the inverse transpose of [du dv dw],
-    computed in float64 from the float32 values the library receives, flip: the frame is left-handed).  A singular frame is
-    refused."""
-    o, du, dv, dw = (np.asarray(frame[k], np.float64).reshape(-1).astype(np.float32) for k in ('origin', 'du', 'dv', 'dw'))
-    if any(v.size != 3 for v in (o, du, dv, dw)):
-        raise ValueError('%s: origin, du, dv and dw have three components each' % entry)
-    J = np.stack([du, dv, dw], 1).astype(np.float64)
-    det = float(np.linalg.det(J))
-    scale = float(np.linalg.norm(J[:, 0]) * np.linalg.norm(J[:, 1]) * np.linalg.norm(J[:, 2]))
-    if not np.isfinite(J).all() or not np.isfinite(o).all() or not abs(det) > 1e-9 * scale:
-        raise ValueError('%s: a singular frame (det [du dv dw] = %g): du = %s, dv = %s, dw = %s'
-                         % (entry, det, du.tolist(), dv.tolist(), dw.tolist()))
-    return o, du, dv, dw, np.linalg.inv(J).T.astype(np.float32).reshape(-1), det < 0
+    """lattice.host under the name callers know: (origin, du, dv, dw, A, flip)"""
+    return lattice.host(frame, entry)
 
 
 def _iso(iso, entry):
@@ -58,19 +50,7 @@ def surface(g, iso, normals=True, attrs=()):
     import torch
     from . import ops
     iso = _iso(iso, 'mesh.surface')
-    d = g['density']
-    if not (torch.is_tensor(d) and d.is_cuda and d.dim() == 3):
-        raise ValueError('mesh.surface: density is a [nu,nv,nw] tensor on the device')
-    shape = tuple(int(s) for s in d.shape)
-    if min(shape) < 2 or shape[0] * shape[1] * shape[2] >= 2 ** 27:
-        raise ValueError('mesh.surface: a lattice of %d x %d x %d points (each dimension >= 2, fewer than 2^27 points)' % shape)
-    o, du, dv, dw, A, flip = host_frame(g['frame'])
-    d = d.to(torch.float32).contiguous()
-    v = g.get('valid')
-    if v is not None:
-        v = v.to(device=d.device, dtype=torch.uint8).contiguous()
-        if tuple(v.shape) != shape:
-            raise ValueError('mesh.surface: valid of shape %s for a lattice of %s' % (tuple(v.shape), shape))
+    d, v, shape, (o, du, dv, dw, A, flip) = lattice.device_lattice(g, 'mesh.surface', with_frame=True)
     counts, ws = ops.mesh_count(d, v, shape, iso)
     nv_, nt_ = (int(x) for x in counts.cpu())
     m = ops.mesh_emit(d, v, shape, iso, o, du, dv, dw, ws, nv_, nt_, normal_xform=A if normals else None, flip=flip)
@@ -145,11 +125,9 @@ def object_lattice(c, R, ext_k, step, pad):
     if min(shape) < 3:
         raise ValueError('mesh.extract_object: step = %g leaves a lattice of %s points over half extents %s' % (step, shape, half.tolist()))
     o_obj = np.array([-(n - 1) * step / 2.0 for n in shape])
-    eye = np.eye(3) * step
-    obj = dict(origin=o_obj.tolist(), du=eye[0].tolist(), dv=eye[1].tolist(), dw=eye[2].tolist())
     # X = c + R^T P: the image of object axis j is row j of R
-    world = dict(origin=(c + R.T @ o_obj).tolist(), du=(step * R[0]).tolist(), dv=(step * R[1]).tolist(), dw=(step * R[2]).tolist())
-    return obj, world, shape
+    return (lattice.frame(o_obj, step=step, entry='mesh.extract_object'),
+            lattice.frame(c + R.T @ o_obj, axes=step * R, entry='mesh.extract_object'), shape)
 
 
 def extract_object(model, variables, k, ext, step, iso, ts=0, pad=0.05, colour='query', pose=None, min_points=0, largest=None, **kw):
@@ -218,10 +196,6 @@ _VERTEX = np.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('nx', '<f4'), ('n
                     ('green', 'u1'), ('blue', 'u1')])
 _VERTEX_COMPONENT = np.dtype(_VERTEX.descr + [('component', '<i4')])
 _FACE = np.dtype([('n', 'u1'), ('v', '<i4', (3,))])
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if hasattr(a, 'detach') else np.asarray(a)
 
 
 def write_ply(path, m):

@@ -88,6 +88,19 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+def _z(t):
+    """a tensor's address, or None for no tensor and for one of zero elements (it has no address to hand over)"""
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+def _up256(b):
+    return (b + 255) // 256 * 256
+
+
+def _ws(ws, need, dev):
+    return torch.empty(max(need, 256), dtype=torch.uint8, device=dev) if ws is None else ws
+
+
 def _f32(t):
     assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous(), (t.dtype, t.device, t.is_contiguous())
     return t
@@ -1832,6 +1845,15 @@ def _host_floats(values, n, what):
     return (C.c_float * n)(*a.tolist())
 
 
+def _dims(shape):
+    nu, nv, nw = (int(s) for s in shape)
+    return nu, nv, nw
+
+
+def _lattice_args(origin, du, dv, dw):
+    return _host_floats(origin, 3, 'origin'), _host_floats(du, 3, 'du'), _host_floats(dv, 3, 'dv'), _host_floats(dw, 3, 'dw')
+
+
 def lidar_rays(sensor_row, inclinations, sweep_row, near, far, first=0, count=None):
     """rays [first, first + count) of one sweep (durf_lidar_rays, one launch): sensor_row 6 host floats, inclinations [H] on the
     device, sweep_row 18 host floats -> (origins, directions, viewdirs [count,3], radii, near, far [count])"""
@@ -2166,27 +2188,26 @@ def field_query(a, points, viewdirs, chunk):
 def field_grid(a, origin, du, dv, dw, shape, view, chunk, dev, want_points=False):
     """durf_field_grid: the grid origin + i du + j dv + k dw (k fastest) of shape (nu, nv, nw) in ONE call -> field_query's
     dict over the nu nv nw cells[, points [nu nv nw, 3]]; view: one direction (3 floats) or None (density only)"""
-    nu, nv, nw = (int(s) for s in shape)
+    nu, nv, nw = _dims(shape)
     n = nu * nv * nw
     if min(nu, nv, nw) < 1 or n >= 2 ** 31:
         raise ValueError('field_grid: a grid of %d x %d x %d cells' % (nu, nv, nw))
     out = _field_outputs(a, n, dev, view is not None)
     a.points = a.viewdirs = None
     out['points'] = torch.empty(n, 3, device=dev) if want_points else None
-    f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])
     vx, vy, vz = (float(x) for x in view) if view is not None else (0.0, 0.0, 0.0)
     ck = max(min(int(chunk), n), 1) if chunk > 0 else int(chunk)
     L = _lib.field_lib()
     ws = _workspace(dev, int(L.durf_field_workspace_bytes(ck, a.K)))
     with _Timed('field_grid'):
-        _lib.check(L.durf_field_grid(_stream(), C.addressof(a), f3(origin), f3(du), f3(dv), f3(dw), nu, nv, nw, int(view is not None),
+        _lib.check(L.durf_field_grid(_stream(), C.addressof(a), *_lattice_args(origin, du, dv, dw), nu, nv, nw, int(view is not None),
                                      vx, vy, vz, ck, _p(ws), ws.numel(), _p(out['points'])), 'durf_field_grid')
     return out
 
 
 def field_columns(density, valid, shape, step, threshold):
     """durf_field_columns over density / valid [nu nv nw] -> col_max, col_opacity [nu,nv] float, col_first [nu,nv] int32"""
-    nu, nv, nw = (int(s) for s in shape)
+    nu, nv, nw = _dims(shape)
     dev = density.device
     assert density.numel() == nu * nv * nw and valid.numel() == nu * nv * nw and valid.dtype == torch.uint8 and valid.is_contiguous()
     cmax, cop = torch.empty(nu, nv, device=dev), torch.empty(nu, nv, device=dev)
@@ -2201,21 +2222,20 @@ def field_columns(density, valid, shape, step, threshold):
 # the iso-surface of a density lattice (include/durf_mesh.h, csrc/mesh.hip, libdurf_mesh.so)
 # ---------------------------------------------------------------------------
 def mesh_workspace_bytes(shape):
-    nu, nv, nw = (int(s) for s in shape)
-    return int(_lib.mesh_lib().durf_mesh_workspace_bytes(nu, nv, nw))
+    return int(_lib.mesh_lib().durf_mesh_workspace_bytes(*_dims(shape)))
 
 
 def mesh_workspace_views(ws, shape):
     """voff, toff int32 [n] and mask uint8 [n] of a workspace durf_mesh_count filled (the layout include/durf_mesh.h states)"""
-    n = int(shape[0]) * int(shape[1]) * int(shape[2])
-    up = lambda b: (b + 255) // 256 * 256
-    o1 = up(4 * n)
-    o2 = o1 + up(4 * n)
+    nu, nv, nw = _dims(shape)
+    n = nu * nv * nw
+    o1 = _up256(4 * n)
+    o2 = o1 + _up256(4 * n)
     return ws[:4 * n].view(torch.int32), ws[o1:o1 + 4 * n].view(torch.int32), ws[o2:o2 + n]
 
 
 def _mesh_lattice(density, valid, shape):
-    nu, nv, nw = (int(s) for s in shape)
+    nu, nv, nw = _dims(shape)
     n = nu * nv * nw
     assert density.numel() == n, (tuple(density.shape), shape)
     if valid is not None:
@@ -2229,9 +2249,7 @@ def mesh_count(density, valid, shape, iso, ws=None):
     nu, nv, nw = _mesh_lattice(density, valid, shape)
     dev = density.device
     L = _lib.mesh_lib()
-    need = int(L.durf_mesh_workspace_bytes(nu, nv, nw))
-    if ws is None:
-        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    ws = _ws(ws, int(L.durf_mesh_workspace_bytes(nu, nv, nw)), dev)
     counts = torch.empty(2, dtype=torch.int32, device=dev)
     with _Timed('mesh_count'):
         _lib.check(L.durf_mesh_count(_stream(), nu, nv, nw, _p(_f32(density)), _p(valid), float(iso), _p(ws), ws.numel(), _p(counts)),
@@ -2258,9 +2276,9 @@ def mesh_emit(density, valid, shape, iso, origin, du, dv, dw, ws, max_vertices, 
     A = None if normal_xform is None else _host_floats(normal_xform, 9, 'normal_xform')
     with _Timed('mesh_emit'):
         _lib.check(_lib.mesh_lib().durf_mesh_emit(
-            _stream(), nu, nv, nw, _p(_f32(density)), _p(valid), float(iso), _host_floats(origin, 3, 'origin'), _host_floats(du, 3, 'du'),
-            _host_floats(dv, 3, 'dv'), _host_floats(dw, 3, 'dw'), A, int(bool(flip)), _p(ws), ws.numel(), mv, mt, _p(o['vertices']),
-            _p(o['normals']), _p(o['vertex_edge']), _p(o['vertex_t']), _p(o['triangles'])), 'durf_mesh_emit')
+            _stream(), nu, nv, nw, _p(_f32(density)), _p(valid), float(iso), *_lattice_args(origin, du, dv, dw), A, int(bool(flip)),
+            _p(ws), ws.numel(), mv, mt, _p(o['vertices']), _p(o['normals']), _p(o['vertex_edge']), _p(o['vertex_t']), _p(o['triangles'])),
+            'durf_mesh_emit')
     return o
 
 
@@ -2268,7 +2286,7 @@ def mesh_gather(shape, counts, vertex_edge, vertex_t, attr_f=None, attr_i=None, 
                 out_i=None):
     """durf_mesh_gather: lattice attributes at the vertices -> (out_f [V,C] = a + t (b - a) or None, out_i [V] int32 = the label
     of each edge's in end, or None)"""
-    nu, nv, nw = (int(s) for s in shape)
+    nu, nv, nw = _dims(shape)
     n = nu * nv * nw
     V, dev = int(vertex_edge.shape[0]), vertex_edge.device
     assert vertex_edge.dtype == torch.int32 and vertex_edge.is_contiguous() and vertex_t.numel() == V
@@ -2293,12 +2311,7 @@ def mesh_gather(shape, counts, vertex_edge, vertex_t, attr_f=None, attr_i=None, 
 # connected components of a density lattice (include/durf_parts.h, csrc/parts.hip, libdurf_parts.so)
 # ---------------------------------------------------------------------------
 def parts_workspace_bytes(shape):
-    nu, nv, nw = (int(s) for s in shape)
-    return int(_lib.parts_lib().durf_parts_workspace_bytes(nu, nv, nw))
-
-
-def _parts_ws(ws, need, dev):
-    return torch.empty(max(need, 256), dtype=torch.uint8, device=dev) if ws is None else ws
+    return int(_lib.parts_lib().durf_parts_workspace_bytes(*_dims(shape)))
 
 
 def _i32(t, n, what):
@@ -2312,7 +2325,7 @@ def parts_label(density, valid, shape, iso, ws=None, labels=None):
     nu, nv, nw = _mesh_lattice(density, valid, shape)
     n, dev = nu * nv * nw, density.device
     L = _lib.parts_lib()
-    ws = _parts_ws(ws, int(L.durf_parts_workspace_bytes(nu, nv, nw)), dev)
+    ws = _ws(ws, int(L.durf_parts_workspace_bytes(nu, nv, nw)), dev)
     labels = torch.empty(n, dtype=torch.int32, device=dev) if labels is None else _i32(labels, n, 'labels')
     with _Timed('parts_label'):
         _lib.check(L.durf_parts_label(_stream(), nu, nv, nw, _p(_f32(density)), _p(valid), float(iso), _p(ws), ws.numel(), _p(labels)),
@@ -2325,8 +2338,7 @@ def parts_number(labels, ws=None):
     THE DEVICE).  No read-back."""
     n, dev = int(labels.numel()), labels.device
     _i32(labels, n, 'labels')
-    up = lambda b: (b + 255) // 256 * 256
-    ws = _parts_ws(ws, up(4 * n) + up(4 * ((n + PARTS_BLOCK - 1) // PARTS_BLOCK + 1)), dev)
+    ws = _ws(ws, _up256(4 * n) + _up256(4 * ((n + PARTS_BLOCK - 1) // PARTS_BLOCK + 1)), dev)
     comp, count = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
     with _Timed('parts_number'):
         _lib.check(_lib.parts_lib().durf_parts_number(_stream(), n, _p(labels), _p(ws), ws.numel(), _p(comp), _p(count)), 'durf_parts_number')
@@ -2335,14 +2347,13 @@ def parts_number(labels, ws=None):
 
 def parts_stats(comp, shape, max_components, size=None, bbox=None):
     """durf_parts_stats -> (size int32 [max_components], bbox int32 [max_components,6]: imin, jmin, kmin, imax, jmax, kmax)"""
-    nu, nv, nw = (int(s) for s in shape)
+    nu, nv, nw = _dims(shape)
     mc, dev = int(max_components), comp.device
     _i32(comp, nu * nv * nw, 'comp')
     size = torch.empty(max(mc, 0), dtype=torch.int32, device=dev) if size is None else size
     bbox = torch.empty(max(mc, 0), 6, dtype=torch.int32, device=dev) if bbox is None else bbox
     with _Timed('parts_stats'):
-        _lib.check(_lib.parts_lib().durf_parts_stats(_stream(), nu, nv, nw, _p(comp), mc, _p(size) if mc > 0 else None,
-                                                     _p(bbox) if mc > 0 else None), 'durf_parts_stats')
+        _lib.check(_lib.parts_lib().durf_parts_stats(_stream(), nu, nv, nw, _p(comp), mc, _z(size), _z(bbox)), 'durf_parts_stats')
     return size, bbox
 
 
@@ -2354,13 +2365,12 @@ def parts_select_mesh(counts, vertex_comp, triangles, keep, ws=None):
     _i32(counts, 2, 'counts'), _i32(vertex_comp, V, 'vertex_comp'), _i32(triangles, 3 * T, 'triangles')
     nc = int(keep.numel())
     assert keep.dtype == torch.uint8 and keep.is_contiguous() and keep.is_cuda
-    ws = _parts_ws(ws, (8 * ((max(V, T) + PARTS_BLOCK - 1) // PARTS_BLOCK + 1) + 255) // 256 * 256, dev)
+    ws = _ws(ws, _up256(8 * ((max(V, T) + PARTS_BLOCK - 1) // PARTS_BLOCK + 1)), dev)
     vmap, vsrc = torch.empty(V, dtype=torch.int32, device=dev), torch.empty(V, dtype=torch.int32, device=dev)
     tri, out = torch.empty(T, 3, dtype=torch.int32, device=dev), torch.empty(2, dtype=torch.int32, device=dev)
-    z = lambda t, k: _p(t) if k else None                                # (a zero-row tensor has no address to hand over)
     with _Timed('parts_select_mesh'):
-        _lib.check(_lib.parts_lib().durf_parts_select_mesh(_stream(), _p(counts), V, T, z(vertex_comp, V), z(triangles, T), z(keep, nc), nc,
-                                                           _p(ws), ws.numel(), z(vmap, V), z(vsrc, V), z(tri, T), _p(out)),
+        _lib.check(_lib.parts_lib().durf_parts_select_mesh(_stream(), _p(counts), V, T, _z(vertex_comp), _z(triangles), _z(keep), nc,
+                                                           _p(ws), ws.numel(), _z(vmap), _z(vsrc), _z(tri), _p(out)),
                    'durf_parts_select_mesh')
     return vmap, vsrc, tri, out
 
@@ -2384,22 +2394,12 @@ def _raster_mesh(cams, vertices, triangles):
     return int(cams.shape[0]), V, T
 
 
-def _raster_ws(ws, F, T, h, w, dev):
-    need = raster_workspace_bytes(F, T, h, w)
-    return torch.empty(max(need, 256), dtype=torch.uint8, device=dev) if ws is None else ws
-
-
-def _z(t):
-    """a tensor's address, or None for no tensor and for one of zero elements (it has no address to hand over)"""
-    return None if t is None or t.numel() == 0 else t.data_ptr()
-
-
 def raster_setup(cams, h, w, vertices, triangles, znear, cull=0, ws=None):
     """durf_raster_setup: project, cull, snap and count per tile, scan -> (counts int32 [RASTER_COUNTS] ON THE DEVICE:
     RASTER_COUNT_FIELDS; the workspace, a uint8 tensor raster_draw reads).  No read-back."""
     F, V, T = _raster_mesh(cams, vertices, triangles)
     dev = cams.device
-    ws = _raster_ws(ws, F, T, h, w, dev)
+    ws = _ws(ws, raster_workspace_bytes(F, T, h, w), dev)
     counts = torch.empty(RASTER_COUNTS, dtype=torch.int32, device=dev)
     with _Timed('raster_setup'):
         _lib.check(_lib.raster_lib().durf_raster_setup(_stream(), F, int(h), int(w), _z(cams), V, T, _z(vertices), _z(triangles), float(znear),
@@ -2453,7 +2453,7 @@ def raster_render_mesh(cams, h, w, vertices, triangles, znear, max_pairs, cull=0
     counts (ON THE DEVICE), tri, depth, bary, out_f, out_i.  counts[0] > max_pairs: the -2 / NaN picture."""
     F, V, T = _raster_mesh(cams, vertices, triangles)
     dev, mp = cams.device, int(max_pairs)
-    ws = _raster_ws(ws, F, T, h, w, dev)
+    ws = _ws(ws, raster_workspace_bytes(F, T, h, w), dev)
     if pairs is None:
         pairs = torch.empty(max(mp, 0), dtype=torch.int32, device=dev)
     Cn, attr_f, attr_i = _raster_attrs(V, attr_f, attr_i)
@@ -2490,8 +2490,8 @@ def geom_keys(points, origin, inv_cell, dims):
     n = int(_geom_points(points, 'points').shape[0])
     keys = torch.empty(n, dtype=torch.int64, device=points.device)
     with _Timed('geom_keys'):
-        _lib.check(_lib.geom_lib().durf_geom_keys(_stream(), n, _p(points) if n else None, _host_floats(origin, 3, 'origin'), float(inv_cell),
-                                                  int(dims[0]), int(dims[1]), int(dims[2]), _p(keys) if n else None), 'durf_geom_keys')
+        _lib.check(_lib.geom_lib().durf_geom_keys(_stream(), n, _z(points), _host_floats(origin, 3, 'origin'), float(inv_cell),
+                                                  int(dims[0]), int(dims[1]), int(dims[2]), _z(keys)), 'durf_geom_keys')
     return keys
 
 
@@ -2503,11 +2503,10 @@ def geom_nearest(query, ref_sorted, ref_keys, ref_index, origin, inv_cell, dims,
     assert ref_index.dtype == torch.int32 and ref_index.is_contiguous() and ref_index.numel() == m
     dev = query.device
     dist, index = torch.empty(q, device=dev), torch.empty(q, dtype=torch.int32, device=dev)
-    z = lambda t, k: _p(t) if k else None                                # (a zero-row tensor has no address to hand over)
     with _Timed('geom_nearest'):
         _lib.check(_lib.geom_lib().durf_geom_nearest(
-            _stream(), q, z(query, q), m, z(ref_sorted, m), z(ref_keys, m), z(ref_index, m), _host_floats(origin, 3, 'origin'),
-            float(inv_cell), int(dims[0]), int(dims[1]), int(dims[2]), float(max_dist), z(dist, q), z(index, q)), 'durf_geom_nearest')
+            _stream(), q, _z(query), m, _z(ref_sorted), _z(ref_keys), _z(ref_index), _host_floats(origin, 3, 'origin'),
+            float(inv_cell), int(dims[0]), int(dims[1]), int(dims[2]), float(max_dist), _z(dist), _z(index)), 'durf_geom_nearest')
     return dist, index
 
 
@@ -2518,15 +2517,13 @@ def geom_stats(dist, index, thresholds=(), out=None, ws=None):
     assert index.dtype == torch.int32 and index.is_contiguous() and index.numel() == q and _f32(dist) is dist
     th = [float(t) for t in thresholds]
     L = _lib.geom_lib()
-    need = int(L.durf_geom_workspace_bytes(q, 0))
-    if ws is None:
-        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dist.device)
+    ws = _ws(ws, int(L.durf_geom_workspace_bytes(q, 0)), dist.device)
     if out is None:
         out = torch.empty(GEOM_STAT_DOUBLES, dtype=torch.float64, device=dist.device)
     assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == GEOM_STAT_DOUBLES
     arr = (C.c_float * max(len(th), 1))(*th)
     with _Timed('geom_stats'):
-        _lib.check(L.durf_geom_stats(_stream(), q, _p(dist) if q else None, _p(index) if q else None, len(th), arr, _p(ws), ws.numel(),
+        _lib.check(L.durf_geom_stats(_stream(), q, _z(dist), _z(index), len(th), arr, _p(ws), ws.numel(),
                                      _p(out)), 'durf_geom_stats')
     return out
 
@@ -2538,14 +2535,12 @@ def geom_sample_mesh(vertices, triangles, n, ws=None):
     assert triangles.dtype == torch.int32 and triangles.is_contiguous() and triangles.dim() == 2 and triangles.shape[1] == 3
     dev = vertices.device
     L = _lib.geom_lib()
-    need = int(L.durf_geom_workspace_bytes(0, T))
-    if ws is None:
-        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    ws = _ws(ws, int(L.durf_geom_workspace_bytes(0, T)), dev)
     points, tri = torch.empty(max(n, 0), 3, device=dev), torch.empty(max(n, 0), dtype=torch.int32, device=dev)
     total = torch.empty(1, dtype=torch.float64, device=dev)
     with _Timed('geom_sample_mesh'):
-        _lib.check(L.durf_geom_sample_mesh(_stream(), V, _p(vertices) if V else None, T, _p(triangles) if T else None, n, _p(ws), ws.numel(),
-                                           _p(points) if n > 0 else None, _p(tri) if n > 0 else None, _p(total)), 'durf_geom_sample_mesh')
+        _lib.check(L.durf_geom_sample_mesh(_stream(), V, _z(vertices), T, _z(triangles), n, _p(ws), ws.numel(), _z(points), _z(tri),
+                                           _p(total)), 'durf_geom_sample_mesh')
     return points, tri, total
 
 
@@ -2553,7 +2548,7 @@ def geom_sample_mesh(vertices, triangles, n, ws=None):
 # depth frames fused into a TSDF volume (include/durf_tsdf.h, csrc/tsdf.hip, libdurf_tsdf.so)
 # ---------------------------------------------------------------------------
 def _tsdf_state(tsdf, weight, colour, shape):
-    nu, nv, nw = (int(s) for s in shape)
+    nu, nv, nw = _dims(shape)
     n = nu * nv * nw
     assert _f32(tsdf).numel() == n and _f32(weight).numel() == n, (tuple(tsdf.shape), tuple(weight.shape), shape)
     assert colour is None or _f32(colour).numel() == 4 * n, (tuple(colour.shape), shape)
@@ -2576,9 +2571,9 @@ def tsdf_integrate(tsdf, weight, colour, shape, origin, du, dv, dw, cams, depth,
     assert frame_weight is None or _f32(frame_weight).numel() == F
     with _Timed('tsdf_integrate'):
         _lib.check(_lib.tsdf_lib().durf_tsdf_integrate(
-            _stream(), nu, nv, nw, _host_floats(origin, 3, 'origin'), _host_floats(du, 3, 'du'), _host_floats(dv, 3, 'dv'),
-            _host_floats(dw, 3, 'dw'), F, h, w, _z(cams), _z(depth), _z(acc), float(min_acc), _z(rgb), _z(label), int(select), int(other_mode),
-            _z(xform), _z(frame_weight), float(trunc), float(max_weight), float(znear), _p(tsdf), _p(weight), _p(colour)), 'durf_tsdf_integrate')
+            _stream(), nu, nv, nw, *_lattice_args(origin, du, dv, dw), F, h, w, _z(cams), _z(depth), _z(acc), float(min_acc), _z(rgb),
+            _z(label), int(select), int(other_mode), _z(xform), _z(frame_weight), float(trunc), float(max_weight), float(znear), _p(tsdf),
+            _p(weight), _p(colour)), 'durf_tsdf_integrate')
 
 
 def tsdf_lattice(tsdf, weight, colour, shape, min_weight=1.0, want_rgb=True):
@@ -2714,12 +2709,11 @@ def closest_points(ws, T, points, max_dist=float('inf'), want_bary=True, want_po
 def closest_grid(ws, T, shape, origin, du, dv, dw, max_dist=float('inf'), want_tri=True):
     """durf_closest_grid: the lattice of shape (nu, nv, nw) at origin + i du + j dv + k dw (host floats), its points generated in
     the kernel -> (dist [nu,nv,nw], tri int32 [nu,nv,nw] or None)"""
-    nu, nv, nw = (int(s) for s in shape)
+    nu, nv, nw = _dims(shape)
     dev = ws.device
     dist = torch.empty(max(nu, 0), max(nv, 0), max(nw, 0), device=dev)
     tri = torch.empty(max(nu, 0), max(nv, 0), max(nw, 0), dtype=torch.int32, device=dev) if want_tri else None
     with _Timed('closest_grid'):
-        _lib.check(_lib.closest_lib().durf_closest_grid(_stream(), nu, nv, nw, _host_floats(origin, 3, 'origin'), _host_floats(du, 3, 'du'),
-                                                        _host_floats(dv, 3, 'dv'), _host_floats(dw, 3, 'dw'), float(max_dist), int(T),
-                                                        _p(ws), ws.numel(), _p(dist), _p(tri)), 'durf_closest_grid')
+        _lib.check(_lib.closest_lib().durf_closest_grid(_stream(), nu, nv, nw, *_lattice_args(origin, du, dv, dw), float(max_dist), int(T), _p(ws),
+                                                        ws.numel(), _p(dist), _p(tri)), 'durf_closest_grid')
     return dist, tri

@@ -15,21 +15,7 @@ are untouched, nothing is re-meshed and no density is overwritten
 value read back by components is the number of components, as mesh.surface reads its two counts."""
 
 
-def _lattice(g, entry):
-    import torch
-    d = g['density']
-    if not (torch.is_tensor(d) and d.is_cuda and d.dim() == 3):
-        raise ValueError('%s: density is a [nu,nv,nw] tensor on the device' % entry)
-    shape = tuple(int(s) for s in d.shape)
-    if min(shape) < 2 or shape[0] * shape[1] * shape[2] >= 2 ** 27:
-        raise ValueError('%s: a lattice of %d x %d x %d points (each dimension >= 2, fewer than 2^27 points)' % ((entry,) + shape))
-    d = d.to(torch.float32).contiguous()
-    v = g.get('valid')
-    if v is not None:
-        v = v.to(device=d.device, dtype=torch.uint8).contiguous()
-        if tuple(v.shape) != shape:
-            raise ValueError('%s: valid of shape %s for a lattice of %s' % (entry, tuple(v.shape), shape))
-    return d, v, shape
+from .lattice import device_lattice as _lattice
 
 
 def components(g, iso):

@@ -14,15 +14,12 @@ integer coverage: the same inputs give the same bits.  A triangle that crosses t
 import numpy as np
 
 from . import camera
+from .lattice import _host
 from ._raster_sigs import DURF_RASTER_MAX_SIZE as MAX_SIZE, DURF_RASTER_RECORD_INTS as RECORD_INTS, DURF_RASTER_TILE as TILE
 
 COUNT_FIELDS = ('pairs', 'drawn', 'invalid', 'behind', 'crossing', 'range', 'degenerate', 'culled')
 WORKSPACE_BOUND = 1 << 30           # bytes: render_mesh chunks over frames to keep the workspace of one call under this
 ATTRIBUTES = ('rgb', 'normals', 'owner', 'component')              # what merge carries when every mesh has it
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if hasattr(a, 'detach') else np.asarray(a)
 
 
 def workspace_estimate(F, T, h, w):

@@ -15,11 +15,8 @@ moves through, from the pixels the instance map gives it.  The known artefact is
 false surface at the back of the truncation band where another camera sees free space."""
 import numpy as np
 
-from . import camera
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if hasattr(a, 'detach') else np.asarray(a)
+from . import camera, lattice as lat                  # (lattice() below is this module's own function)
+from .lattice import _host
 
 
 def volume(origin, shape, step=None, axes=None, trunc=None, colour=True, device=None):
@@ -27,23 +24,11 @@ def volume(origin, shape, step=None, axes=None, trunc=None, colour=True, device=
     x, y, z, or axes = (du, dv, dw)); trunc: the half width of the band, in scene units (a few voxel steps) -> dict tsdf, weight
     [nu,nv,nw] float32 and colour [nu,nv,nw,4] (None with colour=False) on the device, all zero, plus frame, shape and trunc."""
     import torch
-    if (step is None) == (axes is None):
-        raise ValueError('tsdf.volume: give step or axes')
-    if axes is None:
-        s = float(step)
-        axes = ((s, 0.0, 0.0), (0.0, s, 0.0), (0.0, 0.0, s))
-    du, dv, dw = ([float(x) for x in v] for v in axes)
-    origin = [float(x) for x in origin]
-    shape = tuple(int(s) for s in shape)
-    if len(origin) != 3 or len(shape) != 3 or any(len(v) != 3 for v in (du, dv, dw)):
-        raise ValueError('tsdf.volume: origin, the axes and shape have three components each')
-    if min(shape) < 2 or shape[0] * shape[1] * shape[2] >= 2 ** 27:
-        raise ValueError('tsdf.volume: a lattice of %d x %d x %d points (each dimension >= 2, fewer than 2^27 points)' % shape)
+    frame = lat.frame(origin, shape, step, axes, 'tsdf.volume')
+    shape = lat.check_shape(shape, 'tsdf.volume')
     if trunc is None or not (float(trunc) > 0 and np.isfinite(float(trunc))):
         raise ValueError('tsdf.volume: trunc = %r, expected a finite number > 0 (the half width of the band, in scene units)' % (trunc,))
-    frame = dict(origin=origin, du=du, dv=dv, dw=dw, shape=list(shape))
-    from . import mesh
-    mesh.host_frame(frame, 'tsdf.volume')                                    # a singular frame is refused here, not at sample()
+    lat.host(frame, 'tsdf.volume')                                       # a singular frame is refused here, not at sample()
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     return dict(tsdf=torch.zeros(shape, device=dev), weight=torch.zeros(shape, device=dev),
                 colour=torch.zeros(shape + (4,), device=dev) if colour else None, frame=frame, shape=shape, trunc=float(trunc))
@@ -101,8 +86,8 @@ def integrate(vol, cams, depth, acc=None, rgb=None, label=None, select=None, car
     shape = _check_volume(vol, 'tsdf.integrate')
     F, h, w = check_frames(cams, depth, acc, rgb, label, select, carve, xform, frame_weight, min_acc, max_weight, znear)
     import torch
-    from . import mesh, ops
-    o, du, dv, dw = mesh.host_frame(vol['frame'], 'tsdf.integrate')[:4]
+    from . import ops
+    o, du, dv, dw = lat.host(vol['frame'], 'tsdf.integrate')[:4]
     dev = vol['tsdf'].device
     up = lambda a, dt: None if a is None else \
         torch.as_tensor(np.ascontiguousarray(a) if not torch.is_tensor(a) else a).to(device=dev, dtype=dt).contiguous()
@@ -152,9 +137,9 @@ def sample(vol, points, min_weight=1.0):
     if len(tuple(points.shape)) != 2 or points.shape[1] != 3:
         raise ValueError('tsdf.sample: points of shape %s, expected [m,3]' % (tuple(points.shape),))
     import torch
-    from . import mesh, ops
-    o, du, dv, dw, A, _ = mesh.host_frame(vol['frame'], 'tsdf.sample')
-    inv = np.ascontiguousarray(A.reshape(3, 3).T)                            # host_frame's A is the inverse TRANSPOSE of [du dv dw]
+    from . import ops
+    o, du, dv, dw, A, _ = lat.host(vol['frame'], 'tsdf.sample')
+    inv = np.ascontiguousarray(A.reshape(3, 3).T)                            # lattice.host's A is the inverse TRANSPOSE of [du dv dw]
     dev = vol['tsdf'].device
     p = torch.as_tensor(np.ascontiguousarray(points) if not torch.is_tensor(points) else points).to(device=dev, dtype=torch.float32).contiguous()
     sdf, ok, rgb = ops.tsdf_sample(vol['tsdf'], vol['weight'], vol.get('colour'), shape, o, inv, vol['trunc'], p, min_weight)

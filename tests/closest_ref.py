@@ -219,13 +219,6 @@ def walk32(vertices, triangles, order, points, max_dist=np.inf, stats=None):
     return _finish(P, usable, max_dist, best_id, best_d2, best_w, best_c)
 
 
-def lattice32(shape, origin, du, dv, dw):
-    """durf_tsdf.h's P_c in its float order for every point of the lattice -> [nu nv nw, 3], index g = (i nv + j) nw + k"""
-    o, du, dv, dw = (_f(x).reshape(3) for x in (origin, du, dv, dw))
-    i, j, k = (x.reshape(-1, 1).astype(F32) for x in np.meshgrid(*[np.arange(s) for s in shape], indexing='ij'))
-    return (((o + i * du) + j * dv) + k * dw).astype(F32)
-
-
 # ---- scenes -----------------------------------------------------------------------------------------------------------------------
 def near_points(vertices, triangles, n, seed, spread=0.2):
     """n points: three in four near a point of a triangle of the mesh (within `spread`), the others anywhere around the unit cube"""

@@ -196,14 +196,6 @@ def query(params, points, viewdirs, pose, ext, enable=None, sigma=0.0, alpha=10.
 
 
 # ---- grids and columns --------------------------------------------------------------------------------------------------------
-def grid_points(origin, du, dv, dw, shape, dt=F64):
-    """X(i, j, k) = ((origin + i du) + j dv) + k dw, k fastest -> [nu nv nw, 3]"""
-    o, du, dv, dw = (_a(v, dt) for v in (origin, du, dv, dw))
-    nu, nv, nw = shape
-    i, j, k = (g.reshape(-1).astype(dt) for g in np.meshgrid(np.arange(nu), np.arange(nv), np.arange(nw), indexing='ij'))
-    return np.stack([((o[c] + i * du[c]) + j * dv[c]) + k * dw[c] for c in range(3)], 1).astype(dt)
-
-
 def columns(density, valid, shape, step, threshold):
     """-> col_max [nu,nv] float32 (exact: a maximum of the inputs), sum [nu,nv] float64 of the counted densities, opacity
     float64 = 1 - exp(-step sum), first [nu,nv] int32"""

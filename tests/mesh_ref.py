@@ -13,6 +13,9 @@ import itertools
 
 import numpy as np
 
+from tests import lattice_ref
+from tests.lattice_ref import host_frame  # noqa: F401  (the frame and its inverse are lattice_ref's)
+
 PERMS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
 POP8 = np.array([bin(x).count('1') for x in range(256)], np.int64)
 
@@ -146,34 +149,18 @@ def gradient(density, valid, dt):
     return out
 
 
-def host_frame(frame):
-    """origin, du, dv, dw as the float32 values the library receives, and A = the inverse transpose of [du dv dw] computed in
-    float64 from them and rounded to float32 (row-major nine), and the handedness"""
-    o, du, dv, dw = (np.asarray(frame[k], np.float64).astype(np.float32) for k in ('origin', 'du', 'dv', 'dw'))
-    J = np.stack([du, dv, dw], 1).astype(np.float64)
-    det = float(np.linalg.det(J))
-    A = np.linalg.inv(J).T.astype(np.float32)
-    return o, du, dv, dw, A, det
-
-
 def geometry(density, valid, iso, frame, vertex_edge, dt=np.float64, normals=True):
     """t [V], vertices [V,3], normals [V,3] of the vertices on edges vertex_edge, in dtype dt, the header's order of operations"""
     d = np.asarray(density, np.float32)
-    nu, nv, nw = d.shape
-    o, du, dv, dw, A, _ = host_frame(frame)
-    o, du, dv, dw, A = (x.astype(dt) for x in (o, du, dv, dw, A))
+    A = host_frame(frame)[4].astype(dt)
     g, e = vertex_edge[:, 0].astype(np.int64), vertex_edge[:, 1].astype(np.int64)
-    k, r = g % nw, g // nw
-    j, i = r % nv, r // nv
-    di, dj, dk = (e + 1) >> 2 & 1, (e + 1) >> 1 & 1, (e + 1) & 1
-    gb = g + (di * nv + dj) * nw + dk
+    (i, j, k), (di, dj, dk), gb = lattice_ref.ijk(g, d.shape), lattice_ref.edge(e), lattice_ref.edge_end(g, e, d.shape)
     flat = d.reshape(-1).astype(dt)
     da, db = flat[g], flat[gb]
     with np.errstate(all='ignore'):
         t = (dt(np.float32(iso)) - da) / (db - da)
         t = np.fmin(np.fmax(t, dt(0)), dt(1))
-    q = [i.astype(dt) + t * di.astype(dt), j.astype(dt) + t * dj.astype(dt), k.astype(dt) + t * dk.astype(dt)]
-    X = np.stack([((o[c] + q[0] * du[c]) + q[1] * dv[c]) + q[2] * dw[c] for c in range(3)], 1)
+    X = lattice_ref.place(frame, [i.astype(dt) + t * di.astype(dt), j.astype(dt) + t * dj.astype(dt), k.astype(dt) + t * dk.astype(dt)], dt)
     nrm = None
     if normals:
         G = gradient(density, valid, dt).reshape(-1, 3)
@@ -195,9 +182,8 @@ def surface(density, valid, iso, frame, flip=False, dt=np.float64, normals=True)
 
 def gather_float(attr, vertex_edge, t, shape, dt=np.float64):
     """attr [n,C] at the vertices: a + t (b - a)"""
-    nu, nv, nw = shape
     g, e = vertex_edge[:, 0].astype(np.int64), vertex_edge[:, 1].astype(np.int64)
-    gb = g + (((e + 1) >> 2 & 1) * nv + ((e + 1) >> 1 & 1)) * nw + ((e + 1) & 1)
+    gb = lattice_ref.edge_end(g, e, shape)
     a, b = np.asarray(attr, np.float32).astype(dt)[g], np.asarray(attr, np.float32).astype(dt)[gb]
     return a + np.asarray(t, dt)[:, None] * (b - a)
 
@@ -205,9 +191,8 @@ def gather_float(attr, vertex_edge, t, shape, dt=np.float64):
 def gather_label(label, vertex_edge, density, valid, iso):
     """the label of each edge's in end"""
     _, inn = lattice_state(density, valid, iso)
-    nu, nv, nw = inn.shape
     g, e = vertex_edge[:, 0].astype(np.int64), vertex_edge[:, 1].astype(np.int64)
-    gb = g + (((e + 1) >> 2 & 1) * nv + ((e + 1) >> 1 & 1)) * nw + ((e + 1) & 1)
+    gb = lattice_ref.edge_end(g, e, inn.shape)
     return np.where(inn.reshape(-1)[g], np.asarray(label).reshape(-1)[g], np.asarray(label).reshape(-1)[gb])
 
 
@@ -252,6 +237,7 @@ def ulp32(x):
 
 # ---- planted fields -------------------------------------------------------------------------------------------------------------
 def lattice_points(frame, shape):
+    """float64 from the frame's values AS GIVEN (the planted fields' bits hang on it): not the libraries' rule, lattice_ref.points"""
     o, du, dv, dw = (np.asarray(frame[k], np.float64) for k in ('origin', 'du', 'dv', 'dw'))
     i, j, k = np.meshgrid(*[np.arange(s, dtype=np.float64) for s in shape], indexing='ij')
     return o + i[..., None] * du + j[..., None] * dv + k[..., None] * dw
@@ -287,4 +273,4 @@ def corner_patterns(density, iso):
 
 
 def unit_frame(step=1.0, origin=(0.0, 0.0, 0.0)):
-    return dict(origin=list(origin), du=[step, 0.0, 0.0], dv=[0.0, step, 0.0], dw=[0.0, 0.0, step])
+    return lattice_ref.frame_of(origin, step)

@@ -2,7 +2,9 @@
 structure -- no tiles, no passes, no atomics: one union-find over every owned edge whose two ends are IN, by minimum index."""
 import numpy as np
 
-OFFSETS = tuple(((e + 1) >> 2, (e + 1) >> 1 & 1, (e + 1) & 1) for e in range(7))       # o_e: the bits of e + 1
+from tests import lattice_ref
+
+OFFSETS = tuple(lattice_ref.edge(e) for e in range(7))       # o_e: the bits of e + 1
 
 
 def in_points(density, valid, iso):
@@ -89,9 +91,8 @@ def min_index_labels(numbered):
 
 def vertex_component(comp, vertex_edge, inn):
     """the component of each vertex's IN end: vertex_edge [V,2] = (g, e)"""
-    nu, nv, nw = comp.shape
-    g, e = vertex_edge[:, 0].astype(np.int64), vertex_edge[:, 1].astype(np.int64) + 1
-    gb = g + ((e >> 2) * nv + (e >> 1 & 1)) * nw + (e & 1)
+    g, e = vertex_edge[:, 0].astype(np.int64), vertex_edge[:, 1].astype(np.int64)
+    gb = lattice_ref.edge_end(g, e, comp.shape)
     return np.where(inn.reshape(-1)[g], comp.reshape(-1)[g], comp.reshape(-1)[gb]).astype(np.int32)
 
 

@@ -18,6 +18,7 @@ from durf_amd import _lib, field, ops, synthetic
 from oracle import durf_ref as R
 from tests import enc_rows_ref as E
 from tests import field_ref as F
+from tests import lattice_ref
 from tests import overlay_ref as OR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -123,7 +124,7 @@ def test_the_yardstick_is_the_float32_twins_distance():
 
 
 def test_columns_and_grid_oracle():
-    g = F.grid_points((1, 2, 3), (0.5, 0, 0), (0, 0.25, 0), (0, 0, 2), (2, 3, 4))
+    g = lattice_ref.points(dict(origin=(1, 2, 3), du=(0.5, 0, 0), dv=(0, 0.25, 0), dw=(0, 0, 2)), (2, 3, 4), np.float64)
     assert g.shape == (24, 3) and (g[1] == (1, 2, 5)).all() and (g[4] == (1, 2.25, 3)).all() and (g[12] == (1.5, 2, 3)).all()
     d = np.array([[[0.5, np.nan, 3.0, 2.0], [1.0, 1.0, 1.0, 1.0]]], np.float32)
     v = np.array([[[1, 1, 0, 1], [0, 0, 0, 0]]], np.uint8)

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from durf_amd import _lib, cast, closest, geometry, mesh, ops
-from tests import cast_ref as C, closest_ref as R
+from tests import cast_ref as C, closest_ref as R, lattice_ref
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -77,7 +77,7 @@ SKEW = dict(origin=(-1.45, -1.4, -1.5), du=(0.19, 0.01, 0.0), dv=(-0.008, 0.2, 0
 def test_the_lattice_equals_the_points(cuda, shape):
     v, t = C.icosphere(2)
     b = cast.build(dict(vertices=v, triangles=t))
-    P = R.lattice32(shape, **SKEW)
+    P = lattice_ref.points(SKEW, shape, F32)
     for md in (np.inf, 0.6):
         dist, tri = ops.closest_grid(b['ws'], b['T'], shape, SKEW['origin'], SKEW['du'], SKEW['dv'], SKEW['dw'], md)
         assert tuple(dist.shape) == shape and tuple(tri.shape) == shape
@@ -95,7 +95,7 @@ def test_the_offset_surface_of_a_sphere_through_mesh_surface(cuda):
     r, step = 0.3, 0.2
     axes = np.stack([np.asarray(SKEW[k], np.float64) / step for k in ('du', 'dv', 'dw')])
     g = closest.grid(b, SKEW['origin'], (16, 16, 16), step, axes=axes)
-    assert np.array_equal(R.bits(g['density'].cpu().numpy().reshape(-1)), R.bits(R.closest32(v, t, R.lattice32((16, 16, 16), **SKEW))[1]))
+    assert np.array_equal(R.bits(g['density'].cpu().numpy().reshape(-1)), R.bits(R.closest32(v, t, lattice_ref.points(SKEW, (16, 16, 16), F32))[1]))
     s = mesh.surface(g, r, normals=False)
     X = s['vertices'].cpu().numpy()
     assert X.shape[0] > 500 and s['triangles'].shape[0] > 1000

@@ -14,6 +14,7 @@ from durf_amd import field, obbpose_model, ops, synthetic, utils
 from oracle import durf_ref as R
 from tests import field_ref as F
 from tests import helpers as H
+from tests import lattice_ref
 
 pytestmark = pytest.mark.gpu
 I32 = torch.int32
@@ -289,7 +290,7 @@ def test_grid_is_the_query_of_its_points(cuda):
     g = field.grid(s['model'], s['variables'], origin, shape, axes=axes, view=view, ext=s['ext'], box_enable=s['en'], chunk=100,
                    want_points=True)
     pts = g['points'].reshape(-1, 3)
-    want = F.grid_points(origin, *axes, shape)
+    want = lattice_ref.points(dict(origin=origin, du=axes[0], dv=axes[1], dw=axes[2]), shape, np.float64)
     err = np.abs(pts.cpu().numpy().astype(np.float64) - want)
     assert (err <= 2 * F.ulp32(np.maximum(np.abs(want), np.abs(np.asarray(origin))[None]))).all()
     n = pts.shape[0]

@@ -13,7 +13,7 @@ depth), holes(), random_extras() and random_scene()."""
 import numpy as np
 
 from tests import camera_ref
-
+from tests.lattice_ref import frame_of, inverse_of, points as voxels  # noqa: F401  (the lattice is lattice_ref's)
 from tests.raster_ref import camera, look_at  # noqa: F401  (the camera rows are the rasteriser's)
 
 F32 = np.float32
@@ -21,24 +21,9 @@ MAX_COORD = float(1 << 20)
 RULES = ('updated', 'invalid', 'behind', 'range', 'outside', 'hole', 'faint', 'occluded', 'other', 'weight')
 
 
-def frame_of(origin, step=None, axes=None):
-    if axes is None:
-        s = float(step)
-        axes = ((s, 0.0, 0.0), (0.0, s, 0.0), (0.0, 0.0, s))
-    return dict(origin=[float(x) for x in origin], du=list(map(float, axes[0])), dv=list(map(float, axes[1])), dw=list(map(float, axes[2])))
-
-
 def new_state(shape, colour=True):
     n = int(np.prod(shape))
     return dict(tsdf=np.zeros(n, F32), weight=np.zeros(n, F32), colour=np.zeros((n, 4), F32) if colour else None)
-
-
-def voxels(frame, shape, dtype):
-    """P [n,3] in `dtype`, in the header's order of operations, from the float32 values of the frame"""
-    nu, nv, nw = shape
-    i, j, k = (a.reshape(-1).astype(dtype) for a in np.meshgrid(np.arange(nu), np.arange(nv), np.arange(nw), indexing='ij'))
-    o, du, dv, dw = (np.asarray(frame[key], F32).astype(dtype) for key in ('origin', 'du', 'dv', 'dw'))
-    return np.stack([((o[c] + i * du[c]) + j * dv[c]) + k * dw[c] for c in range(3)], 1)
 
 
 def _integrate(dtype, state, frame, shape, cams, depth, trunc, acc, min_acc, rgb, label, select, other_mode, xform, frame_weight,
@@ -142,12 +127,6 @@ def lattice32(state, min_weight=1.0):
     col = state.get('colour')
     rgb = None if col is None else np.where(col[:, 3:4] > 0, col[:, :3], F32(0)).astype(F32)
     return (-state['tsdf']).astype(F32), (state['weight'] >= F32(min_weight)).astype(np.uint8), rgb
-
-
-def inverse_of(frame):
-    """the nine host floats of durf_tsdf_sample: the inverse of [du dv dw] in float64 from the frame's float32 values"""
-    J = np.stack([np.asarray(frame[k], F32) for k in ('du', 'dv', 'dw')], 1).astype(np.float64)
-    return np.linalg.inv(J).astype(F32)
 
 
 def _lerp(a, b, t):
