@@ -8,7 +8,10 @@
 
 The meshes, --poses / --ts, --traj, --focal, --size, --pp, --cull and --ids are durf_amd.render_mesh's, and so are the files of
 a camera run: OUT2/depth_%04d.npy, depth_%04d.ppm, ids_%04d.ppm per frame -- cast along the pixel's ray (durf_amd.cast.cameras),
-so a camera that stands on or inside the mesh loses nothing to a near plane.  --sweeps: sensor-to-world poses [F,3,4] (npy), one
+so a camera that stands on or inside the mesh loses nothing to a near plane.  --shade [--ao_dirs 64 --ao_reach R --light X Y Z
+--ambient 0.5 --no_sun] adds shade_%04d.ppm (the mesh's colours under a sun with its shadow and ambient occlusion:
+durf_amd.shade.cameras), ao_%04d.ppm and normals_%04d.ppm per frame, and ao_dirs, ao_reach, bias and light to cast.json; R
+defaults to 2 % of the merged mesh's bounding diagonal.  --sweeps: sensor-to-world poses [F,3,4] (npy), one
 standing sweep each, of a sensor with --beams uniform inclinations over --incl degrees and --columns azimuth columns; written
 per sweep as durf_amd.render_lidar names them: range_%04d.npy ([H,W] float32, 0 where nothing is hit) and sweep_%04d.ply.  Either
 way OUT2/cast.json holds the counts of rays, hits and unusable rays per frame or sweep.  --synthetic casts at
@@ -43,6 +46,8 @@ def build_parser():
     ap.add_argument('--ids', choices=('component', 'part', 'tri'), default=None, help='cameras: what ids_%%04d.ppm shows')
     ap.add_argument('--synthetic', action='store_true', help='cast at a synthetic sphere: an orbit of cameras and one sweep from its centre (no data needed)')
     ap.add_argument('--frames', type=int, default=8, help='--synthetic: cameras of the orbit')
+    from . import shade
+    shade.add_arguments(ap)
     return ap
 
 
@@ -52,6 +57,13 @@ def check_args(args):
         return '--beams %d --columns %d --incl %g %g' % (args.beams, args.columns, args.incl[0], args.incl[1])
     if not 0 <= args.near <= args.far:
         return '--near %g --far %g' % (args.near, args.far)
+    if args.shade:
+        from . import shade
+        why = shade.check_arguments(args)
+        if why:
+            return why
+        if not args.synthetic and args.sweeps is not None:
+            return '--shade shades the pictures of cameras (--traj), not --sweeps'
     if args.synthetic:
         return None if args.frames >= 1 else '--frames %d' % args.frames
     if not args.ply:
@@ -130,6 +142,12 @@ def main(argv=None):
             raster.write_ids(os.path.join(args.eval_dir, 'ids_%04d.ppm' % f), picture[f])
         meta.update(h=int(h), w=int(w), focal=float(focal), principal_point=[float(pp[0]), float(pp[1])], cull=args.cull, ids=ids,
                     frames=_counts(r['tri']))
+        if args.shade:
+            from . import shade
+            s = shade.cameras(b, cams, cull=CULL[args.cull], **shade.arguments(args, m['vertices']))
+            for f in range(cams.shape[0]):
+                shade.write_pictures(args.eval_dir, f, s)
+            meta.update(shade.meta(args, s))
         done.append('%d frames of %d x %d' % (cams.shape[0], h, w))
     with open(os.path.join(args.eval_dir, 'cast.json'), 'w') as fjson:
         json.dump(meta, fjson, indent=1)

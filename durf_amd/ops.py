@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import _lib, camera
-from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs, _cast_sigs, _closest_sigs
+from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs, _cast_sigs, _closest_sigs, _shade_sigs
 
 
 
@@ -22,7 +22,7 @@ def _by_prefix(table, prefix):
 # the tables imported above; tests/test_headers_host.py holds the tables to the C compiler).  Every `#define DURF_X <integer>`
 # of include/durf_hip.h and include/durf_<name>.h is ops.X: ENC_DIM, MAX_OBJ, TRAIN_OBJ_FP32, TIMED_STAGES, MESH_BLOCK, PARTS_TILE_K, ...
 # -- all but OVERLAP_MIN_ROWS, launch policy that the library is asked for (__getattr__ below).
-for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs, _cast_sigs, _closest_sigs):
+for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs, _cast_sigs, _closest_sigs, _shade_sigs):
     globals().update(_by_prefix(_table, 'DURF_'))
 del OVERLAP_MIN_ROWS
 
@@ -2717,3 +2717,77 @@ def closest_grid(ws, T, shape, origin, du, dv, dw, max_dist=float('inf'), want_t
         _lib.check(_lib.closest_lib().durf_closest_grid(_stream(), nu, nv, nw, *_lattice_args(origin, du, dv, dw), float(max_dist), int(T), _p(ws),
                                                         ws.numel(), _p(dist), _p(tri)), 'durf_closest_grid')
     return dist, tri
+
+
+# ---------------------------------------------------------------------------
+# a shaded picture of a triangle mesh (include/durf_shade.h, csrc/shade.hip, libdurf_shade.so)
+# ---------------------------------------------------------------------------
+def shade_surface(vertices, triangles, tri, bary, toward=None):
+    """durf_shade_surface: tri int32 [...], bary [..., 3] = (w, u, v), toward [..., 3] or None -> (point [..., 3], normal [..., 3]);
+    zero where the sample is not valid, a zero normal on a flat triangle"""
+    V, T = _cast_mesh(vertices, triangles)
+    n, lead, dev = int(tri.numel()), tuple(tri.shape), tri.device
+    _i32(tri, n, 'tri')
+    assert _f32(bary).numel() == 3 * n and (toward is None or _f32(toward).numel() == 3 * n), (tuple(bary.shape), lead)
+    point, normal = torch.empty(lead + (3,), device=dev), torch.empty(lead + (3,), device=dev)
+    with _Timed('shade_surface'):
+        _lib.check(_lib.shade_lib().durf_shade_surface(_stream(), n, V, T, _z(vertices), _z(triangles), _z(tri), _z(bary), _z(toward), _z(point),
+                                                       _z(normal)), 'durf_shade_surface')
+    return point, normal
+
+
+def shade_occlusion(ws, T, points, normals, dirs, bias, reach, cull=0):
+    """durf_shade_occlusion: points, normals [..., 3], dirs [S,3] on the device against the tree in ws -> (used, blocked) int32 [...]"""
+    n = int(points.numel() // 3)
+    assert _f32(points).numel() == 3 * n == _f32(normals).numel() and points.dim() >= 1 and points.shape[-1] == 3, (tuple(points.shape), tuple(normals.shape))
+    assert _f32(dirs).dim() == 2 and dirs.shape[1] == 3, tuple(dirs.shape)
+    lead, dev = tuple(points.shape[:-1]), points.device
+    used, blocked = torch.empty(lead, dtype=torch.int32, device=dev), torch.empty(lead, dtype=torch.int32, device=dev)
+    with _Timed('shade_occlusion'):
+        _lib.check(_lib.shade_lib().durf_shade_occlusion(_stream(), n, _z(points), _z(normals), int(dirs.shape[0]), _z(dirs), float(bias), float(reach),
+                                                         int(cull), int(T), _p(ws), ws.numel(), _z(used), _z(blocked)), 'durf_shade_occlusion')
+    return used, blocked
+
+
+def shade_compose(tri, normals, used, blocked, light, ambient, background, sun_blocked=None, albedo=None, want_f=True, want_u8=True):
+    """durf_shade_compose: the colour of every sample -> (out_f [..., 3] or None, out_u8 uint8 [..., 3] or None); light and
+    background: three host floats each"""
+    n, lead, dev = int(tri.numel()), tuple(tri.shape), tri.device
+    _i32(tri, n, 'tri'), _i32(used, n, 'used'), _i32(blocked, n, 'blocked')
+    assert _f32(normals).numel() == 3 * n and (albedo is None or _f32(albedo).numel() == 3 * n), tuple(normals.shape)
+    if sun_blocked is not None:
+        _i32(sun_blocked, n, 'sun_blocked')
+    out_f = torch.empty(lead + (3,), device=dev) if want_f else None
+    out_u8 = torch.empty(lead + (3,), dtype=torch.uint8, device=dev) if want_u8 else None
+    with _Timed('shade_compose'):
+        _lib.check(_lib.shade_lib().durf_shade_compose(_stream(), n, _z(tri), _z(normals), _z(used), _z(blocked), _z(sun_blocked), _z(albedo),
+                                                       _host_floats(light, 3, 'light'), float(ambient), _host_floats(background, 3, 'background'),
+                                                       _z(out_f), _z(out_u8)), 'durf_shade_compose')
+    return out_f, out_u8
+
+
+def shade_workspace_bytes(F, h, w):
+    return int(_lib.shade_lib().durf_shade_workspace_bytes(int(F), int(h), int(w)))
+
+
+def shade_cameras(cast_ws, vertices, triangles, cams, h, w, dirs, bias, reach, light, sun, ambient, background, albedo_vertex=None,
+                  tmin=0.0, tmax=float('inf'), cull=0, want_normal=True, want_f=True, want_u8=True, ws=None):
+    """durf_shade_cameras: cams [F,CAM_FLOATS] on the device, all h x w -> dict tri, depth, normal (or None), ao_used, ao_blocked,
+    out_f, out_u8 as [F,h,w(,3)]: the cast, the surface, the two occlusions and the colour in four launches"""
+    V, T = _cast_mesh(vertices, triangles)
+    assert _f32(cams).dim() == 2 and cams.shape[1] == CAM_FLOATS, tuple(cams.shape)
+    assert _f32(dirs).dim() == 2 and dirs.shape[1] == 3, tuple(dirs.shape)
+    assert albedo_vertex is None or _f32(albedo_vertex).numel() == 3 * V, (V,)
+    F, h, w, dev = int(cams.shape[0]), int(h), int(w), cams.device
+    ws = _ws(ws, shade_workspace_bytes(F, h, w), dev)
+    i32 = lambda: torch.empty(F, h, w, dtype=torch.int32, device=dev)
+    r = dict(tri=i32(), depth=torch.empty(F, h, w, device=dev), normal=torch.empty(F, h, w, 3, device=dev) if want_normal else None,
+             ao_used=i32(), ao_blocked=i32(), out_f=torch.empty(F, h, w, 3, device=dev) if want_f else None,
+             out_u8=torch.empty(F, h, w, 3, dtype=torch.uint8, device=dev) if want_u8 else None)
+    with _Timed('shade_cameras'):
+        _lib.check(_lib.shade_lib().durf_shade_cameras(
+            _stream(), F, h, w, _z(cams), float(tmin), float(tmax), int(cull), V, T, _z(vertices), _z(triangles), _p(cast_ws), cast_ws.numel(),
+            int(dirs.shape[0]), _z(dirs), float(bias), float(reach), _host_floats(light, 3, 'light'), int(sun), float(ambient), _z(albedo_vertex),
+            _host_floats(background, 3, 'background'), _p(ws), ws.numel(), _z(r['tri']), _z(r['depth']), _z(r['normal']), _z(r['ao_used']),
+            _z(r['ao_blocked']), _z(r['out_f']), _z(r['out_u8'])), 'durf_shade_cameras')
+    return r

@@ -12,6 +12,9 @@ intrinsics come from --focal, --size and --pp (default: the frame's centre).  Wr
 depth, float32, 0 where no triangle covers), depth_%04d.ppm, ids_%04d.ppm (--ids: the PLY's per-vertex component, the file a
 vertex came from -- the default with several files -- or the triangle id) and OUT2/raster.json (the counts per frame: pairs,
 drawn, invalid, behind, crossing, range, degenerate, culled).  A triangle crossing the near plane is dropped, not clipped.
+--shade [--ao_dirs 64 --ao_reach R --light X Y Z --ambient 0.5 --no_sun] adds shade_%04d.ppm, ao_%04d.ppm and normals_%04d.ppm
+per frame and ao_dirs, ao_reach, bias and light to raster.json: the rasteriser's hits, shaded by any-hit rays through a cast tree
+of the same mesh (durf_amd.shade.primaries; R defaults to 2 % of the merged mesh's bounding diagonal).
 --synthetic renders a sphere's iso-surface (durf_amd.mesh.surface of an analytic density lattice) from an orbit of --frames
 cameras instead: no data, no checkpoint, the command end to end."""
 import argparse
@@ -37,11 +40,18 @@ def build_parser():
     ap.add_argument('--ids', choices=('component', 'part', 'tri'), default=None, help='what ids_%%04d.ppm shows')
     ap.add_argument('--synthetic', action='store_true', help='render a synthetic sphere from an orbit (no data needed)')
     ap.add_argument('--frames', type=int, default=8, help='--synthetic: cameras of the orbit')
+    from . import shade
+    shade.add_arguments(ap)
     return ap
 
 
 def check_args(args):
     """the refusals of the command line, before anything is read -> the message, or None"""
+    if args.shade:
+        from . import shade
+        why = shade.check_arguments(args)
+        if why:
+            return why
     if args.synthetic:
         return None if args.frames >= 1 else '--frames %d' % args.frames
     if not args.ply:
@@ -116,6 +126,17 @@ def main(argv=None):
     meta = dict(meshes=names, vertices=int(m['vertices'].shape[0]), triangles=int(m['triangles'].shape[0]), h=int(h), w=int(w), focal=float(focal),
                 principal_point=[float(pp[0]), float(pp[1])], znear=args.znear, cull=args.cull, ids=ids,
                 frames=[dict(dict(zip(raster.COUNT_FIELDS, (int(x) for x in row))), covered=int(c)) for row, c in zip(r['counts'], covered)])
+    if args.shade:
+        # the rasteriser's primaries, the cast's secondaries: a tree for the any-hit rays, the surface from the rasteriser's tri / bary
+        import torch
+        from . import cast, raygen, shade
+        b = cast.build(m)
+        kw = shade.arguments(args, m['vertices'])
+        for f in range(cams.shape[0]):
+            toward = raygen.camera_rays(cams[f], 0.0, 1.0, device=b['ws'].device).directions.reshape(h, w, 3).contiguous()
+            s = shade.primaries(b, r['tri'][f].contiguous(), r['bary'][f].contiguous(), toward, cull=CULL[args.cull], **kw)
+            shade.write_pictures(args.eval_dir, f, {k: (v[None] if torch.is_tensor(v) else v) for k, v in s.items()}, 0)
+        meta.update(shade.meta(args, s))
     with open(os.path.join(args.eval_dir, 'raster.json'), 'w') as fjson:
         json.dump(meta, fjson, indent=1)
     print('render_mesh: %d frames of %d x %d, %d triangles; written to %s' % (cams.shape[0], h, w, meta['triangles'], args.eval_dir))
