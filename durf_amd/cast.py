@@ -13,17 +13,7 @@ depth), range for the LIDAR's unit directions.  A ray has no near plane: nothing
 mesh.  Meshes of moving boxes: one raster.merge(meshes, poses, ts) and one build per timestep."""
 import numpy as np
 
-
-def _mesh_arrays(m, entry):
-    if not isinstance(m, dict) or m.get('vertices') is None or m.get('triangles') is None:
-        raise ValueError('%s: m is a dict with vertices [V,3] and triangles [T,3]' % entry)
-    vs, ts = tuple(m['vertices'].shape), tuple(m['triangles'].shape)
-    if len(vs) != 2 or vs[1] != 3 or len(ts) != 2 or ts[1] != 3:
-        raise ValueError('%s: vertices of shape %s and triangles of shape %s, expected [V,3] and [T,3]' % (entry, vs, ts))
-    from ._cast_sigs import DURF_CAST_MAX_TRIANGLES
-    if vs[0] >= 2 ** 31 or ts[0] >= DURF_CAST_MAX_TRIANGLES:
-        raise ValueError('%s: %d vertices and %d triangles, the limits are 2^31 - 1 and %d' % (entry, vs[0], ts[0], DURF_CAST_MAX_TRIANGLES - 1))
-    return vs[0], ts[0]
+from . import trimesh
 
 
 def _check_bounds(entry, tmin, tmax, cull):
@@ -39,13 +29,12 @@ def build(m, order=None):
     other per-vertex array of m as it was), V, T, order (the permutation the tree was built over) and ws (the workspace the
     casts read).  Bounds by torch.aminmax, durf_cast_keys, a stable torch.sort, durf_cast_build: no read-back.  order: a
     permutation of the triangles to build over instead (it changes the speed of a cast, never its result)."""
-    V, T = _mesh_arrays(m, 'cast.build')
+    from ._cast_sigs import DURF_CAST_MAX_TRIANGLES
+    V, T = trimesh.arrays(m, 'cast.build', DURF_CAST_MAX_TRIANGLES, 'the limits are 2^31 - 1 and %d' % (DURF_CAST_MAX_TRIANGLES - 1))
     import torch
     from . import ops
-    v = m['vertices']
-    dev = v.device if torch.is_tensor(v) and v.is_cuda else torch.device('cuda', torch.cuda.current_device())
-    up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a) if not torch.is_tensor(a) else a).to(device=dev, dtype=dt).contiguous()
-    vertices, triangles = up(v, torch.float32).reshape(V, 3), up(m['triangles'], torch.int32).reshape(T, 3)
+    dev = trimesh.device_of(m['vertices'])
+    vertices, triangles = trimesh.on_device(m, V, T, dev)
     if order is None:
         if V > 0 and T > 0:
             lo, hi = torch.aminmax(vertices, dim=0)
@@ -54,7 +43,7 @@ def build(m, order=None):
         else:
             order = torch.arange(T, dtype=torch.int32, device=dev)
     else:
-        order = up(order, torch.int32).reshape(-1)
+        order = trimesh.upload(order, torch.int32, dev).reshape(-1)
         if order.numel() != T:
             raise ValueError('cast.build: order has %d entries for %d triangles' % (order.numel(), T))
     b = {k: a for k, a in m.items() if k not in ('vertices', 'triangles')}
@@ -64,9 +53,7 @@ def build(m, order=None):
 
 def _rays_on(b, origins, directions, entry):
     import torch
-    dev = b['ws'].device
-    up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32) if not torch.is_tensor(a) else a).to(device=dev, dtype=torch.float32).contiguous()
-    o, d = up(origins), up(directions)
+    o, d = (trimesh.upload(a, torch.float32, b['ws'].device) for a in (origins, directions))
     if o.dim() < 1 or o.shape[-1] != 3 or tuple(o.shape) != tuple(d.shape):
         raise ValueError('%s: origins of shape %s and directions of shape %s, expected the same [..., 3]' % (entry, tuple(o.shape), tuple(d.shape)))
     return o, d
@@ -113,17 +100,12 @@ def attributes_at(b, tri, bary, attrs, label, out):
     """The per-vertex arrays of build()'s b at (tri, bary), through durf_raster_interp, added to the dict `out`: every key of
     `attrs` that b holds as [...,C] (uint8 colours as [0, 1] floats) and `label` as [...] int32 (-1 where tri < 0).  cameras()
     and closest.attributes share it."""
-    import torch
     from . import ops
     V = b['V']
-    for key in attrs:
-        a = b.get(key)
-        if a is not None:
-            scale = 1.0 / 255.0 if (a.dtype == np.uint8 or a.dtype == torch.uint8) else 1.0
-            a = torch.as_tensor(a).to(device=tri.device, dtype=torch.float32).reshape(V, -1)
-            out[key] = ops.raster_interp(b['triangles'], tri, bary, V, attr_f=(a * scale).contiguous())[0]
-    if label is not None and b.get(label) is not None:
-        lab = torch.as_tensor(b[label]).to(device=tri.device, dtype=torch.int32).reshape(V).contiguous()
+    fattrs, lab = trimesh.vertex_attributes(b, attrs, label, V, tri.device)
+    for key, a in fattrs.items():
+        out[key] = ops.raster_interp(b['triangles'], tri, bary, V, attr_f=a)[0]
+    if lab is not None:
         out[label] = ops.raster_interp(b['triangles'], tri, None, V, attr_i=lab, fill=-1)[1]
     return out
 
@@ -139,8 +121,7 @@ def cameras(b, cams, tmin=0.0, tmax=float('inf'), attrs=('rgb', 'normals'), labe
     if not np.isfinite(cams).all():
         raise ValueError('%s: a camera row that is not finite' % entry)
     _check_bounds(entry, tmin, tmax, cull)
-    if isinstance(attrs, str) or not all(isinstance(a, str) for a in attrs):
-        raise ValueError('%s: attrs = %r, expected a tuple of keys of the mesh' % (entry, attrs))
+    trimesh.check_attrs(attrs, entry)
     if cams.shape[0] * h * w >= 2 ** 31:
         raise ValueError('%s: %d frames of %d x %d: frames x pixels must stay below 2^31' % (entry, cams.shape[0], h, w))
     import torch

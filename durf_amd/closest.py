@@ -12,7 +12,7 @@ max_dist is looked for: such a point reports tri = -1 and dist = max_dist (geome
 takes the two arrays as they are); a point with a NaN or infinite coordinate reports -2 and NaN."""
 import numpy as np
 
-from . import lattice
+from . import lattice, trimesh
 
 SORT_QUERIES = True                 # points()'s default: queries in the order of a Morton key of their own
 
@@ -55,7 +55,7 @@ def points(b, p, max_dist=float('inf'), sort_queries=None):
     import torch
     from . import ops
     dev = b['ws'].device
-    p = torch.as_tensor(np.ascontiguousarray(p, dtype=np.float32) if not torch.is_tensor(p) else p).to(device=dev, dtype=torch.float32).contiguous()
+    p = trimesh.upload(p, torch.float32, dev)
     if p.dim() < 1 or p.shape[-1] != 3:
         raise ValueError('%s: points of shape %s, expected [..., 3]' % (entry, tuple(p.shape)))
     if p.numel() // 3 >= 2 ** 31:
@@ -79,8 +79,7 @@ def attributes(b, r, attrs=('rgb', 'normals'), label='owner'):
     the triangle's first vertex, -1 where nothing was found)."""
     entry = 'closest.attributes'
     _tree(b, entry)
-    if isinstance(attrs, str) or not all(isinstance(a, str) for a in attrs):
-        raise ValueError('%s: attrs = %r, expected a tuple of keys of the mesh' % (entry, attrs))
+    trimesh.check_attrs(attrs, entry)
     if not isinstance(r, dict) or r.get('tri') is None or r.get('bary') is None:
         raise ValueError('%s: r is what closest.points returns (a dict with tri and bary)' % entry)
     from . import cast

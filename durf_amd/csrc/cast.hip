@@ -14,7 +14,7 @@ k_cast_keys(int V, int T, const float* __restrict__ vertices, const int32_t* __r
     const int i = blockIdx.x * CB + threadIdx.x;
     if (i >= T) return;
     float P[9];
-    if (!cast_fetch(i, V, T, vertices, triangles, P)) {
+    if (!tri_fetch(i, V, T, vertices, triangles, P)) {
         keys[i] = LLONG_MAX;
         return;
     }
@@ -43,7 +43,7 @@ k_cast_leaves(int V, int T, int n0, const float* __restrict__ vertices, const in
         const size_t s = (size_t)l * CLEAF + j;
         float P[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         int id = s < (size_t)T ? order[s] : -1;
-        if (cast_fetch(id, V, T, vertices, triangles, P)) {
+        if (tri_fetch(id, V, T, vertices, triangles, P)) {
             cast_union(B, cast_tri_box(P, P + 3, P + 6));
         } else {
             id = -1;
@@ -139,14 +139,6 @@ k_cast_cameras(const CastTree R, int F, int h, int w, const float* __restrict__ 
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------------
 namespace {
-
-int check_cast_mesh(const char* who, int V, int T, const float* vertices, const int32_t* triangles) {
-    if (!(V >= 0)) { durf_set_error("%s: requirement failed: V >= 0, V = %d", who, V); return -1; }
-    if (check_cast_t(who, T) != 0) return -1;
-    if (!(vertices || V == 0)) { durf_set_error("%s: requirement failed: vertices for V = %d", who, V); return -1; }
-    if (!(triangles || T == 0)) { durf_set_error("%s: requirement failed: triangles for T = %d", who, T); return -1; }
-    return 0;
-}
 
 int check_cast_bounds(const char* who, bool scalar_tmin, bool scalar_tmax, float tmin, float tmax, int cull) {
     if (!(cull >= 0 && cull <= 2)) { durf_set_error("%s: requirement failed: cull in 0 .. 2, cull = %d", who, cull); return -1; }

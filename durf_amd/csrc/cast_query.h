@@ -1,31 +1,10 @@
 // The ray query of the implicit box tree (include/durf_cast.h), defined once for everything that sends rays through it (cast.hip:
 // the nearest hit and any hit; shade.hip: the secondary rays of a shaded picture): the ray, the header's box rule and triangle
-// rule, the two queries of cast_tree.h's one walk, and the outputs of a hit.  Internal.
+// rule, the two queries of cast_tree.h's one walk, the outputs of a hit, and the launchers' refusal of a mesh under the tree's
+// limit.  The mesh itself -- the readable triangle and its fetch -- is triangles.h's.  Internal.
 #pragma once
 #include "cast_tree.h"
-#include "camera.h"
-
-// a valid triangle's vertices; false for an id outside 0 .. T-1, an index outside 0 .. V-1 or a coordinate that is not finite
-__device__ __forceinline__ bool cast_fetch(int id, int V, int T, const float* __restrict__ vertices, const int32_t* __restrict__ triangles,
-                                           float* P /* [9] */) {
-    if (id < 0 || id >= T) return false;
-    bool ok = true;
-    int v[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        v[c] = triangles[(size_t)id * 3 + c];
-        ok = ok && v[c] >= 0 && v[c] < V;
-    }
-    if (!ok) return false;
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            P[3 * c + a] = vertices[(size_t)v[c] * 3 + a];
-            ok = ok && cam_finite(P[3 * c + a]);
-        }
-    return ok;
-}
+#include "triangles.h"
 
 struct CastRay {
     float o[3], d[3], inv[3];
@@ -71,20 +50,22 @@ __device__ __forceinline__ bool cast_triangle(const CastRay& r, int cull, const 
     float bn, bf;
     if (!cast_box_rule(r, cast_tri_box(P, P + 3, P + 6), bn, bf)) return false;
     const float* d = r.d;
-    const float e1[3] = {P[3] - P[0], P[4] - P[1], P[5] - P[2]}, e2[3] = {P[6] - P[0], P[7] - P[1], P[8] - P[2]};
-    const float p[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
-    const float det = (e1[0] * p[0] + e1[1] * p[1]) + e1[2] * p[2];
+    float e1[3], e2[3], p[3], s[3], q[3];
+    vec3_sub(P + 3, P, e1);
+    vec3_sub(P + 6, P, e2);
+    vec3_cross(d, e2, p);
+    const float det = vec3_dot(e1, p);
     if (!(det != 0.0f)) return false;                                        // (a NaN det is refused by inv below)
     const float inv = 1.0f / det;
     if (!cam_finite(inv)) return false;
     if ((cull == 1 && det < 0.0f) || (cull == 2 && det > 0.0f)) return false;
-    const float s[3] = {r.o[0] - P[0], r.o[1] - P[1], r.o[2] - P[2]};
-    u = ((s[0] * p[0] + s[1] * p[1]) + s[2] * p[2]) * inv;
-    const float q[3] = {s[1] * e1[2] - s[2] * e1[1], s[2] * e1[0] - s[0] * e1[2], s[0] * e1[1] - s[1] * e1[0]};
-    v = ((d[0] * q[0] + d[1] * q[1]) + d[2] * q[2]) * inv;
+    vec3_sub(r.o, P, s);
+    u = vec3_dot(s, p) * inv;
+    vec3_cross(s, e1, q);
+    v = vec3_dot(d, q) * inv;
     w = (1.0f - u) - v;
     if (!(u >= 0.0f && v >= 0.0f && w >= 0.0f)) return false;
-    const float t0 = ((e2[0] * q[0] + e2[1] * q[1]) + e2[2] * q[2]) * inv;
+    const float t0 = vec3_dot(e2, q) * inv;
     if (t0 != t0) return false;
     t = fminf(fmaxf(t0, bn), bf) + 0.0f;
     return r.tmin <= t && t <= r.tmax;
@@ -132,4 +113,9 @@ __device__ __forceinline__ void cast_write(const CastHit& hit, bool usable, size
         bary[i * 3 + 1] = !usable ? nan : found ? hit.u : 0.0f;
         bary[i * 3 + 2] = !usable ? nan : found ? hit.v : 0.0f;
     }
+}
+
+// the mesh of an entry that also takes the tree: triangles.h's refusals around the tree's own limit on T
+inline int check_cast_mesh(const char* who, int V, int T, const float* vertices, const int32_t* triangles) {
+    return check_mesh(who, V, T, check_cast_t(who, T), vertices, triangles);
 }

@@ -5,21 +5,19 @@
 // nothing else: no atomics, nothing synchronises or copies to the host, no workgroup waits for another.
 #include <cmath>
 #include "cast_tree.h"
-#include "camera.h"
+#include "triangles.h"
 #include "lattice.h"
 #include "../../include/durf_closest.h"
 
 static_assert(DURF_CLOSEST_BLOCK == CB && DURF_CLOSEST_STACK == CSTACK, "the walk's workgroup and its one stack entry per level");
 static_assert(DURF_CLOSEST_BRICK * DURF_CLOSEST_BRICK * DURF_CLOSEST_BRICK == 64 && CB % 64 == 0, "a brick per wave");
 
-__device__ __forceinline__ float closest_dot(const float* x, const float* y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
-
 // the box bound: +inf for the empty box by the formula itself
 __device__ __forceinline__ float closest_bound(const float* P, const CastBox& B) {
     float e[3];
 #pragma unroll
     for (int a = 0; a < 3; a++) e[a] = fmaxf(fmaxf(B.lo[a] - P[a], P[a] - B.hi[a]), 0.0f);
-    return closest_dot(e, e);
+    return vec3_dot(e, e);
 }
 
 struct ClosestBest {
@@ -36,7 +34,7 @@ __device__ __forceinline__ void closest_candidate(const float* P, const float* A
         c[k] = (A[k] + u * e1[k]) + v * e2[k];
         q[k] = P[k] - c[k];
     }
-    const float d2 = closest_dot(q, q);
+    const float d2 = vec3_dot(q, q);
     if (d2 < best.d2) best = ClosestBest{best.tri, d2, w, u, v, {c[0], c[1], c[2]}};
 }
 
@@ -54,8 +52,8 @@ __device__ __forceinline__ ClosestBest closest_triangle(const float* P, const fl
         f[k] = C[k] - B[k];
         r[k] = P[k] - B[k];
     }
-    const float a = closest_dot(e1, e1), b = closest_dot(e1, e2), c = closest_dot(e2, e2), d = closest_dot(e1, s), e = closest_dot(e2, s);
-    const float l = closest_dot(f, f), g = closest_dot(f, r);
+    const float a = vec3_dot(e1, e1), b = vec3_dot(e1, e2), c = vec3_dot(e2, e2), d = vec3_dot(e1, s), e = vec3_dot(e2, s);
+    const float l = vec3_dot(f, f), g = vec3_dot(f, r);
     ClosestBest best{-1, __builtin_inff(), 1.0f, 0.0f, 0.0f, {A[0], A[1], A[2]}};
     const float det = a * c - b * b;
     if (det > 0.0f) {

@@ -65,6 +65,13 @@ __device__ __forceinline__ float nan_to_num(float x) {
     if (x == -__builtin_inff()) return -3.4028234663852886e+38f;
     return x;
 }
+// The 8-bit colour of every picture the libraries write (k_frame_pack, the vis kernels, k_shade_compose):
+// rintf(clamp(x, 0, 1) * 255), NaN -> 0 (== torch.round(x.clamp(0, 1) * 255): one multiply, then the round-half-even of rintf;
+// nothing to contract).  flow.hip's colour wheel has no clamp and overlay.hip blends in 0 .. 255: other rules, on purpose.
+__device__ __forceinline__ unsigned rgb8(float x) {
+    const float c = (x != x) ? 0.0f : fminf(fmaxf(x, 0.0f), 1.0f);
+    return (unsigned)rintf(c * 255.0f);
+}
 // math.safe_sin (internal/math.py:35-46): sin(|x| < 100*pi ? x : x mod 100*pi), the mod
 // being jnp.remainder (exact fmod, then shifted to the sign of the divisor).
 __device__ __forceinline__ float safe_sin(float x) {

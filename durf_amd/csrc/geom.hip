@@ -6,6 +6,7 @@
 #include <cmath>
 #include "workspace.h"
 #include "scan.h"
+#include "triangles.h"
 #include "../../include/durf_geom.h"
 
 #define GEOM_B DURF_GEOM_BLOCK
@@ -162,15 +163,14 @@ k_geom_areas(int V, const float* __restrict__ vert, int T, const int32_t* __rest
     const int t = threadIdx.x, g = blockIdx.x * GEOM_B + t;
     double area = 0.0;
     if (g < T) {
-        const int ia = tri[(size_t)g * 3], ib = tri[(size_t)g * 3 + 1], ic = tri[(size_t)g * 3 + 2];
-        if (ia >= 0 && ia < V && ib >= 0 && ib < V && ic >= 0 && ic < V) {
-            const float* A = vert + (size_t)ia * 3;
-            const float* B = vert + (size_t)ib * 3;
-            const float* Cc = vert + (size_t)ic * 3;
-            const float e1x = B[0] - A[0], e1y = B[1] - A[1], e1z = B[2] - A[2];
-            const float e2x = Cc[0] - A[0], e2y = Cc[1] - A[1], e2z = Cc[2] - A[2];
-            const float cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
-            const float a = 0.5f * sqrtf((cx * cx + cy * cy) + cz * cz);
+        int v[3];
+        if (tri_indices<false>(g, V, T, tri, v)) {                          // (not tri_fetch: what is not finite fails the area test)
+            const float* A = vert + (size_t)v[0] * 3;
+            float e1[3], e2[3], c[3];
+            vec3_sub(vert + (size_t)v[1] * 3, A, e1);
+            vec3_sub(vert + (size_t)v[2] * 3, A, e2);
+            vec3_cross(e1, e2, c);
+            const float a = 0.5f * sqrtf(vec3_dot(c, c));
             if (fabsf(a) <= 3.0e38f) area = (double)a;                      // (false for NaN and the infinities)
         }
         cum[g] = area;
@@ -218,16 +218,17 @@ k_geom_sample(int V, const float* __restrict__ vert, int T, const int32_t* __res
     v = v - floor(v);
     if (u + v > 1.0) { u = 1.0 - u; v = 1.0 - v; }
     const float uf = (float)u, vf = (float)v;
-    const int ia = tri[(size_t)g * 3], ib = tri[(size_t)g * 3 + 1], ic = tri[(size_t)g * 3 + 2];
+    int iv[3];
+    const bool readable = tri_indices<false>(g, V, T, tri, iv);             // (0 <= g < T: tot > 0 means T > 0)
     tri_out[s] = g;
-    if (ia < 0 || ia >= V || ib < 0 || ib >= V || ic < 0 || ic >= V) {      // (an area-0 triangle is never chosen: a guard)
+    if (!readable) {                                                        // (an area-0 triangle is never chosen: a guard)
         P[0] = P[1] = P[2] = nanf("");
         return;
     }
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        const float a = vert[(size_t)ia * 3 + c], b = vert[(size_t)ib * 3 + c], cc = vert[(size_t)ic * 3 + c];
-        P[c] = a + (uf * (b - a) + vf * (cc - a));
+        const float a = vert[(size_t)iv[0] * 3 + c], b = vert[(size_t)iv[1] * 3 + c], cc = vert[(size_t)iv[2] * 3 + c];
+        P[c] = a + (uf * (b - a) + vf * (cc - a));                          // (its own order: a + (u e1 + v e2), not tri_interp's)
     }
 }
 
@@ -346,6 +347,7 @@ int durf_geom_sample_mesh(void* stream, int n_vertices, const float* vertices, i
                           void* workspace, size_t workspace_bytes, float* points, int32_t* tri, double* total_area) {
     DURF_REQUIREF(n >= 0 && n_vertices >= 0 && n_triangles >= 0, "n, n_vertices and n_triangles >= 0, n = %d, n_vertices = %d, n_triangles = %d",
                  n, n_vertices, n_triangles);
+    // (not triangles.h's check_mesh: this entry's arguments are called n_vertices and n_triangles, and its messages say so)
     DURF_REQUIREF(n_vertices == 0 || vertices, "vertices for n_vertices = %d", n_vertices);
     DURF_REQUIREF(n_triangles == 0 || triangles, "triangles for n_triangles = %d", n_triangles);
     DURF_REQUIREF(n == 0 || (points && tri), "points and tri for n = %d", n);

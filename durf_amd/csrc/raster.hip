@@ -6,7 +6,7 @@
 #include <climits>
 #include "workspace.h"
 #include "scan.h"
-#include "camera.h"
+#include "triangles.h"
 #include "../../include/durf_raster.h"
 
 #define RB DURF_RASTER_BLOCK
@@ -56,13 +56,8 @@ k_raster_setup(const RasterDims D, const float* __restrict__ cams, int V, const 
         const int f = i / (unsigned)D.T, t = i - (unsigned)f * (unsigned)D.T;
         const float* cam = cams + (size_t)f * DURF_CAM_FLOATS;
         float x[3], y[3], z[3];
-        bool valid = true;
         int v[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            v[c] = triangles[(size_t)t * 3 + c];
-            valid = valid && v[c] >= 0 && v[c] < V;
-        }
+        bool valid = tri_indices<false>(t, V, D.T, triangles, v);            // (t < T by construction; finiteness is tested in camera space below)
         if (valid) {
 #pragma unroll
             for (int c = 0; c < 3; c++) {
@@ -322,14 +317,7 @@ k_raster_interp(int n_pixels, int V, int T, const int32_t* __restrict__ triangle
     if (p >= n_pixels) return;
     const int t = tri[p];
     int v[3] = {-1, -1, -1};
-    bool hit = t >= 0 && t < T;
-    if (hit) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            v[c] = triangles[(size_t)t * 3 + c];
-            hit = hit && v[c] >= 0 && v[c] < V;
-        }
-    }
+    const bool hit = tri_indices(t, V, T, triangles, v);
     if (out_i) out_i[p] = hit ? attr_i[v[0]] : fill;
     if (out_f) {
         float q[3] = {0.0f, 0.0f, 0.0f};
@@ -337,9 +325,7 @@ k_raster_interp(int n_pixels, int V, int T, const int32_t* __restrict__ triangle
 #pragma unroll
             for (int c = 0; c < 3; c++) q[c] = bary[(size_t)p * 3 + c];
         }
-        for (int c = 0; c < C; c++)
-            out_f[(size_t)p * C + c] = hit ? (q[0] * attr_f[(size_t)v[0] * C + c] + q[1] * attr_f[(size_t)v[1] * C + c]) +
-                                             q[2] * attr_f[(size_t)v[2] * C + c] : 0.0f;
+        for (int c = 0; c < C; c++) out_f[(size_t)p * C + c] = hit ? tri_interp(q, v, attr_f, C, c) : 0.0f;
     }
 }
 
@@ -408,14 +394,16 @@ int check_raster_ws(const char* who, const void* workspace, size_t workspace_byt
     return durf::check_workspace(who, workspace_bytes, ws->total, "durf_raster_workspace_bytes(%d, %d, %d, %d)", D.F, D.T, D.h, D.w);
 }
 
-int check_setup_args(const char* who, int F, const float* cams, int V, int T, const float* vertices, const int32_t* triangles,
-                     float znear, int cull, const int32_t* counts) {
-    if (!(V >= 0)) { durf_set_error("%s: requirement failed: V >= 0, V = %d", who, V); return -1; }
+int check_setup_view(const char* who, int F, const float* cams, float znear, int cull) {
     if (!(znear >= FLT_MIN)) { durf_set_error("%s: requirement failed: znear > 0 (a normal float), znear = %g", who, (double)znear); return -1; }
     if (!(cull >= 0 && cull <= 2)) { durf_set_error("%s: requirement failed: cull in 0 .. 2, cull = %d", who, cull); return -1; }
     if (!(cams || F == 0)) { durf_set_error("%s: requirement failed: cams_dev for F = %d", who, F); return -1; }
-    if (!(vertices || V == 0)) { durf_set_error("%s: requirement failed: vertices for V = %d", who, V); return -1; }
-    if (!(triangles || T == 0)) { durf_set_error("%s: requirement failed: triangles for T = %d", who, T); return -1; }
+    return 0;
+}
+
+int check_setup_args(const char* who, int F, const float* cams, int V, int T, const float* vertices, const int32_t* triangles,
+                     float znear, int cull, const int32_t* counts) {
+    if (check_mesh(who, V, T, check_setup_view(who, F, cams, znear, cull), vertices, triangles) != 0) return -1;
     if (!counts) { durf_set_error("%s: requirement failed: counts", who); return -1; }
     return 0;
 }
@@ -438,8 +426,7 @@ int check_interp_args(const char* who, int n_pixels, int V, int T, const int32_t
     if (attr_f && !(C >= 1)) { durf_set_error("%s: requirement failed: C >= 1, C = %d", who, C); return -1; }
     if (attr_i && !out_i) { durf_set_error("%s: requirement failed: out_i with attr_i", who); return -1; }
     if (!(tri || n_pixels == 0)) { durf_set_error("%s: requirement failed: tri for n_pixels = %d", who, n_pixels); return -1; }
-    if (!(triangles || T == 0)) { durf_set_error("%s: requirement failed: triangles for T = %d", who, T); return -1; }
-    return 0;
+    return check_mesh_triangles(who, T, triangles);
 }
 
 int launch_setup(hipStream_t s, const RasterDims& D, const RasterWs& w, const float* cams, int V, const float* vertices,

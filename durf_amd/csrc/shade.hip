@@ -9,8 +9,6 @@
 
 static_assert(DURF_SHADE_MAX_DIRS >= 1, "at least one direction");
 
-__device__ __forceinline__ float shade_dot(const float* x, const float* y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
-
 // the surface rule of a sample: point and normal, zero where the sample is not valid; toward [3] is read when `facing`
 __device__ __forceinline__ void shade_surface_rule(int t, float u, float v, int V, int T, const float* __restrict__ vertices,
                                                    const int32_t* __restrict__ triangles, bool facing, const float* toward, float* point,
@@ -18,16 +16,18 @@ __device__ __forceinline__ void shade_surface_rule(int t, float u, float v, int 
 #pragma unroll
     for (int a = 0; a < 3; a++) point[a] = normal[a] = 0.0f;
     float P[9];
-    if (!cast_fetch(t, V, T, vertices, triangles, P)) return;
-    const float e1[3] = {P[3] - P[0], P[4] - P[1], P[5] - P[2]}, e2[3] = {P[6] - P[0], P[7] - P[1], P[8] - P[2]};
+    if (!tri_fetch(t, V, T, vertices, triangles, P)) return;
+    float e1[3], e2[3], N[3];
+    vec3_sub(P + 3, P, e1);
+    vec3_sub(P + 6, P, e2);
 #pragma unroll
     for (int a = 0; a < 3; a++) point[a] = (P[a] + u * e1[a]) + v * e2[a];
-    const float N[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-    const float len2 = shade_dot(N, N);
+    vec3_cross(e1, e2, N);
+    const float len2 = vec3_dot(N, N);
     if (!(len2 > 0.0f) || !cam_finite(len2)) return;                         // FLAT
     const float inv = 1.0f / sqrtf(len2);
     float n[3] = {N[0] * inv, N[1] * inv, N[2] * inv};
-    const bool flip = facing && shade_dot(n, toward) > 0.0f;
+    const bool flip = facing && vec3_dot(n, toward) > 0.0f;
 #pragma unroll
     for (int a = 0; a < 3; a++) normal[a] = flip ? -n[a] : n[a];
 }
@@ -151,7 +151,7 @@ k_shade_occlusion(const CastTree R, const ShadeTiles G, unsigned long long n, co
         for (int s = 0; s < S; s++) {                                        // (S is read before the loop: at most DURF_SHADE_MAX_DIRS)
             const float* __restrict__ ds = dirs + (size_t)s * 3;             // (not read when dirs is null)
             const float d[3] = {dirs ? ds[0] : one.v[0], dirs ? ds[1] : one.v[1], dirs ? ds[2] : one.v[2]};
-            if (!(shade_dot(nr, d) > 0.0f)) continue;
+            if (!(vec3_dot(nr, d) > 0.0f)) continue;
             n_used++;
 #pragma unroll
             for (int a = 0; a < 3; a++) r.d[a] = d[a];
@@ -165,15 +165,9 @@ k_shade_occlusion(const CastTree R, const ShadeTiles G, unsigned long long n, co
 }
 
 // ---- compose ------------------------------------------------------------------------------------------------------------------------
-// k_frame_pack's rule (csrc/trajectory.hip): rintf(clamp(x, 0, 1) * 255), NaN -> 0
-__device__ __forceinline__ unsigned shade_u8(float x) {
-    const float c = (x != x) ? 0.0f : fminf(fmaxf(x, 0.0f), 1.0f);
-    return (unsigned)rintf(c * 255.0f);
-}
-
 struct ShadeLook { float light[3], background[3], ambient; };
 
-// the albedo of durf_shade_cameras: durf_raster_interp's rule on a per-vertex colour (attr null: none)
+// the albedo of durf_shade_cameras: tri_interp on a per-vertex colour, as durf_raster_interp does it (attr null: none)
 struct ShadeGather {
     const float* attr;                 // [V,3]
     const int32_t* triangles;
@@ -193,7 +187,7 @@ k_shade_compose(int n, const int32_t* __restrict__ tri, const float* __restrict_
         const int nu = used[i], nb = blocked[i];
         const float ao = nu > 0 ? (float)(nu - nb) / (float)nu : 1.0f;
         const float nr[3] = {normals[(size_t)i * 3], normals[(size_t)i * 3 + 1], normals[(size_t)i * 3 + 2]};
-        const float lam = fmaxf(shade_dot(nr, L.light), 0.0f);
+        const float lam = fmaxf(vec3_dot(nr, L.light), 0.0f);
         const float sun = (sun_blocked && sun_blocked[i] > 0) ? 0.0f : 1.0f;
         const float shade = L.ambient * ao + (1.0f - L.ambient) * (lam * sun);
         c[0] = c[1] = c[2] = shade;
@@ -202,14 +196,7 @@ k_shade_compose(int n, const int32_t* __restrict__ tri, const float* __restrict_
             for (int k = 0; k < 3; k++) c[k] = albedo[(size_t)i * 3 + k] * shade;
         } else if (G.attr) {
             int v[3] = {-1, -1, -1};
-            bool hit = t < G.T;
-            if (hit) {
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    v[k] = G.triangles[(size_t)t * 3 + k];
-                    hit = hit && v[k] >= 0 && v[k] < G.V;
-                }
-            }
+            const bool hit = tri_indices(t, G.V, G.T, G.triangles, v);
             float q[3] = {0.0f, 0.0f, 0.0f};
             if (hit) {
 #pragma unroll
@@ -217,28 +204,19 @@ k_shade_compose(int n, const int32_t* __restrict__ tri, const float* __restrict_
             }
 #pragma unroll
             for (int k = 0; k < 3; k++) {
-                const float a = hit ? (q[0] * G.attr[(size_t)v[0] * 3 + k] + q[1] * G.attr[(size_t)v[1] * 3 + k]) + q[2] * G.attr[(size_t)v[2] * 3 + k] : 0.0f;
-                c[k] = a * shade;
+                c[k] = (hit ? tri_interp(q, v, G.attr, 3, k) : 0.0f) * shade;
             }
         }
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         if (out_f) out_f[(size_t)i * 3 + k] = c[k];
-        if (out_u8) out_u8[(size_t)i * 3 + k] = (uint8_t)shade_u8(c[k]);
+        if (out_u8) out_u8[(size_t)i * 3 + k] = (uint8_t)rgb8(c[k]);
     }
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------------
 namespace {
-
-int check_shade_mesh(const char* who, int V, int T, const float* vertices, const int32_t* triangles) {
-    if (!(V >= 0)) { durf_set_error("%s: requirement failed: V >= 0, V = %d", who, V); return -1; }
-    if (check_cast_t(who, T) != 0) return -1;
-    if (!(vertices || V == 0)) { durf_set_error("%s: requirement failed: vertices for V = %d", who, V); return -1; }
-    if (!(triangles || T == 0)) { durf_set_error("%s: requirement failed: triangles for T = %d", who, T); return -1; }
-    return 0;
-}
 
 // S, bias, reach, cull, T and the cast workspace, in this order
 int check_shade_rays(const char* who, int S, const float* dirs, float bias, float reach, int cull, int T, const void* workspace,
@@ -313,7 +291,7 @@ extern "C" {
 int durf_shade_surface(void* stream, int n, int V, int T, const float* vertices, const int32_t* triangles, const int32_t* tri,
                        const float* bary, const float* toward, float* point, float* normal) {
     if (!(n >= 0)) { durf_set_error("%s: requirement failed: n >= 0, n = %d", __func__, n); return -1; }
-    if (check_shade_mesh(__func__, V, T, vertices, triangles) != 0) return -1;
+    if (check_cast_mesh(__func__, V, T, vertices, triangles) != 0) return -1;
     if (!((tri && bary) || n == 0)) { durf_set_error("%s: requirement failed: tri and bary for n = %d", __func__, n); return -1; }
     if (!((point && normal) || n == 0)) { durf_set_error("%s: requirement failed: point and normal for n = %d", __func__, n); return -1; }
     if (n == 0) return 0;
@@ -370,7 +348,7 @@ int durf_shade_cameras(void* stream, int F, int h, int w, const float* cams_dev,
         durf_set_error("%s: requirement failed: F h w < 2^31 pixels, F = %d, h = %d, w = %d", __func__, F, h, w);
         return -1;
     }
-    if (check_shade_mesh(__func__, V, T, vertices, triangles) != 0) return -1;
+    if (check_cast_mesh(__func__, V, T, vertices, triangles) != 0) return -1;
     if (!(tmin >= 0.0f)) { durf_set_error("%s: requirement failed: tmin >= 0, tmin = %g", __func__, (double)tmin); return -1; }
     if (tmax != tmax) { durf_set_error("%s: requirement failed: tmax is a number, tmax = %g", __func__, (double)tmax); return -1; }
     if (!(sun == 0 || sun == 1)) { durf_set_error("%s: requirement failed: sun in 0 .. 1, sun = %d", __func__, sun); return -1; }

@@ -45,35 +45,28 @@ k_pose_interp(int K6, TimeTable times, int f0, const float* __restrict__ box_cen
     out[e] = a + w * ((e % 6) < 3 ? d : wrap_pi(d));
 }
 
-// rgb8 = (uint8) rintf(clamp(rgb, 0, 1) * 255), NaN -> 0 (== torch.round(x.clamp(0, 1) * 255): one multiply, then the
-// round-half-even of rintf; nothing to contract)
-__device__ __forceinline__ unsigned to_u8(float x) {
-    const float c = (x != x) ? 0.0f : fminf(fmaxf(x, 0.0f), 1.0f);
-    return (unsigned)rintf(c * 255.0f);
-}
-
 struct U32x3 { unsigned a, b, c; };
 
-// the chunk epilogue of an 8-bit output: every lane packs 4 whole pixels -- three 16-byte loads, one 12-byte store -- when
-// both pointers allow it (wave-uniform), and byte by byte otherwise or on the last partial group
+// the chunk epilogue of an 8-bit output (durf_common.h's rgb8 per value): every lane packs 4 whole pixels -- three 16-byte loads,
+// one 12-byte store -- when both pointers allow it (wave-uniform), and byte by byte otherwise or on the last partial group
 __global__ void __launch_bounds__(256)
-k_frame_pack(int count, const float* __restrict__ rgb, uint8_t* __restrict__ rgb8) {
+k_frame_pack(int count, const float* __restrict__ rgb, uint8_t* __restrict__ out8) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     const int p0 = g * 4;
     if (p0 >= count) return;
-    const bool aligned = (((size_t)rgb & 15) == 0) && (((size_t)rgb8 & 3) == 0);
+    const bool aligned = (((size_t)rgb & 15) == 0) && (((size_t)out8 & 3) == 0);
     if (aligned && p0 + 4 <= count) {
         const f32x4* src = (const f32x4*)(rgb + (size_t)p0 * 3);
         const f32x4 v0 = src[0], v1 = src[1], v2 = src[2];
         U32x3 o;
-        o.a = to_u8(v0[0]) | (to_u8(v0[1]) << 8) | (to_u8(v0[2]) << 16) | (to_u8(v0[3]) << 24);
-        o.b = to_u8(v1[0]) | (to_u8(v1[1]) << 8) | (to_u8(v1[2]) << 16) | (to_u8(v1[3]) << 24);
-        o.c = to_u8(v2[0]) | (to_u8(v2[1]) << 8) | (to_u8(v2[2]) << 16) | (to_u8(v2[3]) << 24);
-        *(U32x3*)(rgb8 + (size_t)p0 * 3) = o;
+        o.a = rgb8(v0[0]) | (rgb8(v0[1]) << 8) | (rgb8(v0[2]) << 16) | (rgb8(v0[3]) << 24);
+        o.b = rgb8(v1[0]) | (rgb8(v1[1]) << 8) | (rgb8(v1[2]) << 16) | (rgb8(v1[3]) << 24);
+        o.c = rgb8(v2[0]) | (rgb8(v2[1]) << 8) | (rgb8(v2[2]) << 16) | (rgb8(v2[3]) << 24);
+        *(U32x3*)(out8 + (size_t)p0 * 3) = o;
         return;
     }
     const int p1 = p0 + 4 < count ? p0 + 4 : count;
-    for (int j = p0 * 3; j < p1 * 3; j++) rgb8[j] = (uint8_t)to_u8(rgb[j]);
+    for (int j = p0 * 3; j < p1 * 3; j++) out8[j] = (uint8_t)rgb8(rgb[j]);
 }
 
 namespace durf {

@@ -153,17 +153,12 @@ k_vis_stats_final(int F, int G, const double* __restrict__ part1, const double* 
 }
 
 // ---- four pixels per lane ------------------------------------------------------------------------------------------------
-// k_frame_pack's rule (csrc/trajectory.hip): rintf(clamp(x, 0, 1) * 255), NaN -> 0
-__device__ __forceinline__ unsigned vis_u8(float x) {
-    const float c = (x != x) ? 0.0f : fminf(fmaxf(x, 0.0f), 1.0f);
-    return (unsigned)rintf(c * 255.0f);
-}
-
 struct VisU32x3 { unsigned a, b, c; };
 
-// c[12] = the colours of pixels [p0, p0 + cnt), cnt <= 4: 16-byte float stores / one 12-byte store of the bytes when the
-// group is whole and the pointers are aligned (wave-uniform but for the last group), element by element otherwise
-__device__ __forceinline__ void store_pixels(size_t p0, int cnt, const float* c, float* __restrict__ rgb, uint8_t* __restrict__ rgb8) {
+// c[12] = the colours of pixels [p0, p0 + cnt), cnt <= 4: 16-byte float stores / one 12-byte store of the bytes (durf_common.h's
+// rgb8 per value) when the group is whole and the pointers are aligned (wave-uniform but for the last group), element by element
+// otherwise
+__device__ __forceinline__ void store_pixels(size_t p0, int cnt, const float* c, float* __restrict__ rgb, uint8_t* __restrict__ out8) {
     if (rgb) {
         if (cnt == 4 && (((size_t)rgb & 15) == 0)) {
             f32x4* dst = (f32x4*)(rgb + p0 * 3);
@@ -174,15 +169,15 @@ __device__ __forceinline__ void store_pixels(size_t p0, int cnt, const float* c,
             for (int j = 0; j < cnt * 3; j++) rgb[p0 * 3 + j] = c[j];
         }
     }
-    if (rgb8) {
-        if (cnt == 4 && (((size_t)rgb8 & 3) == 0)) {
+    if (out8) {
+        if (cnt == 4 && (((size_t)out8 & 3) == 0)) {
             VisU32x3 o;
-            o.a = vis_u8(c[0]) | (vis_u8(c[1]) << 8) | (vis_u8(c[2]) << 16) | (vis_u8(c[3]) << 24);
-            o.b = vis_u8(c[4]) | (vis_u8(c[5]) << 8) | (vis_u8(c[6]) << 16) | (vis_u8(c[7]) << 24);
-            o.c = vis_u8(c[8]) | (vis_u8(c[9]) << 8) | (vis_u8(c[10]) << 16) | (vis_u8(c[11]) << 24);
-            *(VisU32x3*)(rgb8 + p0 * 3) = o;
+            o.a = rgb8(c[0]) | (rgb8(c[1]) << 8) | (rgb8(c[2]) << 16) | (rgb8(c[3]) << 24);
+            o.b = rgb8(c[4]) | (rgb8(c[5]) << 8) | (rgb8(c[6]) << 16) | (rgb8(c[7]) << 24);
+            o.c = rgb8(c[8]) | (rgb8(c[9]) << 8) | (rgb8(c[10]) << 16) | (rgb8(c[11]) << 24);
+            *(VisU32x3*)(out8 + p0 * 3) = o;
         } else {
-            for (int j = 0; j < cnt * 3; j++) rgb8[p0 * 3 + j] = (uint8_t)vis_u8(c[j]);
+            for (int j = 0; j < cnt * 3; j++) out8[p0 * 3 + j] = (uint8_t)rgb8(c[j]);
         }
     }
 }

@@ -15,7 +15,7 @@ means and the thresholds (<= max_dist) need.  The grid rule of include/durf_geom
 cells per axis) makes the result equal to a brute-force search in the same fp32 arithmetic, bit for bit."""
 import numpy as np
 
-from . import camera
+from . import camera, trimesh
 from .lattice import _max_dist
 from ._geom_sigs import DURF_GEOM_MAX_CELLS as MAX_CELLS        # per axis (include/durf_geom.h)
 SLACK = 1.0 + 2.0 ** -10            # a cell is max_dist * SLACK wide
@@ -209,10 +209,9 @@ def sample_mesh(m, n):
     sequence inside each triangle: deterministic.  A mesh of total area 0: n rows of NaN with id -1."""
     import torch
     from . import ops
-    v, t = m['vertices'], m['triangles']
-    dev = v.device if torch.is_tensor(v) and v.is_cuda else torch.device('cuda', torch.cuda.current_device())
-    v = torch.as_tensor(np.ascontiguousarray(v) if not torch.is_tensor(v) else v).to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
-    t = torch.as_tensor(np.ascontiguousarray(t) if not torch.is_tensor(t) else t).to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+    v, t = m['vertices'], m['triangles']                              # (no refusal of its own: a mesh of any shape with 3 V and 3 T values)
+    dev = trimesh.device_of(v)
+    v, t = trimesh.upload(v, torch.float32, dev).reshape(-1, 3), trimesh.upload(t, torch.int32, dev).reshape(-1, 3)
     if int(n) < 0:
         raise ValueError('geometry.sample_mesh: n = %r samples' % (n,))
     points, tri, _ = ops.geom_sample_mesh(v, t, int(n))

@@ -106,6 +106,11 @@ def _f32(t):
     return t
 
 
+def _i32(t, n, what):
+    assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == n, (what, t.dtype, tuple(t.shape), n)
+    return t
+
+
 def _enable(box_enable, K, dev):
     """box_enable (None or K values 0 / 1) -> None or a contiguous int32 [K] tensor on `dev`: the device-side switch of the box
     test (durf_ray_setup_masked).  A tensor already on the device is used where it is: no copy, no synchronisation."""
@@ -1850,6 +1855,19 @@ def _dims(shape):
     return nu, nv, nw
 
 
+def _mesh(vertices, triangles):
+    """the triangle mesh every mesh library takes: vertices float32 [V,3], triangles int32 [T,3], contiguous on the device -> (V, T)"""
+    V, T = int(vertices.shape[0]), int(triangles.shape[0])
+    assert _f32(vertices).numel() == 3 * V and _i32(triangles, 3 * T, 'triangles') is triangles
+    return V, T
+
+
+def _cams(cams):
+    """cams [F,CAM_FLOATS] float32, contiguous on the device -> F"""
+    assert _f32(cams).dim() == 2 and cams.shape[1] == CAM_FLOATS, tuple(cams.shape)
+    return int(cams.shape[0])
+
+
 def _lattice_args(origin, du, dv, dw):
     return _host_floats(origin, 3, 'origin'), _host_floats(du, 3, 'du'), _host_floats(dv, 3, 'dv'), _host_floats(dw, 3, 'dw')
 
@@ -2314,11 +2332,6 @@ def parts_workspace_bytes(shape):
     return int(_lib.parts_lib().durf_parts_workspace_bytes(*_dims(shape)))
 
 
-def _i32(t, n, what):
-    assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == n, (what, t.dtype, tuple(t.shape), n)
-    return t
-
-
 def parts_label(density, valid, shape, iso, ws=None, labels=None):
     """durf_parts_label: the label of every lattice point (the smallest index of its component, -1 where it is not in) ->
     (labels int32 [n], the workspace).  Three launches, no read-back."""
@@ -2386,18 +2399,10 @@ def raster_workspace_bytes(F, T, h, w):
     return int(_lib.raster_lib().durf_raster_workspace_bytes(int(F), int(T), int(h), int(w)))
 
 
-def _raster_mesh(cams, vertices, triangles):
-    assert cams.dtype == torch.float32 and cams.is_cuda and cams.is_contiguous() and cams.dim() == 2 and cams.shape[1] == CAM_FLOATS, tuple(cams.shape)
-    V, T = int(vertices.shape[0]), int(triangles.shape[0])
-    assert vertices.numel() == 3 * V and triangles.dtype == torch.int32 and triangles.is_cuda and triangles.is_contiguous() and triangles.numel() == 3 * T
-    _f32(vertices)
-    return int(cams.shape[0]), V, T
-
-
 def raster_setup(cams, h, w, vertices, triangles, znear, cull=0, ws=None):
     """durf_raster_setup: project, cull, snap and count per tile, scan -> (counts int32 [RASTER_COUNTS] ON THE DEVICE:
     RASTER_COUNT_FIELDS; the workspace, a uint8 tensor raster_draw reads).  No read-back."""
-    F, V, T = _raster_mesh(cams, vertices, triangles)
+    F, (V, T) = _cams(cams), _mesh(vertices, triangles)
     dev = cams.device
     ws = _ws(ws, raster_workspace_bytes(F, T, h, w), dev)
     counts = torch.empty(RASTER_COUNTS, dtype=torch.int32, device=dev)
@@ -2451,7 +2456,7 @@ def raster_interp(triangles, tri, bary, n_vertices, attr_f=None, attr_i=None, fi
 def raster_render_mesh(cams, h, w, vertices, triangles, znear, max_pairs, cull=0, attr_f=None, attr_i=None, fill=-1, ws=None, pairs=None):
     """durf_render_mesh: setup, draw and (with an attribute) interp in one call, for a pair capacity the caller chose -> dict
     counts (ON THE DEVICE), tri, depth, bary, out_f, out_i.  counts[0] > max_pairs: the -2 / NaN picture."""
-    F, V, T = _raster_mesh(cams, vertices, triangles)
+    F, (V, T) = _cams(cams), _mesh(vertices, triangles)
     dev, mp = cams.device, int(max_pairs)
     ws = _ws(ws, raster_workspace_bytes(F, T, h, w), dev)
     if pairs is None:
@@ -2531,8 +2536,7 @@ def geom_stats(dist, index, thresholds=(), out=None, ws=None):
 def geom_sample_mesh(vertices, triangles, n, ws=None):
     """durf_geom_sample_mesh: n area-uniform samples of the mesh (vertices [V,3], triangles [T,3] int32) -> (points [n,3], tri [n]
     int32: the triangle of each sample, total_area float64 [1] on the device)"""
-    V, T, n = int(_geom_points(vertices, 'vertices').shape[0]), int(triangles.shape[0]), int(n)
-    assert triangles.dtype == torch.int32 and triangles.is_contiguous() and triangles.dim() == 2 and triangles.shape[1] == 3
+    (V, T), n = _mesh(vertices, triangles), int(n)
     dev = vertices.device
     L = _lib.geom_lib()
     ws = _ws(ws, int(L.durf_geom_workspace_bytes(0, T)), dev)
@@ -2563,7 +2567,7 @@ def tsdf_integrate(tsdf, weight, colour, shape, origin, du, dv, dw, cams, depth,
     nu, nv, nw, n = _tsdf_state(tsdf, weight, colour, shape)
     assert _f32(depth).dim() == 3, tuple(depth.shape)
     F, h, w = (int(s) for s in depth.shape)
-    assert _f32(cams).numel() == CAM_FLOATS * F, (tuple(cams.shape), F)
+    assert _cams(cams) == F, (tuple(cams.shape), F)
     assert acc is None or _f32(acc).numel() == F * h * w
     assert rgb is None or _f32(rgb).numel() == 3 * F * h * w
     assert label is None or _i32(label, F * h * w, 'label') is label
@@ -2611,16 +2615,10 @@ def cast_workspace_bytes(T):
     return int(_lib.cast_lib().durf_cast_workspace_bytes(int(T)))
 
 
-def _cast_mesh(vertices, triangles):
-    V, T = int(vertices.shape[0]), int(triangles.shape[0])
-    assert _f32(vertices).numel() == 3 * V and _i32(triangles, 3 * T, 'triangles') is triangles
-    return V, T
-
-
 def cast_keys(vertices, triangles, bounds):
     """durf_cast_keys: the Morton key of every triangle's centroid inside bounds [6] ON THE DEVICE (lo, hi) -> int64 [T];
     INT64_MAX for an invalid triangle"""
-    V, T = _cast_mesh(vertices, triangles)
+    V, T = _mesh(vertices, triangles)
     assert _f32(bounds).numel() == 6
     keys = torch.empty(T, dtype=torch.int64, device=vertices.device)
     with _Timed('cast_keys'):
@@ -2630,7 +2628,7 @@ def cast_keys(vertices, triangles, bounds):
 
 def cast_build(vertices, triangles, order, ws=None):
     """durf_cast_build: the implicit tree over the permutation order [T] int32 -> the workspace (a uint8 tensor the casts read)"""
-    V, T = _cast_mesh(vertices, triangles)
+    V, T = _mesh(vertices, triangles)
     _i32(order, T, 'order')
     if ws is None:
         ws = torch.empty(cast_workspace_bytes(T), dtype=torch.uint8, device=vertices.device)
@@ -2678,8 +2676,7 @@ def cast_any(ws, T, origins, directions, tmin=0.0, tmax=float('inf'), cull=0):
 
 def cast_cameras(ws, T, cams, h, w, tmin=0.0, tmax=float('inf'), cull=0, want_bary=True):
     """durf_cast_cameras: cams [F,CAM_FLOATS] on the device, all h x w -> (tri int32 [F,h,w], depth [F,h,w], bary [F,h,w,3] or None)"""
-    assert _f32(cams).dim() == 2 and cams.shape[1] == CAM_FLOATS, tuple(cams.shape)
-    F, h, w, dev = int(cams.shape[0]), int(h), int(w), cams.device
+    F, h, w, dev = _cams(cams), int(h), int(w), cams.device
     tri, depth = torch.empty(F, h, w, dtype=torch.int32, device=dev), torch.empty(F, h, w, device=dev)
     bary = torch.empty(F, h, w, 3, device=dev) if want_bary else None
     with _Timed('cast_cameras'):
@@ -2725,7 +2722,7 @@ def closest_grid(ws, T, shape, origin, du, dv, dw, max_dist=float('inf'), want_t
 def shade_surface(vertices, triangles, tri, bary, toward=None):
     """durf_shade_surface: tri int32 [...], bary [..., 3] = (w, u, v), toward [..., 3] or None -> (point [..., 3], normal [..., 3]);
     zero where the sample is not valid, a zero normal on a flat triangle"""
-    V, T = _cast_mesh(vertices, triangles)
+    V, T = _mesh(vertices, triangles)
     n, lead, dev = int(tri.numel()), tuple(tri.shape), tri.device
     _i32(tri, n, 'tri')
     assert _f32(bary).numel() == 3 * n and (toward is None or _f32(toward).numel() == 3 * n), (tuple(bary.shape), lead)
@@ -2774,11 +2771,10 @@ def shade_cameras(cast_ws, vertices, triangles, cams, h, w, dirs, bias, reach, l
                   tmin=0.0, tmax=float('inf'), cull=0, want_normal=True, want_f=True, want_u8=True, ws=None):
     """durf_shade_cameras: cams [F,CAM_FLOATS] on the device, all h x w -> dict tri, depth, normal (or None), ao_used, ao_blocked,
     out_f, out_u8 as [F,h,w(,3)]: the cast, the surface, the two occlusions and the colour in four launches"""
-    V, T = _cast_mesh(vertices, triangles)
-    assert _f32(cams).dim() == 2 and cams.shape[1] == CAM_FLOATS, tuple(cams.shape)
+    V, T = _mesh(vertices, triangles)
     assert _f32(dirs).dim() == 2 and dirs.shape[1] == 3, tuple(dirs.shape)
     assert albedo_vertex is None or _f32(albedo_vertex).numel() == 3 * V, (V,)
-    F, h, w, dev = int(cams.shape[0]), int(h), int(w), cams.device
+    F, h, w, dev = _cams(cams), int(h), int(w), cams.device
     ws = _ws(ws, shade_workspace_bytes(F, h, w), dev)
     i32 = lambda: torch.empty(F, h, w, dtype=torch.int32, device=dev)
     r = dict(tri=i32(), depth=torch.empty(F, h, w, device=dev), normal=torch.empty(F, h, w, 3, device=dev) if want_normal else None,

@@ -13,7 +13,7 @@ integer coverage: the same inputs give the same bits.  A triangle that crosses t
 (counts['crossing'] says how many)."""
 import numpy as np
 
-from . import camera
+from . import camera, trimesh
 from .lattice import _host
 from ._raster_sigs import DURF_RASTER_MAX_SIZE as MAX_SIZE, DURF_RASTER_RECORD_INTS as RECORD_INTS, DURF_RASTER_TILE as TILE
 
@@ -39,33 +39,22 @@ def default_frames_per_call(F, T, h, w, bound=WORKSPACE_BOUND):
 def _check(m, cams, znear, attrs, label, cull, per_call):
     """every refusal of render_mesh, on the host, before anything touches the device -> (cams float32 [F,CAM_FLOATS], h, w, V, T)"""
     entry = 'raster.render_mesh'
-    if not isinstance(m, dict) or m.get('vertices') is None or m.get('triangles') is None:
-        raise ValueError('%s: m is a dict with vertices [V,3] and triangles [T,3]' % entry)
-    vs, ts = tuple(m['vertices'].shape), tuple(m['triangles'].shape)
-    if len(vs) != 2 or vs[1] != 3 or len(ts) != 2 or ts[1] != 3:
-        raise ValueError('%s: vertices of shape %s and triangles of shape %s, expected [V,3] and [T,3]' % (entry, vs, ts))
+    V, T = trimesh.shapes(m, entry)
     cams, h, w = camera.as_rows(cams, entry)
     if not np.isfinite(cams).all():
         raise ValueError('%s: a camera row that is not finite' % entry)
     if not (1 <= h <= MAX_SIZE and 1 <= w <= MAX_SIZE):
         raise ValueError('%s: frames of %d x %d, expected 1 .. %d each way' % (entry, h, w, MAX_SIZE))
-    if vs[0] >= 2 ** 31 or ts[0] >= 2 ** 31:
-        raise ValueError('%s: %d vertices and %d triangles, the limit is 2^31 - 1' % (entry, vs[0], ts[0]))
+    trimesh.limits(V, T, entry)
     if not float(znear) > 0:
         raise ValueError('%s: znear = %r, expected a number > 0' % (entry, znear))
     if cull not in (0, 1, 2):
         raise ValueError('%s: cull = %r, expected 0 (both faces), 1 (drop back faces) or 2 (drop front faces)' % (entry, cull))
-    if isinstance(attrs, str) or not all(isinstance(a, str) for a in attrs):
-        raise ValueError('%s: attrs = %r, expected a tuple of keys of m' % (entry, attrs))
-    for key in tuple(attrs) + ((label,) if label is not None else ()):
-        if not isinstance(key, str):
-            raise ValueError('%s: label = %r, expected a key of m or None' % (entry, key))
-        a = m.get(key)
-        if a is not None and a.shape[0] != vs[0]:
-            raise ValueError('%s: m[%r] has %d rows for %d vertices' % (entry, key, a.shape[0], vs[0]))
+    trimesh.check_attrs(attrs, entry, of='m')
+    trimesh.check_attribute_rows(m, attrs, label, V, entry)
     if per_call is not None and (int(per_call) != per_call or per_call < 1):
         raise ValueError('%s: frames_per_call = %r, expected an integer >= 1 or None' % (entry, per_call))
-    return cams, h, w, vs[0], ts[0]
+    return cams, h, w, V, T
 
 
 def render_mesh(m, cams, znear=1e-2, attrs=('rgb', 'normals'), label='owner', cull=0, frames_per_call=None):
@@ -82,17 +71,9 @@ def render_mesh(m, cams, znear=1e-2, attrs=('rgb', 'normals'), label='owner', cu
     cams, h, w, V, T = _check(m, cams, znear, attrs, label, cull, frames_per_call)
     import torch
     from . import ops
-    v = m['vertices']
-    dev = v.device if torch.is_tensor(v) and v.is_cuda else torch.device('cuda', torch.cuda.current_device())
-    up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a) if not torch.is_tensor(a) else a).to(device=dev, dtype=dt).contiguous()
-    vertices, triangles = up(v, torch.float32).reshape(V, 3), up(m['triangles'], torch.int32).reshape(T, 3)
-    fattrs = {}
-    for key in attrs:
-        a = m.get(key)
-        if a is not None:
-            scale = 1.0 / 255.0 if (a.dtype == np.uint8 or a.dtype == torch.uint8) else 1.0
-            fattrs[key] = (up(a, torch.float32).reshape(V, -1) * scale).contiguous()
-    lab = up(m[label], torch.int32).reshape(V) if label is not None and m.get(label) is not None else None
+    dev = trimesh.device_of(m['vertices'])
+    vertices, triangles = trimesh.on_device(m, V, T, dev)
+    fattrs, lab = trimesh.vertex_attributes(m, attrs, label, V, dev)
     F = cams.shape[0]
     per = int(frames_per_call) if frames_per_call is not None else default_frames_per_call(F, T, h, w)
     cams_dev = torch.as_tensor(cams).to(dev)

@@ -14,6 +14,8 @@ import math
 
 import numpy as np
 
+from . import trimesh
+
 MAX_DIRS = 256                         # DURF_SHADE_MAX_DIRS (tests/test_shade_host.py holds the two together)
 LIGHT = (0.35, 0.85, 0.4)              # the default sun: from above, a little to the side
 
@@ -82,11 +84,6 @@ def _tree(entry, b):
     return b
 
 
-def _on(dev, a, dtype):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a) if not torch.is_tensor(a) else a).to(device=dev, dtype=dtype).contiguous()
-
-
 def surface(b, tri, bary, toward=None):
     """The primary hits (tri [...] int32, bary [...,3] = (w, u, v): the cast's, the rasteriser's or closest's) on cast.build's b
     -> (point [...,3], normal [...,3]); toward [...,3]: the rays' directions, the normal then faces their origin.  Zero where
@@ -100,8 +97,8 @@ def surface(b, tri, bary, toward=None):
     import torch
     from . import ops
     dev = b['ws'].device
-    return ops.shade_surface(b['vertices'], b['triangles'], _on(dev, tri, torch.int32), _on(dev, bary, torch.float32),
-                             None if toward is None else _on(dev, toward, torch.float32))
+    return ops.shade_surface(b['vertices'], b['triangles'], trimesh.upload(tri, torch.int32, dev), trimesh.upload(bary, torch.float32, dev),
+                             None if toward is None else trimesh.upload(toward, torch.float32, dev))
 
 
 def occlusion(b, points, normals, dirs, reach, bias=None, cull=0):
@@ -118,7 +115,7 @@ def occlusion(b, points, normals, dirs, reach, bias=None, cull=0):
     import torch
     from . import ops
     dev = b['ws'].device
-    return ops.shade_occlusion(b['ws'], b['T'], _on(dev, points, torch.float32), _on(dev, normals, torch.float32), _on(dev, dirs, torch.float32),
+    return ops.shade_occlusion(b['ws'], b['T'], trimesh.upload(points, torch.float32, dev), trimesh.upload(normals, torch.float32, dev), trimesh.upload(dirs, torch.float32, dev),
                                bias, reach, cull)
 
 
@@ -139,9 +136,9 @@ def compose(tri, normals, used, blocked, light=LIGHT, ambient=0.5, background=(1
             raise ValueError('%s: %s of shape %s for tri of shape %s' % (entry, name, tuple(getattr(a, 'shape', ())), lead))
     import torch
     from . import ops
-    dev = tri.device if torch.is_tensor(tri) and tri.is_cuda else torch.device('cuda', torch.cuda.current_device())
-    i32 = lambda a: None if a is None else _on(dev, a, torch.int32)
-    f32 = lambda a: None if a is None else _on(dev, a, torch.float32)
+    dev = trimesh.device_of(tri)
+    i32 = lambda a: None if a is None else trimesh.upload(a, torch.int32, dev)
+    f32 = lambda a: None if a is None else trimesh.upload(a, torch.float32, dev)
     return ops.shade_compose(i32(tri), f32(normals), i32(used), i32(blocked), light, ambient, background, i32(sun_blocked), f32(albedo))
 
 
@@ -192,13 +189,11 @@ def cameras(b, cams, dirs=64, reach=None, bias=None, light=LIGHT, sun=True, ambi
     import torch
     from . import ops
     dev = b['ws'].device
-    a = b.get(albedo) if albedo is not None else None
+    a = trimesh.vertex_attributes(b, (albedo,), None, b['V'], dev)[0].get(albedo) if albedo is not None else None
     if a is not None:
-        scale = 1.0 / 255.0 if (a.dtype == np.uint8 or a.dtype == torch.uint8) else 1.0
-        a = (torch.as_tensor(a).to(device=dev, dtype=torch.float32).reshape(b['V'], -1) * scale).contiguous()
         if a.shape[1] != 3:
             raise ValueError('%s: albedo %r of shape %s, expected [V,3]' % (entry, albedo, tuple(a.shape)))
-    r = ops.shade_cameras(b['ws'], b['vertices'], b['triangles'], torch.as_tensor(cams).to(dev).contiguous(), h, w, _on(dev, dirs, torch.float32),
+    r = ops.shade_cameras(b['ws'], b['vertices'], b['triangles'], torch.as_tensor(cams).to(dev).contiguous(), h, w, trimesh.upload(dirs, torch.float32, dev),
                           bias, reach, light, bool(sun), ambient, background, albedo_vertex=a, tmin=tmin, tmax=tmax, cull=cull)
     return dict(tri=r['tri'], depth=r['depth'], mask=r['tri'] >= 0, normal=r['normal'], ao_used=r['ao_used'], ao_blocked=r['ao_blocked'],
                 ao=ao_plane(r['ao_used'], r['ao_blocked']), shaded=r['out_f'], shaded8=r['out_u8'], reach=reach, bias=bias, light=light)
@@ -266,7 +261,7 @@ def meta(args, r):
 
 
 def to_u8(x):
-    """k_frame_pack's rule in torch: round-half-even of clamp(x, 0, 1) * 255, 0 for a NaN -> uint8"""
+    """rgb8's rule (csrc/durf_common.h) in torch: round-half-even of clamp(x, 0, 1) * 255, 0 for a NaN -> uint8"""
     import torch
     return torch.round(torch.nan_to_num(x, nan=0.0).clamp(0.0, 1.0) * 255.0).to(torch.uint8)
 

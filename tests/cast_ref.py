@@ -7,6 +7,8 @@ import functools
 
 import numpy as np
 
+from tests.trimesh_ref import box_mesh, dirty_mesh, icosphere, quad_grid, random_soup, valid_triangles  # noqa: F401  (the mesh and its scenes are trimesh_ref's)
+
 F32 = np.float32
 LEAF, STACK, KEY_BITS = 4, 32, 21
 INF = F32(np.inf)
@@ -14,18 +16,6 @@ INF = F32(np.inf)
 
 def _f(a):
     return np.ascontiguousarray(a, dtype=F32)
-
-
-def valid_triangles(vertices, triangles):
-    """-> (valid [T] bool, P [T,3,3] float32: the vertices of the valid triangles, 0 for the others)"""
-    v, t = _f(vertices).reshape(-1, 3), np.asarray(triangles, np.int64).reshape(-1, 3)
-    ok = ((t >= 0) & (t < v.shape[0])).all(1)
-    P = np.zeros((t.shape[0], 3, 3), F32)
-    if ok.any():
-        P[ok] = v[t[ok]]
-    ok &= np.isfinite(P).all((1, 2))
-    P[~ok] = 0
-    return ok, P
 
 
 def tri_box(P):
@@ -318,47 +308,7 @@ def bvh32(vertices, triangles, order, o, d, tmin=0.0, tmax=np.inf, cull=0, any_h
     return tri, t, bary
 
 
-# ---- scenes -----------------------------------------------------------------------------------------------------------------------
-def icosphere(level=2, radius=1.0, centre=(0.0, 0.0, 0.0)):
-    """a closed, outward-facing (counter-clockwise from outside) icosphere -> (vertices float32 [V,3], triangles int32 [T,3])"""
-    g = (1.0 + 5.0 ** 0.5) / 2.0
-    v = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g), (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
-    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
-         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
-    v = [np.asarray(x, np.float64) / np.linalg.norm(x) for x in v]
-    for _ in range(level):
-        mid, nf = {}, []
-
-        def m(a, b):
-            key = (min(a, b), max(a, b))
-            if key not in mid:
-                x = v[a] + v[b]
-                v.append(x / np.linalg.norm(x))
-                mid[key] = len(v) - 1
-            return mid[key]
-        for a, b, c in f:
-            ab, bc, ca = m(a, b), m(b, c), m(c, a)
-            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
-        f = nf
-    return (np.asarray(v) * radius + np.asarray(centre)).astype(F32), np.asarray(f, np.int32)
-
-
-def quad_grid(n=16, z=0.0):
-    """n x n axis-aligned unit quads in the plane z (flat boxes), two triangles each, normals +z"""
-    xs = np.arange(n + 1, dtype=F32)
-    v = np.stack(list(np.meshgrid(xs, xs, indexing='ij')) + [np.full((n + 1, n + 1), z, F32)], -1).reshape(-1, 3)
-    i, j = (a.reshape(-1) for a in np.meshgrid(np.arange(n), np.arange(n), indexing='ij'))
-    a, b, c, d = i * (n + 1) + j, (i + 1) * (n + 1) + j, (i + 1) * (n + 1) + j + 1, i * (n + 1) + j + 1
-    return v.astype(F32), np.concatenate([np.stack([a, b, c], 1), np.stack([a, c, d], 1)]).astype(np.int32)
-
-
-def random_soup(T, seed, scale=0.15):
-    """T small random triangles in the unit cube, no shared vertices"""
-    rng = np.random.default_rng(seed)
-    c = rng.random((T, 1, 3))
-    return (c + scale * (rng.random((T, 3, 3)) - 0.5)).reshape(-1, 3).astype(F32), np.arange(3 * T, dtype=np.int32).reshape(T, 3)
-
-
+# ---- scenes (the meshes themselves: trimesh_ref) --------------------------------------------------------------------------------
 def random_rays(n, seed, centre=0.5, spread=1.5):
     """origins around the unit cube, directions towards points inside it: not unit length"""
     rng = np.random.default_rng(seed)
@@ -406,21 +356,6 @@ def bad_rays():
     o = [(nan, 0, 0), (0, 0, 2), (inf, 0, 0), (0, 0, 2), (0, 0, 2), (0, 0, 2), (0, 0, 2), (0.2, 0.2, 2)]
     d = [(0, 0, -1), (0, nan, -1), (0, 0, -1), (0, -inf, -1), (0, 0, 0), (0, 0, -1), (0, 0, -1), (0, 0, -1)]
     return np.asarray(o, F32), np.asarray(d, F32), np.asarray([0, 0, 0, 0, 0, -1, 0, 0], F32), np.asarray([inf, inf, inf, inf, inf, inf, nan, inf], F32)
-
-
-def dirty_mesh(seed=5):
-    """a valid soup with degenerate triangles, out-of-range indices and non-finite vertices mixed in"""
-    v, t = random_soup(200, seed)
-    v, t = v.copy(), t.copy()
-    t[3] = (t[3, 0], t[3, 0], t[3, 1])                                      # degenerate: two equal vertices
-    v[3 * 7 + 1] = v[3 * 7]                                                 # degenerate: two coincident vertices
-    t[11, 2] = -1
-    t[12, 0] = v.shape[0]
-    t[13, 1] = 2 ** 31 - 1
-    v[3 * 20, 1] = np.nan
-    v[3 * 21 + 2, 0] = np.inf
-    v[3 * 22 + 1, 2] = -np.inf
-    return v, t
 
 
 RAY_COUNTS = (0, 1, 63, 64, 65, 255, 256, 257)
@@ -489,14 +424,6 @@ def pinhole32(cam, h, w):
     cd = ((x - cam[13]) / cam[12], -(y - cam[14]) / cam[12], np.full(h * w, F32(-1.0)))
     d = np.stack([(cd[0] * cam[4 * a] + cd[1] * cam[4 * a + 1]) + cd[2] * cam[4 * a + 2] for a in range(3)], 1)
     return np.tile(cam[[3, 7, 11]], (h * w, 1)).astype(F32), d.astype(F32)
-
-
-def box_mesh(lo, hi):
-    """the closed box [lo, hi] as 12 triangles, outward-facing"""
-    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
-    v = np.asarray([[(lo, hi)[i >> a & 1][a] for a in range(3)] for i in range(8)], F32)      # bit a of i: the high side of axis a
-    q = [(0, 2, 6, 4), (1, 5, 7, 3), (0, 4, 5, 1), (2, 3, 7, 6), (0, 1, 3, 2), (4, 6, 7, 5)]   # -x +x -y +y -z +z
-    return v, np.asarray([t for a, b, c, d in q for t in ((a, c, b), (a, d, c))], np.int32)
 
 
 def rasteriser_comparison(rast, cst, rast64, c64, tris, judged=None, edge=None):

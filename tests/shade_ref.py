@@ -9,6 +9,7 @@ import functools
 import numpy as np
 
 from tests import cast_ref as R
+from tests.trimesh_ref import interp32, merge, u8  # noqa: F401  (the interpolation, the 8-bit pack and the merge are trimesh_ref's)
 
 F32 = np.float32
 INF = F32(np.inf)
@@ -130,14 +131,6 @@ def occlusion64(vertices, triangles, points, normals, dirs, bias, reach, cull=0,
     return dict(used=used, blocked=blocked, margin=margin)
 
 
-def u8(x):
-    """k_frame_pack's rule: round-half-even of clamp(x, 0, 1) * 255, 0 for a NaN"""
-    x = _f(x)
-    with np.errstate(all='ignore'):
-        c = np.where(np.isnan(x), F32(0), np.fmin(np.fmax(x, F32(0)), F32(1)))
-        return np.rint(c * F32(255.0)).astype(np.uint8)
-
-
 def compose32(tri, normals, used, blocked, light, ambient, background, sun_blocked=None, albedo=None):
     """-> (out_f float32 [n,3], out_u8 uint8 [n,3])"""
     tri = np.asarray(tri, np.int64).reshape(-1)
@@ -154,30 +147,7 @@ def compose32(tri, normals, used, blocked, light, ambient, background, sun_block
     return out, u8(out)
 
 
-def interp32(triangles, tri, bary, attr):
-    """durf_raster_interp's rule on a per-vertex attr [V,C]: (q0 a0 + q1 a1) + q2 a2, 0 where the sample names no triangle whose
-    indices lie in 0 .. V-1"""
-    t, tri, attr = np.asarray(triangles, np.int64).reshape(-1, 3), np.asarray(tri, np.int64).reshape(-1), _f(attr)
-    n, V = tri.shape[0], attr.shape[0]
-    hit = (tri >= 0) & (tri < t.shape[0])
-    v = t[np.where(hit, tri, 0)] if t.shape[0] else np.zeros((n, 3), np.int64)
-    hit &= ((v >= 0) & (v < V)).all(1)
-    v = np.where(hit[:, None], v, 0)
-    q = np.where(hit[:, None], _f(bary).reshape(n, 3), F32(0))
-    with np.errstate(all='ignore'):
-        a = (q[:, 0:1] * attr[v[:, 0]] + q[:, 1:2] * attr[v[:, 1]]) + q[:, 2:3] * attr[v[:, 2]]
-    return np.where(hit[:, None], a, F32(0)).astype(F32)
-
-
 # ---- scenes -----------------------------------------------------------------------------------------------------------------------
-def merge(*meshes):
-    vs, ts, off = [], [], 0
-    for v, t in meshes:
-        vs.append(_f(v).reshape(-1, 3)), ts.append(np.asarray(t, np.int32).reshape(-1, 3) + off)
-        off += vs[-1].shape[0]
-    return np.concatenate(vs), np.concatenate(ts)
-
-
 @functools.lru_cache(maxsize=None)
 def sphere_on_ground(grid=6):
     """the unit icosphere resting on a grid x grid ground of unit quads: the contact shadow -> (v, t); triangles 0 .. 319 are the

@@ -15,6 +15,7 @@ import numpy as np
 from tests import camera_ref
 from tests.lattice_ref import frame_of, inverse_of, points as voxels  # noqa: F401  (the lattice is lattice_ref's)
 from tests.raster_ref import camera, look_at  # noqa: F401  (the camera rows are the rasteriser's)
+from tests.trimesh_ref import icosphere  # noqa: F401  (the same sphere bit for bit; box_mesh below numbers its vertices its own way and stays)
 
 F32 = np.float32
 MAX_COORD = float(1 << 20)
@@ -270,30 +271,6 @@ def crossings(D, W, P, shape, min_weight=1.0):
         t = a[ok] / (a[ok] - b[ok])
         pts.append(P[sa][ok] + t[:, None] * (P[sb][ok] - P[sa][ok]))
     return np.concatenate(pts)
-
-
-def icosphere(level, radius=1.0):
-    """an icosahedron subdivided `level` times, on the sphere, wound outward -> (vertices [V,3] float32, triangles [T,3] int32)"""
-    g = (1.0 + np.sqrt(5.0)) / 2.0
-    v = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g), (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
-    v = [np.asarray(p, np.float64) / np.linalg.norm(p) for p in v]
-    t = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8), (3, 9, 4), (3, 4, 2),
-         (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
-    for _ in range(level):
-        mid, nt = {}, []
-
-        def m(a, b):
-            key = (min(a, b), max(a, b))
-            if key not in mid:
-                p = v[a] + v[b]
-                v.append(p / np.linalg.norm(p))
-                mid[key] = len(v) - 1
-            return mid[key]
-        for a, b, c in t:
-            ab, bc, ca = m(a, b), m(b, c), m(c, a)
-            nt += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
-        t = nt
-    return (np.asarray(v) * radius).astype(F32), np.asarray(t, np.int32)
 
 
 def box_mesh(half):
