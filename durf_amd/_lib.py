@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get('DURF_LIB_PATH') or os.path.join(_HERE, 'libdurf_hip.s
 
 # the feature libraries built beside it, libdurf_<name>.so (include/durf_<name>.h): each links against libdurf_hip.so, reports
 # errors through its durf_last_error, and keeps its own entry points.  One word here (and one in csrc/Makefile) adds one.
-SATELLITES = ('overlay', 'lidar', 'flow', 'field', 'mesh', 'geom', 'parts', 'raster', 'tsdf', 'cast', 'closest', 'shade')
+SATELLITES = ('overlay', 'lidar', 'flow', 'field', 'mesh', 'geom', 'parts', 'raster', 'tsdf', 'cast', 'closest', 'shade', 'smooth')
 
 _lib = None
 _satellites = {}

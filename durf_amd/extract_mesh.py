@@ -3,6 +3,7 @@
     python -m durf_amd.extract_mesh --gin_file configs/waymo.gin --data_dir DATA --train_dir CKPT --grid "ox,oy,oz;nu,nv,nw;step"
                                     --iso V --ts T --eval_dir OUT [--objects] [--obj_step S] [--pad 0.05] [--colour query|grid|none]
                                     [--min_component N] [--largest K]
+                                    [--smooth N] [--smooth_lambda 0.5] [--smooth_mu -0.53] [--smooth_boundary pin|slide]
     python -m durf_amd.extract_mesh --synthetic --objects --eval_dir OUT [--grid ...]
 
 --grid: query_field's lattice (the origin of point (0, 0, 0), the point counts along x, y, z and one spacing, in scene units).
@@ -45,17 +46,21 @@ def build_parser():
                     'the grid\'s own colour interpolated, or none')
     ap.add_argument('--min_component', type=int, default=0, help='drop connected solid regions of fewer lattice points (0: keep all)')
     ap.add_argument('--largest', type=int, default=None, help='keep only this many of the biggest connected solid regions')
+    from . import smooth
+    smooth.add_arguments(ap)
     return ap
 
 
 def _record(m):
-    return dict(vertices=int(m['vertices'].shape[0]), triangles=int(m['triangles'].shape[0]), frame=m['frame'])
+    census = dict(census=m['census']) if 'census' in m else {}                # (only with --smooth)
+    return dict(vertices=int(m['vertices'].shape[0]), triangles=int(m['triangles'].shape[0]), frame=m['frame'], **census)
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     import numpy as np
-    from . import mesh
+    from . import mesh, smooth
+    sm = smooth.from_args(args, 'extract_mesh')
     if not args.synthetic and (args.data_dir is None or args.train_dir is None or args.grid is None):
         raise SystemExit('extract_mesh: --data_dir, --train_dir and --grid are required (or --synthetic)')
     try:
@@ -73,11 +78,13 @@ def main(argv=None):
     kw = dict(sigma=args.sigma, alpha=alpha, chunk=max(args.chunk, 1))
     if args.min_component or args.largest is not None:
         kw.update(min_points=args.min_component, largest=args.largest)
+    if sm is not None:
+        kw.update(smooth=sm)
     os.makedirs(args.eval_dir, exist_ok=True)
     bg = mesh.extract(model, variables, origin, shape, step=step, iso=args.iso, colour=colour, ts=args.ts, ext=ext if K else None,
                       box_enable=[0] * K if K else None, **kw)
     mesh.write_ply(os.path.join(args.eval_dir, 'background.ply'), bg)
-    meta = dict(iso=args.iso, ts=args.ts, sigma=args.sigma, step=step, background=_record(bg), objects=[], **bg.get('cleaning', {}))
+    meta = dict(iso=args.iso, ts=args.ts, sigma=args.sigma, step=step, background=_record(bg), objects=[], **bg.get('cleaning', {}), **(dict(smooth=bg['smooth']) if sm is not None else {}))
     if args.write_objects:
         obj_step = args.obj_step if args.obj_step is not None else 0.5 * step
         for k in range(K):

@@ -3,6 +3,7 @@
     python -m durf_amd.fuse_tsdf --gin_file configs/waymo.gin --data_dir DATA --train_dir CKPT --traj traj.npz
                                  --grid "ox,oy,oz;nu,nv,nw;step" --eval_dir OUT [--trunc D] [--objects] [--obj_step S]
                                  [--min_weight 1] [--min_component N] [--largest K] [--cam 0] [--carve]
+                                 [--smooth N] [--smooth_lambda 0.5] [--smooth_mu -0.53] [--smooth_boundary pin|slide]
     python -m durf_amd.fuse_tsdf --synthetic --objects --eval_dir OUT [--frames 8] [--grid ...]
 
 The cameras and times come from --traj (render_traj's file), the intrinsics from image --cam of the test split.  Every frame is
@@ -12,7 +13,9 @@ grid's) that follows it through the frames, fed by the pixels the instance map g
 scene units (default: three steps; the object volumes use three of theirs).  A voxel counts as observed from --min_weight on.
 Written: OUT/background.ply, OUT/object_%02d.ply (box k in its canonical frame), OUT/poses.npy ([T,K,6], as extract_mesh writes
 it: render_mesh --poses takes it) and OUT/tsdf.json (the shapes, trunc, the observed voxels and the vertices and triangles of
-every mesh).  --min_component / --largest: as for extract_mesh (durf_amd.parts).  --synthetic fuses
+every mesh).  --min_component / --largest: as for extract_mesh (durf_amd.parts).  --smooth N: N Taubin iterations on every mesh after the
+cleaning (durf_amd.smooth; vertices and normals change, triangles and colours stay); tsdf.json then gains `smooth` and a `census`
+per mesh.  --synthetic fuses
 train_boxpose.SyntheticTimestepDataset's scene instead (no data directory), which exercises the command end to end; like
 render_traj it needs the one-call inference path (bf16 object MLPs: --gin_param 'MipNerfModel.no_pose_opt = True' --gin_param
 'MipNerfModel.no_yaw_opt = True' for a freshly initialised model)."""
@@ -45,6 +48,8 @@ def build_parser():
     ap.add_argument('--batch', type=int, default=8, help='frames staged per integrate call')
     ap.add_argument('--min_component', type=int, default=0, help='drop connected regions of fewer lattice points (0: keep all)')
     ap.add_argument('--largest', type=int, default=None, help='keep only this many of the biggest connected regions')
+    from . import smooth
+    smooth.add_arguments(ap)
     return ap
 
 
@@ -70,15 +75,17 @@ def check_args(args):
 
 
 def _record(m, vol):
+    census = dict(census=m['census']) if 'census' in m else {}                # (only with --smooth)
     return dict(vertices=int(m['vertices'].shape[0]), triangles=int(m['triangles'].shape[0]), observed=int(m['observed']),
-                shape=list(vol['shape']), trunc=vol['trunc'], frame=vol['frame'], **m.get('cleaning', {}))
+                shape=list(vol['shape']), trunc=vol['trunc'], frame=vol['frame'], **m.get('cleaning', {}), **census)
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     origin, shape, step = check_args(args)
     import numpy as np
-    from . import camera, mesh, trajectory, tsdf
+    from . import camera, mesh, smooth, trajectory, tsdf
+    sm = smooth.from_args(args, 'fuse_tsdf')
     dev, config, dataset = open_scene(args, boxes=args.synthetic_boxes)  # (--objects is this command's switch, not the box count)
     cam_rows, ext, key_c2w, key_t = camera.scene_cameras(args, dataset, 'fuse_tsdf')
     focal, ppx, ppy, h, w = camera.intrinsics(cam_rows[args.cam])
@@ -94,10 +101,14 @@ def main(argv=None):
                         args.trunc if args.trunc is not None else 3.0 * step, obj_step=obj_step, pad=args.pad, carve=args.carve,
                         near=config.near, far=config.far, chunk=max(args.chunk, 1), batch=args.batch, min_acc=args.min_acc,
                         min_weight=args.min_weight, min_points=args.min_component, largest=args.largest, objects=args.write_objects)
+    if sm is not None:                                                       # (after the cleaning; the colours stay the fused ones)
+        s['background'] = mesh.smoothed(s['background'], sm)
+        s['objects'] = [mesh.smoothed(o, sm) for o in s['objects']]
     os.makedirs(args.eval_dir, exist_ok=True)
     mesh.write_ply(os.path.join(args.eval_dir, 'background.ply'), s['background'])
     meta = dict(frames=int(cams.shape[0]), h=int(h), w=int(w), min_weight=args.min_weight, step=step,
-                background=_record(s['background'], s['volumes']['background']), objects=[])
+                background=_record(s['background'], s['volumes']['background']), objects=[],
+                **(dict(smooth=s['background']['smooth']) if sm is not None else {}))
     for k, (o, v) in enumerate(zip(s['objects'], s['volumes']['objects'])):
         mesh.write_ply(os.path.join(args.eval_dir, 'object_%02d.ply' % k), o)
         meta['objects'].append(dict(_record(o, v), box=k, step=obj_step))

@@ -95,24 +95,47 @@ def _clean(m, g, iso, min_points, largest):
     return m
 
 
+def smoothed(m, sm):
+    """the opt-in smoothing of extract, extract_object and extract_scene (durf_amd.smooth.taubin, after _clean): with smooth=0 m
+    as it is.  Adds `smooth` (the arguments used) and `census` (of the mesh that was smoothed: closed? manifold?).  sm: None, or
+    smooth.options' dict.  fuse_tsdf applies it to tsdf.fuse_scene's meshes."""
+    if sm is None:
+        return m
+    from . import smooth
+    adj = smooth.adjacency(m)
+    out = smooth.taubin(m, adj=adj, **sm)
+    out['smooth'] = dict(dict(iters=10, lam=0.5, mu=-0.53, boundary='pin'), **{k: v for k, v in sm.items() if k != 'fixed'})
+    out['census'] = smooth.census(adj)
+    return out
+
+
 def extract(model, variables, origin, shape, step=None, axes=None, iso=None, colour='query', view=(0.0, 0.0, -1.0), min_points=0,
-            largest=None, **kw):
+            largest=None, smooth=0, **kw):
     """field.grid over the lattice (its arguments: sigma, ts, alpha, pose, box_enable, chunk, inside_tol, ext), then surface
     -> surface's dict plus owner [V] int32 (the owner of each edge's in end: the box a vertex belongs to, -1 background) and
     rgb [V,3].  colour='query' (default): field.query(vertices, viewdirs=-normals), the colour seen looking straight at the
     surface; 'grid': the grid's own rgb, seen along `view`, interpolated along each edge; None: no colour.
     min_points, largest (opt-in; durf_amd.parts.keep): drop the connected solid regions of the lattice with fewer points, or all
     but the `largest` biggest, from the mesh -- a compaction: what stays keeps its bits; adds component [V] int32 and `cleaning`
-    (components, kept, dropped_points, sizes).  With the defaults nothing of this runs."""
-    from . import field
+    (components, kept, dropped_points, sizes).  With the defaults nothing of this runs.
+    smooth (opt-in; durf_amd.smooth.taubin): a number of Taubin iterations, or a dict of taubin's arguments (iters, lam, mu,
+    boundary, fixed); it runs after the cleaning, replaces vertices and normals, keeps the triangles, and adds `smooth` and
+    `census`.  colour='query' then asks the colour at the smoothed vertices with the fresh normals.  With smooth=0 nothing of
+    this runs."""
+    from . import field, smooth as smooth_
     iso = _iso(iso, 'mesh.extract')
+    sm = smooth_.options(smooth, 'mesh.extract')
     if colour not in ('query', 'grid', None):
         raise ValueError('mesh.extract: colour = %r, expected \'query\', \'grid\' or None' % (colour,))
     g = field.grid(model, variables, origin, shape, step=step, axes=axes, view=view if colour == 'grid' else None, **kw)
     m = surface(g, iso, normals=True, attrs=('rgb',) if colour == 'grid' else ())
     m['owner'] = _owner(m, g, iso)
-    m['rgb'] = _colour(m, g, colour, model, variables, kw, 'mesh.extract')
-    return _clean(m, g, iso, min_points, largest)
+    later = sm is not None and colour == 'query'                              # the colour is asked once, where the vertices end up
+    m['rgb'] = _colour(m, g, None if later else colour, model, variables, kw, 'mesh.extract')
+    m = smoothed(_clean(m, g, iso, min_points, largest), sm)
+    if later:
+        m['rgb'] = _colour(m, g, colour, model, variables, kw, 'mesh.extract')
+    return m
 
 
 def object_lattice(c, R, ext_k, step, pad):
@@ -130,16 +153,18 @@ def object_lattice(c, R, ext_k, step, pad):
             lattice.frame(c + R.T @ o_obj, axes=step * R, entry='mesh.extract_object'), shape)
 
 
-def extract_object(model, variables, k, ext, step, iso, ts=0, pad=0.05, colour='query', pose=None, min_points=0, largest=None, **kw):
+def extract_object(model, variables, k, ext, step, iso, ts=0, pad=0.05, colour='query', pose=None, min_points=0, largest=None, smooth=0,
+                   **kw):
     """Box k as a mesh in the box's own (canonical) frame.  The 24 bytes of its pose are read once; the lattice is built in
     the box's frame (spacing `step`, centred, inside |P_j| <= ext_kj (1 + pad)) and the WORLD field is queried at c_k + R_k^T P;
     the density is set to 0 where the owner is not k, and on the lattice's outermost layer, so the object closes at its faces;
     the surface is then taken in the object frame: vertices and normals are canonical coordinates.  -> extract's dict plus
     `grid` (the world-frame lattice that was meshed: density, valid, owner, frame) and `pose` (c [3], R [3,3] float64).
-    colour='query' asks the world field at the vertices' world positions.  min_points, largest: as for extract."""
+    colour='query' asks the world field at the vertices' world positions.  min_points, largest, smooth: as for extract."""
     import torch
-    from . import field
+    from . import field, smooth as smooth_
     iso = _iso(iso, 'mesh.extract_object')
+    sm = smooth_.options(smooth, 'mesh.extract_object')
     K = variables.layout.K if hasattr(variables, 'layout') else 0
     if not 0 <= int(k) < K:
         raise ValueError('mesh.extract_object: box %r of K = %d boxes' % (k, K))
@@ -162,30 +187,37 @@ def extract_object(model, variables, k, ext, step, iso, ts=0, pad=0.05, colour='
     g['valid'] = torch.where(mine, g['valid'], torch.ones_like(g['valid']))
     m = surface(dict(g, frame=dict(obj, shape=list(shape))), iso, normals=True, attrs=('rgb',) if colour == 'grid' else ())
     m['owner'] = _owner(m, g, iso)
-    if colour == 'query':
+
+    def ask(m):
         Rt = torch.tensor(R, dtype=torch.float32, device=m['vertices'].device)           # row vectors: X = c + P R
         X = (torch.tensor(c, dtype=torch.float32, device=Rt.device) + m['vertices'] @ Rt).contiguous()
         vd = view_of_normals(m['normals'] @ Rt)
-        m['rgb'] = field.query(model, variables, X, vd, ts=ts, pose=p, ext=ext, **kw)['rgb']
-    elif colour is None:
+        return field.query(model, variables, X, vd, ts=ts, pose=p, ext=ext, **kw)['rgb']
+    later = sm is not None and colour == 'query'                              # the colour is asked once, where the vertices end up
+    if colour == 'query' and not later:
+        m['rgb'] = ask(m)
+    elif colour is None or later:
         m['rgb'] = None
-    m = _clean(m, g, iso, min_points, largest)
+    m = smoothed(_clean(m, g, iso, min_points, largest), sm)
+    if later:
+        m['rgb'] = ask(m)
     m['grid'], m['pose'] = g, (c, R)
     return m
 
 
 def extract_scene(model, variables, origin, shape, step=None, axes=None, iso=None, ext=None, obj_step=None, ts=0, pad=0.05,
-                  colour='query', min_points=0, largest=None, **kw):
+                  colour='query', min_points=0, largest=None, smooth=0, **kw):
     """The whole scene as an asset: `background` (extract with every box disabled), `objects` (extract_object of every box,
     each in its own frame, at spacing obj_step) and `poses` [T,K,6] (the boxes' centres and rotation vectors at every timestep,
-    a host array): place object k at time t with X = c + R^T P.  min_points, largest: as for extract, for every mesh."""
+    a host array): place object k at time t with X = c + R^T P.  min_points, largest, smooth: as for extract, for every mesh."""
     iso = _iso(iso, 'mesh.extract_scene')
     K = variables.layout.K
     if K and (obj_step is None or ext is None):
         raise ValueError('mesh.extract_scene: obj_step and ext are needed for K = %d boxes' % K)
     bg = extract(model, variables, origin, shape, step=step, axes=axes, iso=iso, colour=colour, ts=ts, ext=ext,
-                 box_enable=[0] * K if K else None, min_points=min_points, largest=largest, **kw)
-    objs = [extract_object(model, variables, k, ext, obj_step, iso, ts=ts, pad=pad, colour=colour, min_points=min_points, largest=largest, **kw)
+                 box_enable=[0] * K if K else None, min_points=min_points, largest=largest, smooth=smooth, **kw)
+    objs = [extract_object(model, variables, k, ext, obj_step, iso, ts=ts, pad=pad, colour=colour, min_points=min_points, largest=largest,
+                           smooth=smooth, **kw)
             for k in range(K)]
     poses = variables['params']['box_centers'].detach().cpu().numpy()
     return dict(background=bg, objects=objs, poses=poses)

@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import _lib, camera
-from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs, _cast_sigs, _closest_sigs, _shade_sigs
+from . import _sigs as _H, _field_sigs, _flow_sigs, _geom_sigs, _lidar_sigs, _mesh_sigs, _overlay_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs, _cast_sigs, _closest_sigs, _shade_sigs, _smooth_sigs
 
 
 
@@ -22,7 +22,7 @@ def _by_prefix(table, prefix):
 # the tables imported above; tests/test_headers_host.py holds the tables to the C compiler).  Every `#define DURF_X <integer>`
 # of include/durf_hip.h and include/durf_<name>.h is ops.X: ENC_DIM, MAX_OBJ, TRAIN_OBJ_FP32, TIMED_STAGES, MESH_BLOCK, PARTS_TILE_K, ...
 # -- all but OVERLAP_MIN_ROWS, launch policy that the library is asked for (__getattr__ below).
-for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs, _cast_sigs, _closest_sigs, _shade_sigs):
+for _table in (_H, _overlay_sigs, _lidar_sigs, _flow_sigs, _field_sigs, _mesh_sigs, _geom_sigs, _parts_sigs, _raster_sigs, _tsdf_sigs, _cast_sigs, _closest_sigs, _shade_sigs, _smooth_sigs):
     globals().update(_by_prefix(_table, 'DURF_'))
 del OVERLAP_MIN_ROWS
 
@@ -2787,3 +2787,96 @@ def shade_cameras(cast_ws, vertices, triangles, cams, h, w, dirs, bias, reach, l
             _host_floats(background, 3, 'background'), _p(ws), ws.numel(), _z(r['tri']), _z(r['depth']), _z(r['normal']), _z(r['ao_used']),
             _z(r['ao_blocked']), _z(r['out_f']), _z(r['out_u8'])), 'durf_shade_cameras')
     return r
+
+
+# ---------------------------------------------------------------------------
+# vertex adjacency, census, Taubin smoothing and vertex normals of a mesh (include/durf_smooth.h, csrc/smooth.hip, libdurf_smooth.so)
+# ---------------------------------------------------------------------------
+def smooth_keys(triangles, V):
+    """durf_smooth_keys: triangles int32 [T,3] -> (edge_keys int64 [6T], corner_keys int64 [3T]), unsorted"""
+    T, dev = int(triangles.shape[0]), triangles.device
+    _i32(triangles, 3 * T, 'triangles')
+    ek, ck = torch.empty(6 * T, dtype=torch.int64, device=dev), torch.empty(3 * T, dtype=torch.int64, device=dev)
+    with _Timed('smooth_keys'):
+        _lib.check(_lib.smooth_lib().durf_smooth_keys(_stream(), int(V), T, _z(triangles), _z(ek), _z(ck)), 'durf_smooth_keys')
+    return ek, ck
+
+
+def smooth_workspace_bytes(T):
+    return int(_lib.smooth_lib().durf_smooth_workspace_bytes(int(T)))
+
+
+def smooth_adjacency(edge_keys, corner_keys, V, T, ws=None):
+    """durf_smooth_adjacency: the SORTED keys -> dict offsets [V+1], neighbours [6T], multiplicity [6T], corner_offsets [V+1],
+    corner_tri [3T], all int32; entries past offsets[V] (corner_offsets[V]) are not written"""
+    V, T, dev = int(V), int(T), edge_keys.device
+    assert edge_keys.dtype == torch.int64 and edge_keys.is_contiguous() and edge_keys.numel() == 6 * T, tuple(edge_keys.shape)
+    assert corner_keys.dtype == torch.int64 and corner_keys.is_contiguous() and corner_keys.numel() == 3 * T, tuple(corner_keys.shape)
+    ws = _ws(ws, smooth_workspace_bytes(T), dev)
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    r = dict(offsets=i32(V + 1), neighbours=i32(6 * T), multiplicity=i32(6 * T), corner_offsets=i32(V + 1), corner_tri=i32(3 * T))
+    with _Timed('smooth_adjacency'):
+        _lib.check(_lib.smooth_lib().durf_smooth_adjacency(_stream(), V, T, _z(edge_keys), _z(corner_keys), 6 * T, _p(ws), ws.numel(), _p(r['offsets']),
+                                                           _z(r['neighbours']), _z(r['multiplicity']), _p(r['corner_offsets']), _z(r['corner_tri'])),
+                   'durf_smooth_adjacency')
+    return r
+
+
+def smooth_classify(offsets, multiplicity):
+    """durf_smooth_classify -> vertex_class uint8 [V]"""
+    V = int(offsets.numel()) - 1
+    _i32(offsets, V + 1, 'offsets')
+    cls = torch.empty(V, dtype=torch.uint8, device=offsets.device)
+    with _Timed('smooth_classify'):
+        _lib.check(_lib.smooth_lib().durf_smooth_classify(_stream(), V, _p(offsets), _z(multiplicity), _z(cls)), 'durf_smooth_classify')
+    return cls
+
+
+def smooth_census(adj):
+    """durf_smooth_census -> int32 [SMOOTH_CENSUS_INTS] on the device"""
+    V = int(adj['offsets'].numel()) - 1
+    out = torch.empty(SMOOTH_CENSUS_INTS, dtype=torch.int32, device=adj['offsets'].device)
+    with _Timed('smooth_census'):
+        _lib.check(_lib.smooth_lib().durf_smooth_census(_stream(), V, _p(adj['offsets']), _z(adj['neighbours']), _z(adj['multiplicity']),
+                                                        _p(adj['corner_offsets']), _z(adj['vertex_class']), _p(out)), 'durf_smooth_census')
+    return out
+
+
+def _smooth_rows(adj, vertices, fixed):
+    V = int(adj['offsets'].numel()) - 1
+    assert _f32(vertices).numel() == 3 * V, (tuple(vertices.shape), V)
+    assert adj['vertex_class'].dtype == torch.uint8 and adj['vertex_class'].numel() == V
+    assert fixed is None or (fixed.dtype == torch.uint8 and fixed.is_contiguous() and fixed.numel() == V), (V,)
+    return V
+
+
+def smooth_step(adj, vertices, factor, boundary=0, fixed=None):
+    """durf_smooth_step: vertices [V,3] -> a new [V,3]"""
+    V = _smooth_rows(adj, vertices, fixed)
+    out = torch.empty_like(vertices)
+    with _Timed('smooth_step'):
+        _lib.check(_lib.smooth_lib().durf_smooth_step(_stream(), V, _z(vertices), _p(adj['offsets']), _z(adj['neighbours']), _z(adj['multiplicity']),
+                                                      _z(adj['vertex_class']), float(factor), int(boundary), _z(fixed), _z(out)), 'durf_smooth_step')
+    return out
+
+
+def smooth_taubin(adj, vertices, iters, lam, mu, boundary=0, fixed=None):
+    """durf_smooth_taubin: vertices [V,3] -> a new [V,3] after iters iterations (lam then mu; mu == 0: lam alone)"""
+    V = _smooth_rows(adj, vertices, fixed)
+    out, tmp = torch.empty_like(vertices), torch.empty_like(vertices)
+    with _Timed('smooth_taubin'):
+        _lib.check(_lib.smooth_lib().durf_smooth_taubin(_stream(), V, _z(vertices), _p(adj['offsets']), _z(adj['neighbours']), _z(adj['multiplicity']),
+                                                        _z(adj['vertex_class']), int(iters), float(lam), float(mu), int(boundary), _z(fixed), _z(tmp),
+                                                        _z(out)), 'durf_smooth_taubin')
+    return out
+
+
+def smooth_normals(adj, vertices, triangles):
+    """durf_smooth_normals: area-weighted vertex normals [V,3] over the corner rows of adj"""
+    V, T = _mesh(vertices, triangles)
+    assert adj['corner_offsets'].numel() == V + 1, (V,)
+    normals = torch.empty_like(vertices)
+    with _Timed('smooth_normals'):
+        _lib.check(_lib.smooth_lib().durf_smooth_normals(_stream(), V, T, _z(vertices), _z(triangles), _p(adj['corner_offsets']), _z(adj['corner_tri']),
+                                                         _z(normals)), 'durf_smooth_normals')
+    return normals
